@@ -108,6 +108,27 @@ def pmc_traffic(kernel):
     return None, 'kernel not in the PMC table'
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, **arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy.  Row-aligned arrays larger than DUMP_LIMIT_BYTES in all are
+    cut to the same fixed, seeded sample of rows (saved as sample_rows.npy); the config-B outputs are far below it."""
+    rows = max((a.shape[0] for a in arrays.values() if a.ndim), default=0)
+    if sum(a.nbytes for a in arrays.values()) > DUMP_LIMIT_BYTES and rows:
+        aligned = [a for a in arrays.values() if a.ndim and a.shape[0] == rows]
+        fixed = sum(a.nbytes for a in arrays.values()) - sum(a.nbytes for a in aligned)
+        per_row = sum(a.nbytes for a in aligned) // rows + 8           # + the float64 row index
+        keep = max(0, (DUMP_LIMIT_BYTES - fixed - 4096) // per_row)   # 4 KiB for the .npy headers
+        idx = np.sort(np.random.default_rng(0).choice(rows, keep, replace=False))
+        arrays = {k: (a[idx] if a.ndim and a.shape[0] == rows else a) for k, a in arrays.items()}
+        arrays['sample_rows'] = idx.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+    log(f'outputs of the last timed step written to {out_dir}: ' + ', '.join(f'{k} {a.shape}' for k, a in arrays.items()))
+
+
 def prof_report():
     from mmft import lib
     return lib.prof_report()
@@ -259,7 +280,12 @@ def main():
     ap.add_argument('--no-dropin', action='store_true', help='skip the extra timings of the per-level drop-in API')
     ap.add_argument('--cone', action='store_true',
                     help='fan-in-cone pruning inside the step (device-side mask per step; pays when --batch-paths is small)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help="rank 0: write what the last timed step returned (loss, predictions, endpoint ids) as DIR/<name>.npy "
+                         "(float32 / float64); same arguments, same inputs, so two builds can be compared output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error('--steps must be at least 1')
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
@@ -337,6 +363,10 @@ def main():
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     log(f'timed region: {elapsed / args.steps * 1e3:.2f} ms/step')
+    if args.dump_outputs and rank == 0:
+        # copied before anything else runs: a replayed graph returns its static output buffers, which the next replay overwrites
+        dump_outputs(args.dump_outputs, loss=loss.float().cpu().numpy(), predictions=hats.float().cpu().numpy(),
+                     endpoint_ids=np.asarray(tl, dtype=np.float64))
     if dist is not None:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev if dist.get_backend() == 'nccl' else 'cpu')
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)

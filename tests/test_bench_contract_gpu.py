@@ -10,9 +10,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 pytestmark = pytest.mark.gpu
 
 
-def test_bench_line_contract(dev):
+def test_bench_line_contract(dev, tmp_path):
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1', '--designs', '2',
-           '--nodes', '4096', '--levels', '16', '--tile', '64', '--batch-paths', '64']
+           '--nodes', '4096', '--levels', '16', '--tile', '64', '--batch-paths', '64', '--dump-outputs', str(tmp_path)]
     res = subprocess.run(cmd, cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0, res.stderr[-2000:]
     lines = [l for l in res.stdout.splitlines() if l.strip()]
@@ -33,3 +33,10 @@ def test_bench_line_contract(dev):
     assert abs(r['frac'] - r['achieved'] / r['peak']) < 1e-9 and 'traffic' in r
     c = j['cpu_baseline']
     assert c['kind'] in ('port', 'reference') and c['cores'] >= 1 and c['value'] > 0 and isinstance(c['sample'], str)
+    # --dump-outputs: what the last timed step returned (2 designs x 64 sampled paths)
+    import numpy as np
+    assert sorted(os.listdir(tmp_path)) == ['endpoint_ids.npy', 'loss.npy', 'predictions.npy']
+    loss, pred, ids = (np.load(tmp_path / f'{n}.npy') for n in ('loss', 'predictions', 'endpoint_ids'))
+    assert loss.dtype == np.float32 and pred.dtype == np.float32 and ids.dtype == np.float64
+    assert pred.shape == ids.shape == (2 * 64,) and np.isfinite(pred).all()
+    assert float(loss) == j['loss_last_step']

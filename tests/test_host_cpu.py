@@ -211,6 +211,30 @@ def test_bench_pmc_table_lookup(tmp_path, monkeypatch):
     assert val is None and 'stamp' in why
 
 
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """bench.dump_outputs (--dump-outputs): one DIR/<name>.npy per array, dtypes kept; above the size limit the row-aligned
+    arrays are cut to the same fixed, seeded sample of rows (stored as sample_rows.npy) and the whole dump stays under it."""
+    import os
+    import bench
+    loss = np.array(0.25, dtype=np.float32)
+    pred = np.arange(5000, dtype=np.float32) * 0.5
+    ids = np.arange(5000, dtype=np.float64) * 3
+    bench.dump_outputs(str(tmp_path / 'full'), loss=loss, predictions=pred, endpoint_ids=ids)
+    assert sorted(os.listdir(tmp_path / 'full')) == ['endpoint_ids.npy', 'loss.npy', 'predictions.npy']
+    for name, a in (('loss', loss), ('predictions', pred), ('endpoint_ids', ids)):
+        b = np.load(tmp_path / 'full' / (name + '.npy'))
+        assert b.dtype == a.dtype and np.array_equal(a, b), name
+    monkeypatch.setattr(bench, 'DUMP_LIMIT_BYTES', 4096 + 20000)
+    for run in ('s1', 's2'):
+        bench.dump_outputs(str(tmp_path / run), loss=loss, predictions=pred, endpoint_ids=ids)
+        assert sum(os.path.getsize(tmp_path / run / f) for f in os.listdir(tmp_path / run)) <= bench.DUMP_LIMIT_BYTES
+    rows = np.load(tmp_path / 's1' / 'sample_rows.npy')
+    assert 0 < rows.size < 5000 and np.array_equal(rows, np.load(tmp_path / 's2' / 'sample_rows.npy'))
+    assert np.array_equal(np.load(tmp_path / 's1' / 'predictions.npy'), pred[rows.astype(np.int64)])
+    assert np.array_equal(np.load(tmp_path / 's1' / 'endpoint_ids.npy'), ids[rows.astype(np.int64)])
+    assert np.load(tmp_path / 's1' / 'loss.npy') == loss
+
+
 def test_schedule_caches_hold_their_lists_and_stay_bounded():
     """level_set_is_complete / fold_schedule cache per list OBJECTS.  The entry keeps the lists (no id() reuse),
     an equal-length in-place edit of a list is not answered from the cache, and the cache is bounded."""
