@@ -3,9 +3,11 @@
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
 """
+import contextlib
 import ctypes
 import os
 import re
+import threading
 import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -108,26 +110,73 @@ def query(name, *args):
 
 _workspace = {}
 _retired = []
+_scope = threading.local()
+
+
+@contextlib.contextmanager
+def scratch_owner(owner):
+    """with lib.scratch_owner(obj): ...  - `workspace` hands out obj.scratch, a buffer that lives and dies with obj (a replayed
+    graph and the eager calls it was captured from).  Thread-local: autograd runs backward on threads of its own."""
+    prev, _scope.owner = getattr(_scope, 'owner', None), owner
+    try:
+        yield owner
+    finally:
+        _scope.owner = prev
 
 
 def workspace(device, nbytes):
     """Scratch buffer (split-K slabs, BN partials, re-laid-out dgrad weights), grown on demand, never shrunk.
-    One buffer per (device, stream): kernels of the netlist sweep and of the CNN may run concurrently on two
-    streams and must not share scratch."""
+    Inside `scratch_owner(obj)` it is obj.scratch, which may not grow while a capture is running (the eager calls before
+    the capture size it).  Elsewhere there is one buffer per (device, stream): kernels of the netlist sweep and of the CNN
+    may run concurrently on two streams and must not share scratch."""
+    need = max(int(nbytes), 1 << 20)
+    owner = getattr(_scope, 'owner', None)
+    if owner is not None:
+        buf = getattr(owner, 'scratch', None)
+        if buf is None or buf.numel() * 4 < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f'lib.workspace: {need} bytes requested during a capture from a scratch owner that holds '
+                                   f'{0 if buf is None else buf.numel() * 4}')
+            buf = owner.scratch = torch.empty((need + 3) // 4, dtype=torch.float32, device=device)
+        return buf
     dev = torch.device(device)
     idx = dev.index if dev.index is not None else torch.cuda.current_device()
     key = (idx, torch.cuda.current_stream(idx).cuda_stream)
     buf = _workspace.get(key)
-    need = max(int(nbytes), 1 << 20)
     if buf is None or buf.numel() * 4 < need:
         if buf is not None:
-            # a captured HIP graph may hold this buffer's address (the whole-step graph, the U-Net's replay graphs): an
-            # outgrown buffer is retired, never handed back to the allocator for somebody else's tensor
+            # a captured HIP graph may hold this buffer's address (the whole-step graph): an outgrown buffer is retired,
+            # never handed back to the allocator for somebody else's tensor
             _retired.append(buf)
             need = max(need, 2 * buf.numel() * 4)          # geometric growth bounds what the retired ones add up to
         buf = torch.empty((need + 3) // 4, dtype=torch.float32, device=dev)
         _workspace[key] = buf
     return buf
+
+
+class GraphReplay:
+    """One launch sequence of an eager caller replayed from a captured HIP graph: the first call runs it eagerly, the second
+    captures and replays it, later calls only replay.  Owns the scratch of those launches (`scratch_owner`); `keep` holds
+    the other tensors whose addresses the graph bakes in.  Whoever holds it decides when its addresses are still valid."""
+
+    def __init__(self, keep=()):
+        self.keep, self.calls, self.graph, self.scratch = keep, 0, None, None
+
+    def run(self, launches):
+        """launches() on an eager or capturing call (its result returned), None on a pure replay."""
+        self.calls += 1
+        out = None
+        if self.graph is None:
+            with scratch_owner(self):
+                if self.calls < 2:
+                    return launches()
+                torch.cuda.synchronize()
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
+                    out = launches()
+            self.graph = graph
+        self.graph.replay()
+        return out
 
 
 PROF_ON = False

@@ -15,6 +15,7 @@ one pull kernel over the level's OUT-edges (no atomics, bitwise reproducible), a
 two small GEMMs that turn G into DA.  Weight gradients are NOT computed per level: the level-0 node
 (last to run) computes all of them in batched GEMMs over every node of the sweep.
 """
+import contextlib
 import torch
 from . import ops, gradsink, lib
 
@@ -62,6 +63,7 @@ class SweepState:
         self.attn = None                    # attention branch (flag_attn): dict(key, c12, alpha, dcp, o2i)
         self.wpack = None                   # bf16 math mode: fc_cell_neigh pre-packed as bf16 (W1, W2, W2^T, W1^T)
         self.active = None                  # uint8 per node: fan-in cone of the step's endpoints (None: every node)
+        self.record = None                  # _SweepRecord of the schedule (static level lists), or None
         self.spec_lists = None              # speculative drop-in sweep: the level lists it ran with, its token, target rows
         self.spec_token = None
         self.spec_tix = []
@@ -451,19 +453,10 @@ def level_forward(conv, graph, cur_nodes, targets, level_id):
             graph.ndata['h_drive'] = hd
         if rows.numel():
             ops.seg_mean_rows_any(st.net_feat, graph.csr('in', 'net'), rows, hd)
-    if level_id == 0:
-        token = st.h.new_zeros(1)
-        if st.need_grad:
-            st.token, out = LevelFn.apply(token, st, level_id, rows, tix, c12, *st.params)
-        else:
-            with torch.no_grad():
-                st.token, out = LevelFn.apply(token, st, level_id, rows, tix, c12)
-    else:
-        if st.need_grad:
-            st.token, out = LevelFn.apply(st.token, st, level_id, rows, tix, c12)
-        else:
-            with torch.no_grad():
-                st.token, out = LevelFn.apply(st.token, st, level_id, rows, tix, c12)
+    token = st.h.new_zeros(1) if level_id == 0 else st.token
+    params = st.params if (level_id == 0 and st.need_grad) else ()
+    with contextlib.nullcontext() if st.need_grad else torch.no_grad():
+        st.token, out = LevelFn.apply(token, st, level_id, rows, tix, c12, *params)
     return out
 
 
@@ -496,66 +489,65 @@ SWEEP_REPLAY = True      # drop-in loop: the speculative sweep's forward / rever
 _REPLAY_STATE = ('levels', 'wpack', 'hid16', 'HN', 'DHN', 'prep', 'row_sets', 'feat_fused', 'PRE', 'attn')
 
 
-class _SweepReplay:
-    """Captured HIP graphs of ONE speculative whole sweep (the drop-in loop's level-0 call, launched eagerly ~45 + ~70 times
-    per step otherwise): valid while the graph's buffers, the static tables of these level lists, the parameters, their
-    gradient sinks and h keep their addresses (`sig`).  The launches are static: features, lists and buffers do not change
-    from step to step; what does change - the sampled endpoints - is handled by the per-level nodes outside."""
-
+class _SweepRecord:
+    """What eager sweeps of one schedule keep from step to step while the level list objects and the addresses of h, the
+    features, the parameters and their gradient sinks stay (`sig`; the graph's buffers are persistent): `calls`, recorded
+    launches of the two per-level kernels (ops.relaunch); `fwd` / `bwd`, the drop-in loop's level-0 sweep (~45 + ~70
+    launches) as graphs, `state` the sweep state a replayed forward stands for; `keep` = (slot tables, reverse pair tables)
+    that all of these read, which PinGraph's LRU may drop.  The sampled endpoints are handled by the per-level nodes."""
     def __init__(self, sig, lists):
-        self.sig, self.lists = sig, lists
-        self.calls = self.bwd_calls = 0
-        self.fwd = self.bwd = None
-        self.state = None
+        self.sig, self.lists, self.calls, self.state, self.keep = sig, lists, {}, None, (None, None)
+        self.fwd, self.bwd = lib.GraphReplay(), lib.GraphReplay()
 
 
-def _sweep_replay_for(st, tix, c12):
-    """The replay record of this sweep, or None: speculative mode only (no target gather inside the node), gradient sinks on
-    every parameter, recorded-launch preconditions (static lists / buffers), no profiler, no outer capture."""
-    if not SWEEP_REPLAY or tix is not None or c12 is not None or lib.PROF_ON or torch.cuda.is_current_stream_capturing():
+def _sweep_record(st):
+    """The record of this sweep's schedule, or None (no static level lists, a fan-in cone, non-contiguous parameters)."""
+    if st.level_lists is None or st.active is not None or not all(p.is_contiguous() for p in st.params):
         return None
-    if getattr(st, 'level_lists', None) is None or st.active is not None or not st.need_grad:
-        return None
-    recs = [gradsink.of(p) for p in st.params]
-    if any(r is None for r in recs) or lib.get_math_mode() != 'bf16':
-        return None
-    sig = (tuple(id(n) for n in st.level_lists), st.relu, st.h.data_ptr(), tuple(p.data_ptr() for p in st.params),
-           tuple(r[0].data_ptr() for r in recs), st.cell_feat.data_ptr(), st.net_feat.data_ptr())
-    rp = st._bufs.get('replay')
-    if rp is None or rp.sig != sig:
-        rp = st._bufs['replay'] = _SweepReplay(sig, list(st.level_lists))
-    return rp
+    sinks = [gradsink.of(p) for p in st.params]
+    sig = (tuple(id(n) for n in st.level_lists), lib.get_math_mode(), HIDDEN_BF16, st.relu, st.h.data_ptr(),
+           tuple(p.data_ptr() for p in st.params), tuple(r[0].data_ptr() if r is not None else 0 for r in sinks),
+           st.cell_feat.data_ptr(), st.net_feat.data_ptr())
+    rec = st._bufs.get('replay')
+    if rec is None or rec.sig != sig:
+        rec = st._bufs['replay'] = _SweepRecord(sig, list(st.level_lists))     # (the lists are pinned: ids stay theirs)
+    return rec
+
+
+def _pinned(st, i, build):
+    """build(level lists) - PinGraph.level_slots (i = 0) or .level_bwd_pairs (i = 1) - held in the sweep record's keep."""
+    rec = st.record
+    if rec is not None and rec.keep[i] is None:
+        rec.keep = rec.keep[:i] + (build(st.level_lists),) + rec.keep[i + 1:]
+    return build(st.level_lists) if rec is None else rec.keep[i]
 
 
 class SweepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, state, level_rows, tix, c12, anchor, *params):
         st, g = state, state.graph
-        rp = _sweep_replay_for(st, tix, c12)
-        ctx.replay = rp
-        if rp is not None:
-            rp.calls += 1
-            if rp.fwd is not None:
-                st.__dict__.update(rp.state)
-                rp.fwd.replay()
-                ctx.state, ctx.tix, ctx.nparams, ctx.has_c12 = st, tix, len(params), False
-                return st.h.new_zeros(1)
-            if rp.calls >= 2:                                   # second sweep with the same addresses: capture, then replay
-                torch.cuda.synchronize()
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                    SweepFn._forward_launches(ctx, st, g, level_rows, tix, c12, params)
-                rp.fwd, rp.state = graph, {k: st.__dict__.get(k) for k in _REPLAY_STATE}
-                graph.replay()
-                return st.h.new_zeros(1)
-        SweepFn._forward_launches(ctx, st, g, level_rows, tix, c12, params)
+        st.record = rec = _sweep_record(st)
+        ctx.state, ctx.tix, ctx.nparams, ctx.has_c12 = st, tix, len(params), c12 is not None
+        # graph replay: speculative mode only (no target gather inside the node), gradient sinks on every parameter, bf16 mode,
+        # no profiler, no outer capture
+        ctx.replay = rec if (SWEEP_REPLAY and rec is not None and tix is None and c12 is None and st.need_grad and not lib.PROF_ON
+                             and not torch.cuda.is_current_stream_capturing() and lib.get_math_mode() == 'bf16'
+                             and all(gradsink.of(p) is not None for p in st.params)) else None
+        launches = lambda: SweepFn._forward_launches(st, g, level_rows, c12)
+        if ctx.replay is None:
+            launches()
+        else:
+            if rec.fwd.graph is not None:
+                st.__dict__.update(rec.state)
+            rec.fwd.run(launches)
+            rec.state = {k: st.__dict__.get(k) for k in _REPLAY_STATE}
         if tix is None:
             # speculative drop-in sweep: the per-level target gathers (TargetGatherFn) hang off this token
             return st.h.new_zeros(1)
         return ops.gather_rows(st.h, tix) if tix.numel() else st.h.new_zeros((0, st.D))
 
     @staticmethod
-    def _forward_launches(ctx, st, g, level_rows, tix, c12, params):
+    def _forward_launches(st, g, level_rows, c12):
         """Every launch of the forward sweep (and the python-side state of `st` the backward needs)."""
         st.attn = _attn_state(st, g, c12) if c12 is not None else None
         P = [_w(p) for p in st.params]
@@ -580,17 +572,8 @@ class SweepFn(torch.autograd.Function):
         st.hid16 = bool(HIDDEN_BF16 and st.wpack is not None and isinstance(rc2, tuple) and st.attn is None)
         st.HN = st._buf('HN16', st.Hd, torch.bfloat16) if st.hid16 else st._buf('HN', st.Hd)
         st.DHN = None
-        # Recorded launches of the two per-level kernels (ops.relaunch): valid while the sweep's buffers (persistent per graph),
-        # the static tables of these level lists, the parameters and h are the same objects at the same addresses
-        # (the per-level list OBJECTS identify the schedule: the outer list is rebuilt by the drop-in loop's bookkeeping)
-        sig = (tuple(id(n) for n in st.level_lists) if getattr(st, 'level_lists', None) is not None else None, st.hid16, st.relu,
-               st.h.data_ptr(), st.active is None, tuple(p.data_ptr() for p in P))
-        prep = st._bufs.get('prep')
-        if not RECORD_LAUNCHES or getattr(st, 'level_lists', None) is None or st.active is not None:
-            prep = None
-        elif prep is None or prep['sig'] != sig:
-            prep = st._bufs['prep'] = dict(sig=sig, lists=list(st.level_lists), calls={})       # (the lists are pinned: ids stay theirs)
-        st.prep = prep
+        # recorded launches of the two per-level kernels (ops.relaunch), kept in the sweep's record
+        st.prep = prep = st.record.calls if (RECORD_LAUNCHES and st.record is not None) else None
         dev_, stream_ = lib.stream_args(st.h)
         rn = _cat_rows(st, lambda l: l % 2 == 1)
         st.row_sets = (_cat_rows(st, lambda l: l % 2 == 0), rn, rc2)
@@ -627,8 +610,8 @@ class SweepFn(torch.autograd.Function):
             # folded chain: one gather launch per (net level l - 1, cell level l) pair + the fused MLP of the cell level
             L = len(level_rows)
             drv = g.cell_edge_drivers() if EDGE_DRIVERS else None
-            slot_tabs = g.level_slots(st.level_lists) if (LEVEL_SLOTS and FUSE_LEVEL_FWD and st.wpack is not None
-                                                         and getattr(st, 'level_lists', None) is not None) else None
+            slot_tabs = _pinned(st, 0, g.level_slots) if (LEVEL_SLOTS and FUSE_LEVEL_FWD and st.wpack is not None
+                                                          and st.level_lists is not None) else None
             for level_id in range(2, L + 1, 2):
                 net_l = level_id - 1
                 has_cell = level_id < L and level_rows[level_id].numel() > 0
@@ -640,12 +623,14 @@ class SweepFn(torch.autograd.Function):
                 if has_cell:
                     crow = fold[level_id]['range'] or level_rows[level_id]
                 fused = has_cell and st.wpack is not None and fold[level_id]['heavy_in'] is None and FUSE_LEVEL_FWD
+                # gather bytes of the pair + what the MLP part must move per cell row: h read and written (2 x 4 D) and the
+                # hidden row kept for the reverse sweep (4 Hd or 2 Hd)
                 level_bytes = (meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if meta_c else 0) + \
                     (level_rows[level_id].numel() * (8 * st.D + (2 if st.hid16 else 4) * st.Hd) if (meta_c and has_cell) else 0)
                 if fused and slot_tabs is not None and fold[level_id]['range'] is not None and slot_tabs[2][level_id] <= 4 and \
                         (fold[net_l]['range'] is not None or not fold[net_l]['n']):
                     # ... with the static slot table instead of the per-edge index chain, net rows inside the cell workgroups
-                    rec = prep['calls'].get(('f', level_id)) if prep is not None else None
+                    rec = prep.get(('f', level_id)) if prep is not None else None
                     if rec is not None:
                         ops.relaunch('mmft_level_fwd_slots', rec, dev_, stream_)
                         continue
@@ -653,16 +638,13 @@ class SweepFn(torch.autograd.Function):
                                               st.A, st.LSE, st.wpack[0], b1g, st.wpack[1], b2g, st.HN, relu=st.relu, active=st.active,
                                               alg_bytes=level_bytes)
                     if prep is not None:
-                        prep['calls'][('f', level_id)] = rec
+                        prep[('f', level_id)] = rec
                     continue
                 if fused:
                     # bf16 mode: gather + fc_cell_neigh of the pair in ONE launch
                     ops.level_fwd_bf16(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.A, st.LSE,
                                        st.wpack[0], b1g, st.wpack[1], b2g, st.HN, relu=st.relu, active=st.active, in_cell_driver=drv,
-                                       # gather bytes of the pair + what the MLP part must move per cell row: h read and
-                                       # written (2 x 4 D) and the hidden row kept for the reverse sweep (4 Hd)
-                                       alg_bytes=(meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if meta_c else 0)
-                                       + (level_rows[level_id].numel() * (8 * st.D + (2 if st.hid16 else 4) * st.Hd) if meta_c else 0))
+                                       alg_bytes=level_bytes)
                     continue
                 ops.pair_fwd_gather(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.A, st.LSE,
                                     relu=st.relu, heavy=fold[level_id]['heavy_in'] if has_cell else None, active=st.active,
@@ -683,8 +665,6 @@ class SweepFn(torch.autograd.Function):
             else:
                 ops.seg_softmax_sum_fwd(st.h, in_cell, spec, st.A, st.LSE, alg_bytes=meta['bytes_softmax'] if meta else 0)
                 _cell_neigh_fwd(st, rows, w1g, b1g, w2g, b2g, act)
-        ctx.state, ctx.tix, ctx.nparams = st, tix, len(params)
-        ctx.has_c12 = c12 is not None
 
     @staticmethod
     def backward(ctx, gout):
@@ -708,31 +688,19 @@ class SweepFn(torch.autograd.Function):
                 ops.target_rows_begin(st.G, tix, st.tflag)
             ops.scatter_add_targets(st.G, tix, ops.strided_rows(gout),
                                     order=st.target_order, unique=st.targets_unique)
-        rp = getattr(ctx, 'replay', None)
-        recs = [gradsink.of(p) for p in st.params]
-        replayable = (rp is not None and fast and ctx.tix is None and not ctx.has_c12 and ctx.nparams == len(st.params)
-                      and not torch.cuda.is_current_stream_capturing() and not lib.PROF_ON
-                      and all(r is not None and r[1] != gradsink._epoch[0] for r in recs))      # every sink still fresh this step
-        if replayable:
-            rp.bwd_calls += 1
-            if rp.bwd is not None:
-                st.DHN = st._bufs.get('DHN16' if getattr(st, 'hid16', False) else 'DHN')
-                rp.bwd.replay()
-                for r in recs:
-                    gradsink._mark(r)
-                grads = [None] * ctx.nparams
-            else:
-                if rp.bwd_calls >= 2:
-                    torch.cuda.synchronize()
-                    graph = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(graph, capture_error_mode='thread_local'):
-                        grads = SweepFn._backward_launches(ctx, st, g, fast, own)
-                    rp.bwd = graph
-                    graph.replay()
-                else:
-                    grads = SweepFn._backward_launches(ctx, st, g, fast, own)
+        rec, sinks = ctx.replay, [gradsink.of(p) for p in st.params]
+        launches = lambda: SweepFn._backward_launches(ctx, st, g, fast, own)
+        if not (rec is not None and fast and ctx.nparams == len(st.params) and not torch.cuda.is_current_stream_capturing()
+                and not lib.PROF_ON and all(r is not None and r[1] != gradsink._epoch[0] for r in sinks)):   # sinks fresh
+            grads = launches()
+        elif rec.bwd.graph is not None:
+            st.DHN = st._bufs.get('DHN16' if getattr(st, 'hid16', False) else 'DHN')
+            rec.bwd.run(launches)
+            for r in sinks:
+                gradsink._mark(r)
+            grads = [None] * ctx.nparams
         else:
-            grads = SweepFn._backward_launches(ctx, st, g, fast, own)
+            grads = rec.bwd.run(launches)
         dc = None
         if ctx.has_c12:
             rc2 = st.row_sets[2]
@@ -753,8 +721,8 @@ class SweepFn(torch.autograd.Function):
         out_net, out_cell, in_net_ptr = g.csr('out', 'net'), g.csr('out', 'cell'), g.out_net_weight()
         pairs = None
         if LEVEL_BWD_PAIRS and fast and st.fold is not None and st.wpack is not None and st.attn is None \
-                and getattr(st, 'level_lists', None) is not None:
-            pairs = g.level_bwd_pairs(st.level_lists)
+                and st.level_lists is not None:
+            pairs = _pinned(st, 1, g.level_bwd_pairs)
         paired = set()
         prep = getattr(st, 'prep', None) if fast else None
         dev_b, stream_b = lib.stream_args(st.h)
@@ -775,7 +743,7 @@ class SweepFn(torch.autograd.Function):
                     mn = st.level_meta[cell_l + 1] if (st.level_meta and cell_l + 1 < len(st.level_meta)) else None
                     nb = (mc['bytes_pull'] if mc else 0) + (mn['bytes_pull'] if mn else 0) + \
                         (pr['n_cell'] * (8 * st.D + (4 if st.hid16 else 8) * st.Hd) if cell_l > 0 else 0)
-                    rec = prep['calls'].get(('b', cell_l)) if prep is not None else None
+                    rec = prep.get(('b', cell_l)) if prep is not None else None
                     if rec is not None:
                         ops.relaunch('mmft_level_bwd_pair', rec, dev_b, stream_b)
                         continue
@@ -783,7 +751,7 @@ class SweepFn(torch.autograd.Function):
                                              cslots, out_cell, pscratch, pcounters, st.wpack[2], st.wpack[3], st.HN, st.DHN, relu=st.relu,
                                              has_mlp=cell_l > 0, alg_bytes=nb)
                     if prep is not None:
-                        prep['calls'][('b', cell_l)] = rec
+                        prep[('b', cell_l)] = rec
                     continue
             if not rows.numel():
                 continue

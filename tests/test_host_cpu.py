@@ -445,3 +445,31 @@ def test_level_bwd_pair_tables_cover_every_driver_and_sink_once():
             drivers[v0 - row0] += 1
         assert (drivers == 1).all() and (sinks == 1).all()
     assert heavy_seen > 0
+
+
+def test_scratch_owner_scopes_workspace_to_its_owner(monkeypatch):
+    """Inside lib.scratch_owner(obj) the workspace is obj.scratch (grown eagerly, never during a capture); the scope is
+    per thread and restores the enclosing one; outside it the (device, stream) buffers are not touched."""
+    import threading
+    monkeypatch.setattr(torch.cuda, 'is_current_stream_capturing', lambda: False)
+    before = dict(lib._workspace)
+    a, b = lib.GraphReplay(), lib.GraphReplay()
+    with lib.scratch_owner(a):
+        wa = lib.workspace('cpu', 100)
+        assert wa is a.scratch and wa.numel() * 4 >= 1 << 20
+        assert lib.workspace('cpu', 1000) is wa
+        with lib.scratch_owner(b):
+            assert lib.workspace('cpu', 100) is b.scratch is not wa
+            seen = []
+            t = threading.Thread(target=lambda: seen.append(getattr(lib._scope, 'owner', None)))
+            t.start()
+            t.join()
+            assert seen == [None]
+        grown = lib.workspace('cpu', 4 << 20)
+        assert grown is a.scratch and grown.numel() * 4 >= 4 << 20
+        monkeypatch.setattr(torch.cuda, 'is_current_stream_capturing', lambda: True)
+        assert lib.workspace('cpu', 4 << 20) is grown
+        with pytest.raises(RuntimeError, match='during a capture'):
+            lib.workspace('cpu', 8 << 20)
+    assert getattr(lib._scope, 'owner', None) is None
+    assert lib._workspace == before

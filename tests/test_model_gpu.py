@@ -778,7 +778,7 @@ def test_dropin_unet_graph_replay_in_bf16_mode(dev):
                         with torch.no_grad():
                             cnn(torch.rand(1, 3, 32, 64, device=dev))
                 rp = cnn.__dict__.get('_u16_replay')
-                assert (rp is not None and rp.fwd is not None and rp.bwd is not None) == replay
+                assert (rp is not None and rp.fwd.graph is not None and rp.bwd.graph is not None) == replay
                 out[replay] = (losses, ts.optim.flat_param.clone())
                 if replay:                                   # two forwards, then both backwards: the second takes fresh buffers
                     x = ts.batch.images
@@ -815,10 +815,58 @@ def test_dropin_sweep_opt_in_paths_equal_the_default(dev):
                 torch.cuda.synchronize()
                 rp = ts.batch.graph.__dict__.get('_sweep_bufs', {}).get('replay')
                 if name == 'replay':
-                    assert rp is not None and rp.fwd is not None and rp.bwd is not None     # the graphs were captured and used
+                    assert rp is not None and rp.fwd.graph is not None and rp.bwd.graph is not None   # captured and used
                 out[name] = (losses, ts.optim.flat_param.clone())
     finally:
         S.SPEC_SIDE_STREAM, S.SWEEP_REPLAY, S.RECORD_LAUNCHES = saved
     for name in ('side', 'replay', 'plain'):
         assert out[name][0] == out['default'][0], name
         assert torch.equal(out[name][1], out['default'][1]), name
+
+
+def test_dropin_replayed_graphs_own_their_scratch_and_tables(dev):
+    """bf16 drop-in loop: the sweep's reverse graph (replayed on the sweep's own stream) and the U-Net's backward graph
+    (replayed on the caller's stream, concurrently) each own their scratch - disjoint buffers, neither a stream-keyed
+    lib.workspace buffer.  The sweep record keeps the slot and pair tables its recorded launches and graphs read: once
+    PinGraph's schedule cache has dropped them, one more step still equals training without replay bit for bit."""
+    from mmft import lib, sweep as S, unet16
+    from mmft.synth import synth_design
+    from mmft.train import build_models, TrainStep
+    designs = [synth_design(N=6000, L=12, tile=64, seed=420 + i, end_frac=0.2) for i in range(2)]
+    rng = np.random.default_rng(7)
+    batches = [[rng.permutation(d.num_paths)[:60] for d in designs] for _ in range(6)]
+    span = lambda t: (t.data_ptr(), t.data_ptr() + t.numel() * t.element_size())
+    disjoint = lambda a, b: span(a)[1] <= span(b)[0] or span(b)[1] <= span(a)[0]
+    out = {}
+    saved = (S.SWEEP_REPLAY, unet16.REPLAY)
+    try:
+        with lib.math_mode('bf16'):
+            for replay in (False, True):
+                S.SWEEP_REPLAY = unet16.REPLAY = replay
+                pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=11)
+                ts = TrainStep(pmodel, cnn, designs, dev, mode='dropin')
+                losses = [float(ts.step(ids)[0]) for ids in batches[:5]]
+                g = ts.batch.graph
+                rec = g._sweep_bufs['replay']
+                tables = rec.keep
+                if replay:
+                    u16 = cnn._u16_replay
+                    assert rec.bwd.graph is not None and u16.bwd.graph is not None
+                    a, b = rec.bwd.scratch, u16.bwd.scratch
+                    assert disjoint(a, b)
+                    assert all(disjoint(a, w) and disjoint(b, w) for w in list(lib._workspace.values()) + lib._retired)
+                    assert tables[0] is g.level_slots(rec.lists) and tables[1] is g.level_bwd_pairs(rec.lists)
+                for _ in range(g.LIST_CACHE_MAX):             # the same schedule in new list objects: other cache entries
+                    other = [list(n) for n in rec.lists]
+                    g.level_slots(other)
+                    g.level_bwd_pairs(other)
+                assert ('slots',) + g._lists_key(rec.lists) not in g._level_cache
+                assert ('bwd_pairs',) + g._lists_key(rec.lists) not in g._level_cache
+                losses.append(float(ts.step(batches[5])[0]))
+                torch.cuda.synchronize()
+                assert g._sweep_bufs['replay'] is rec and rec.keep[0] is tables[0] and rec.keep[1] is tables[1]
+                out[replay] = (losses, ts.optim.flat_param.clone())
+    finally:
+        S.SWEEP_REPLAY, unet16.REPLAY = saved
+    assert out[True][0] == out[False][0]
+    assert torch.equal(out[True][1], out[False][1])
