@@ -19,6 +19,10 @@ What each function follows (paths relative to /root/reference):
   layoutnet_forward   src/model.py:216-247
   train_step          src/train.py:475-562    one mini-batch step incl. MSE, backward, Adam
 
+rounding='bf16' (mlp, pathconv_level, pathmodel_level, unet_forward, sweep_forward, OracleTrainer): the same functions
+rounded to bf16 exactly where the bf16 math mode rounds (oracle/bf16.py: primitives and the rounding map).  With the
+default rounding=None every function runs the code it always ran, bit for bit.
+
 Pinning status:
   * unet_forward / layoutnet_forward / mlp / pathmodel fusion / the PathConv UDFs are pinned
     against the reference's own code (tests/golden/make_golden.py runs src/Unet.py as-is and
@@ -34,16 +38,22 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
+from . import bf16 as B
+
 
 # --------------------------------------------------------------------------- MLP (src/model.py:10-24)
-def mlp(p, prefix, x, slope=0.0):
-    """Sequential of Linear layers at indices 0,2,4,...; LeakyReLU(slope) between them."""
+def mlp(p, prefix, x, slope=0.0, rounding=None, stored_hidden=False):
+    """Sequential of Linear layers at indices 0,2,4,...; LeakyReLU(slope) between them.
+    rounding='bf16': every layer is B.linear_bf16; stored_hidden: the hidden activations are kept as bf16 (B.stored)."""
     idx = sorted({int(k[len(prefix) + len('layers.'):].split('.')[0]) for k in p
                   if k.startswith(prefix + 'layers.') and k.endswith('.weight')})
+    lin = B.linear_bf16 if rounding else F.linear
     for j, i in enumerate(idx):
-        x = F.linear(x, p[f'{prefix}layers.{i}.weight'], p[f'{prefix}layers.{i}.bias'])
+        x = lin(x, p[f'{prefix}layers.{i}.weight'], p[f'{prefix}layers.{i}.bias'])
         if j < len(idx) - 1:
             x = F.leaky_relu(x, negative_slope=slope)
+            if stored_hidden:
+                x = B.stored(x)
     return x
 
 
@@ -106,7 +116,8 @@ def seg_attn_sum(h, key, indptr, indices, nodes, w_key, w_attn):
 
 
 # --------------------------------------------------------------------------- PathConv.forward
-def pathconv_level(p, prefix, csr, h, cell_feat, net_feat, cur_nodes, targets, level_id, activation=True, key=None):
+def pathconv_level(p, prefix, csr, h, cell_feat, net_feat, cur_nodes, targets, level_id, activation=True, key=None,
+                   rounding=None):
     """One call of PathConv.forward (src/model.py:158-213). Returns (h_new, h_new[targets]).
 
     csr = {'net': (indptr, indices), 'cell': (indptr, indices)} numpy int64, in-edges by dst.
@@ -114,23 +125,29 @@ def pathconv_level(p, prefix, csr, h, cell_feat, net_feat, cur_nodes, targets, l
     key (N, 1): ndata['key'] -> the flag_attn=True branch (src/model.py:190-198); its second pull only fills
     ndata['h_drive'] (mean of net_feat over net in-edges, src/model.py:197-198,66-86), which nothing reads - see
     pathconv_h_drive.
+    rounding: the feature MLPs and fc_cell_neigh on bf16 operands ('sweep'), fc_cell_neigh's hidden rows stored as bf16
+    ('hidden'); gathers and sums stay unrounded (oracle/bf16.py).
     """
+    rc = B.classes(rounding)
+    mr = 'bf16' if 'sweep' in rc else None
+    neigh = dict(rounding=mr, stored_hidden='hidden' in rc) if rc else {}
+    feat = dict(rounding=mr) if rc else {}
     idx = torch.as_tensor(np.asarray(cur_nodes, dtype=np.int64))
     if len(cur_nodes):
         if level_id % 2 == 1:
             a = seg_mean(h, *csr['net'], cur_nodes)                                     # :186-187
-            rows = mlp(p, prefix + 'fc_net_self.', net_feat[idx]) + a                   # :103-109
+            rows = mlp(p, prefix + 'fc_net_self.', net_feat[idx], **feat) + a           # :103-109
         elif level_id == 0:
-            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx])                     # :148-153
+            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx], **feat)             # :148-153
         elif key is not None:
             a = seg_attn_sum(h, key, *csr['cell'], cur_nodes, p[prefix + 'fc_key.weight'],
                              p[prefix + 'fc_attn.weight'])                              # :119-136,190-196
-            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx]) + \
-                mlp(p, prefix + 'fc_cell_neigh.', a)
+            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx], **feat) + \
+                mlp(p, prefix + 'fc_cell_neigh.', a, **neigh)
         else:
             a = seg_softmax_sum(h, *csr['cell'], cur_nodes)                             # :113-116
-            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx]) + \
-                mlp(p, prefix + 'fc_cell_neigh.', a)                                    # :138-146
+            rows = mlp(p, prefix + 'fc_cell_self.', cell_feat[idx], **feat) + \
+                mlp(p, prefix + 'fc_cell_neigh.', a, **neigh)                           # :138-146
         if activation:
             rows = torch.relu(rows)                                                     # :206-208
         h = h.index_copy(0, idx, rows)
@@ -146,14 +163,18 @@ def pathconv_h_drive(csr, net_feat, cur_nodes):
 
 # --------------------------------------------------------------------------- PathModel.forward
 def pathmodel_level(p, csr, h, cell_feat, net_feat, nodes, targets, level_id, level_id_th, path_map,
-                    has_gnn=True, has_fcn=True):
-    """One call of PathModel.forward (src/model.py:269-292). Returns (h_new, prediction | None)."""
+                    has_gnn=True, has_fcn=True, rounding=None):
+    """One call of PathModel.forward (src/model.py:269-292). Returns (h_new, prediction | None).
+    rounding: the sweep as in pathconv_level, mlp_alpha / mlp_fuse on bf16 operands ('head'); fcn stays fp32."""
     T = len(targets)
+    rc = B.classes(rounding)
+    head = dict(rounding='bf16' if 'head' in rc else None) if rc else {}
+    sweep = dict(rounding=rc) if rc else {}
     h_cnn = F.linear(path_map, p['fcn.weight'], p['fcn.bias']) if (has_fcn and T != 0) else None
     h_gnn = None
     if has_gnn:
-        h, h_gnn = pathconv_level(p, 'gnn.', csr, h, cell_feat, net_feat, nodes, targets, level_id)
-    h_global = mlp(p, 'mlp_alpha.', level_id_th).expand(T, 32)
+        h, h_gnn = pathconv_level(p, 'gnn.', csr, h, cell_feat, net_feat, nodes, targets, level_id, **sweep)
+    h_global = mlp(p, 'mlp_alpha.', level_id_th, **head).expand(T, 32)
     if T == 0:
         return h, None
     if h_cnn is None:
@@ -162,7 +183,7 @@ def pathmodel_level(p, csr, h, cell_feat, net_feat, nodes, targets, level_id, le
         z = torch.cat([h_cnn, h_global], dim=1)
     else:
         z = torch.cat((h_gnn, h_cnn, h_global), 1)
-    return h, mlp(p, 'mlp_fuse.', z).squeeze(-1)
+    return h, mlp(p, 'mlp_fuse.', z, **head).squeeze(-1)
 
 
 # --------------------------------------------------------------------------- U-Net (src/Unet.py)
@@ -176,7 +197,40 @@ def _bn_train(p, prefix, x, update_running=True, momentum=0.1, eps=1e-5):
     return y
 
 
-def _double_conv(p, prefix, x, update_running):
+def _bn_split(p, prefix, z, z_stats, update_running=True, momentum=0.1, eps=1e-5):
+    """Train-mode BatchNorm of z with the batch statistics of z_stats (the 'bnstats' ablation: statistics of the unrounded
+    z applied to the rounded one)."""
+    mean, var = z_stats.mean((0, 2, 3)), z_stats.var((0, 2, 3), unbiased=False)
+    c = lambda t: t[None, :, None, None]
+    y = (z - c(mean)) / c(torch.sqrt(var + eps)) * c(p[prefix + 'weight']) + c(p[prefix + 'bias'])
+    rm, rv = p.get(prefix + 'running_mean'), p.get(prefix + 'running_var')
+    if update_running and rm is not None:
+        n = z_stats.numel() // z_stats.shape[1]
+        with torch.no_grad():
+            rm.mul_(1 - momentum).add_(momentum * mean)
+            rv.mul_(1 - momentum).add_(momentum * var * n / (n - 1))
+        if (prefix + 'num_batches_tracked') in p:
+            p[prefix + 'num_batches_tracked'] += 1
+    return y
+
+
+def _conv_bn_relu_r(p, cprefix, bprefix, x, update_running, rc):
+    """Conv2d(3x3, pad 1) -> BatchNorm -> ReLU of the bf16-storage U-Net: z rounded on store with the statistics taken of
+    the rounded z, a = relu(bn(z)) rounded on store; every gradient through a stored tensor rounded."""
+    st = lambda t: B.stored(t, value='act' in rc, grad='grad' in rc)
+    z0 = B.conv2d_bf16(x, p[cprefix], 1) if 'conv' in rc else F.conv2d(x, p[cprefix], None, padding=1)
+    z = st(z0)
+    if 'act' in rc and 'bnstats' not in rc:
+        y = _bn_split(p, bprefix, z, z0, update_running)
+    else:
+        y = _bn_train(p, bprefix, z, update_running)
+    return st(torch.relu(y))
+
+
+def _double_conv(p, prefix, x, update_running, rc=frozenset()):
+    if rc:
+        x = _conv_bn_relu_r(p, prefix + 'double_conv.0.weight', prefix + 'double_conv.1.', x, update_running, rc)
+        return _conv_bn_relu_r(p, prefix + 'double_conv.3.weight', prefix + 'double_conv.4.', x, update_running, rc)
     x = F.conv2d(x, p[prefix + 'double_conv.0.weight'], None, padding=1)
     x = torch.relu(_bn_train(p, prefix + 'double_conv.1.', x, update_running))
     x = F.conv2d(x, p[prefix + 'double_conv.3.weight'], None, padding=1)
@@ -184,19 +238,26 @@ def _double_conv(p, prefix, x, update_running):
     return x
 
 
-def _pool(x, pooling):
-    return F.max_pool2d(x, 2) if pooling == 'max' else F.avg_pool2d(x, 2)
+def _pool(x, pooling, rc=frozenset()):
+    y = F.max_pool2d(x, 2) if pooling == 'max' else F.avg_pool2d(x, 2)
+    return B.stored(y, value='act' in rc, grad='grad' in rc) if rc else y
 
 
-def _up(p, prefix, x1, x2, update_running, bilinear=False):
-    """Up.forward (src/Unet.py:56-68); bilinear=True: nn.Upsample(scale_factor=2, 'bilinear', align_corners=True) (:50)."""
+def _up(p, prefix, x1, x2, update_running, bilinear=False, rc=frozenset()):
+    """Up.forward (src/Unet.py:56-68); bilinear=True: nn.Upsample(scale_factor=2, 'bilinear', align_corners=True) (:50).
+    rc (bf16 rounding classes): ConvTranspose2d on bf16 operands, the concatenation stored as bf16."""
     if bilinear:
         x1 = F.interpolate(x1, scale_factor=2, mode='bilinear', align_corners=True)
+    elif 'conv' in rc:
+        x1 = B.conv_transpose2d_bf16(x1, p[prefix + 'up.weight'], p[prefix + 'up.bias'])
     else:
         x1 = F.conv_transpose2d(x1, p[prefix + 'up.weight'], p[prefix + 'up.bias'], stride=2)
     dy, dx = x2.shape[2] - x1.shape[2], x2.shape[3] - x1.shape[3]
     x1 = F.pad(x1, [dx // 2, dx - dx // 2, dy // 2, dy - dy // 2])
-    return _double_conv(p, prefix + 'conv.', torch.cat([x2, x1], dim=1), update_running)
+    cat = torch.cat([x2, x1], dim=1)
+    if rc:
+        cat = B.stored(cat, value='act' in rc, grad='grad' in rc)
+    return _double_conv(p, prefix + 'conv.', cat, update_running, rc)
 
 
 def up_block(p, x1, x2, bilinear, update_running=True):
@@ -204,17 +265,19 @@ def up_block(p, x1, x2, bilinear, update_running=True):
     return _up(p, '', x1, x2, update_running, bilinear)
 
 
-def unet_forward(p, x, pooling='max', update_running=True):
-    """UNet.forward (src/Unet.py:110-119), BatchNorm in train mode. Accepts (C,H,W) too (D3)."""
+def unet_forward(p, x, pooling='max', update_running=True, rounding=None):
+    """UNet.forward (src/Unet.py:110-119), BatchNorm in train mode. Accepts (C,H,W) too (D3).
+    rounding='bf16': the bf16-storage U-Net (oracle/bf16.py); OutConv keeps fp32 weights and an fp32 output."""
+    rc = B.classes(rounding)
     if x.dim() == 3:
         x = x.unsqueeze(0)
-    x1 = _double_conv(p, 'inc.', x, update_running)
-    x2 = _double_conv(p, 'down1.maxpool_conv.1.', _pool(x1, pooling), update_running)
-    x3 = _double_conv(p, 'down2.maxpool_conv.1.', _pool(x2, pooling), update_running)
-    x4 = _double_conv(p, 'down3.maxpool_conv.1.', _pool(x3, pooling), update_running)
-    y = _up(p, 'up1.', x4, x3, update_running)
-    y = _up(p, 'up2.', y, x2, update_running)
-    y = _up(p, 'up3.', y, x1, update_running)
+    x1 = _double_conv(p, 'inc.', x, update_running, rc)
+    x2 = _double_conv(p, 'down1.maxpool_conv.1.', _pool(x1, pooling, rc), update_running, rc)
+    x3 = _double_conv(p, 'down2.maxpool_conv.1.', _pool(x2, pooling, rc), update_running, rc)
+    x4 = _double_conv(p, 'down3.maxpool_conv.1.', _pool(x3, pooling, rc), update_running, rc)
+    y = _up(p, 'up1.', x4, x3, update_running, rc=rc)
+    y = _up(p, 'up2.', y, x2, update_running, rc=rc)
+    y = _up(p, 'up3.', y, x1, update_running, rc=rc)
     y = F.conv2d(y, p['outc.conv.0.weight'], p['outc.conv.0.bias'])
     return torch.relu(_pool(y, pooling))
 
@@ -250,14 +313,22 @@ def bucket_paths(path_ids, path2level, path2endpoint):
 
 
 def sweep_forward(pm, pc, design, csr, path_ids, pooling='max', update_running=True, dtype=torch.float32,
-                  cnn_kind='unet'):
+                  cnn_kind='unet', rounding=None, feat_map=None):
     """U-Net forward + L-level sweep + fusion head for one endpoint batch (src/train.py:465,475-511).
 
     pm: PathModel params (gnn.*, fcn.*, mlp_fuse.*, mlp_alpha.*), pc: CNN params.
+    rounding='bf16': the bf16 math mode's rounding (U-Net only for the CNN).
+    feat_map: a given CNN output (any shape with map_size^2 elements) used instead of running the CNN - the sweep and the
+    head compared on their own, without the CNN's last-bit sensitivity.
     Returns (label_hats (T,), target_list, feat_map)."""
     img = torch.from_numpy(design.image).to(dtype)
-    if cnn_kind == 'unet':
-        feat_map = unet_forward(pc, img, pooling, update_running).reshape(1, -1)
+    extra = dict(rounding=rounding) if rounding is not None else {}
+    if feat_map is not None:
+        feat_map = feat_map.reshape(1, -1)
+    elif cnn_kind == 'unet':
+        feat_map = unet_forward(pc, img, pooling, update_running, **extra).reshape(1, -1)
+    elif rounding is not None:
+        raise NotImplementedError('rounding: the bf16-storage CNN is the U-Net')
     else:
         feat_map = layoutnet_forward(pc, img, pooling).reshape(1, -1)
     D = pm['gnn.fc_cell_self.layers.2.weight'].shape[0]
@@ -276,7 +347,7 @@ def sweep_forward(pm, pc, design, csr, path_ids, pooling='max', update_running=T
         if len(pids):
             path_map = dense_mask_rows(design.mask_indptr, design.mask_cols, pids, P, dtype) * feat_map
         lvl = torch.tensor([float(level_id)], dtype=dtype)
-        h, y = pathmodel_level(pm, csr, h, cell_feat, net_feat, nodes, targets, level_id, lvl, path_map)
+        h, y = pathmodel_level(pm, csr, h, cell_feat, net_feat, nodes, targets, level_id, lvl, path_map, **extra)
         if y is not None:
             outs.append(y)
     return torch.cat(outs, dim=0), target_list, feat_map
@@ -298,8 +369,9 @@ class OracleTrainer:
     (src/train.py:431-443,475-562: MSE on arrival time, Adam lr 1e-3, weight_decay 0)."""
 
     def __init__(self, pm_state, pc_state, lr=1e-3, weight_decay=0.0, pooling='max', dtype=torch.float32,
-                 cnn_kind='unet'):
+                 cnn_kind='unet', rounding=None):
         self.dtype = dtype
+        self.rounding = rounding
         self.pooling = pooling
         self.cnn_kind = cnn_kind
         self.pm = {k: (v.detach().clone().to(dtype).requires_grad_(True) if v.dtype.is_floating_point else v.clone())
@@ -315,8 +387,11 @@ class OracleTrainer:
         leaves = [v for v in self.pm.values() if v.requires_grad] + [v for v in self.pc.values() if v.requires_grad]
         self.optim = torch.optim.Adam(leaves, lr, weight_decay=weight_decay)
 
-    def forward(self, design, csr, path_ids):
-        return sweep_forward(self.pm, self.pc, design, csr, path_ids, self.pooling, True, self.dtype, self.cnn_kind)
+    def forward(self, design, csr, path_ids, feat_map=None):
+        extra = dict(rounding=self.rounding) if self.rounding is not None else {}
+        if feat_map is not None:
+            extra['feat_map'] = feat_map
+        return sweep_forward(self.pm, self.pc, design, csr, path_ids, self.pooling, True, self.dtype, self.cnn_kind, **extra)
 
     def step(self, design, csr, path_ids):
         """One mini-batch: forward, MSE, backward, Adam. Returns (loss, label_hats, target_list)."""
