@@ -11,8 +11,9 @@
 // (the reference's PathConv defaults, src/model.py:48-51); other widths use the two-launch path.
 // 8 waves per workgroup (two per SIMD): a level is one round of <= 256 workgroups, so its duration is one workgroup's
 // latency; halving every wave's share of the MFMAs and of the register-resident weight panels took 24 -> 19 us
-// (MMFT_MLP2_WAVES=4 restores the four-wave form for comparison).
+// against the four-wave form.
 #include "mlp2_core.h"
+#include "mlp_tile_bf16.h"
 
 namespace mmft {
 
@@ -83,14 +84,12 @@ __global__ void __launch_bounds__(NW * 64, 1) mlp2_rows_kernel(Mlp2Args a) {
       if (a.mask) {
         f32x4 mk = {0.f, 0.f, 0.f, 0.f};
         if (live) mk = *reinterpret_cast<const f32x4*>(a.mask + row * a.ldmask + nn);
-        v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f;
-        v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
+        v = relu_mask4(v, mk);
       } else {
         if (a.b1) {
           v.x += a.b1[nn]; v.y += a.b1[nn + 1]; v.z += a.b1[nn + 2]; v.w += a.b1[nn + 3];
         }
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+        v = relu4(v);
       }
       *reinterpret_cast<f32x4*>(hs + m * HS + nn) = v;
       if (a.hid_out && live) *reinterpret_cast<f32x4*>(a.hid_out + row * a.ldhid + nn) = v;
@@ -119,10 +118,7 @@ __global__ void __launch_bounds__(NW * 64, 1) mlp2_rows_kernel(Mlp2Args a) {
         v.x += a.b2[nn]; v.y += a.b2[nn + 1]; v.z += a.b2[nn + 2]; v.w += a.b2[nn + 3];
       }
       if (a.add_act) v += *reinterpret_cast<const f32x4*>(q);
-      if (a.relu_out) {
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-      }
+      if (a.relu_out) v = relu4(v);
       *reinterpret_cast<f32x4*>(q) = v;
     }
 }
@@ -153,20 +149,15 @@ extern "C" int mmft_mlp2_rows(const float* x1, long long ldx1, const int* rows, 
   hipStream_t st = (hipStream_t)stream;
   Mlp2Args a{x1, ldx1, rows, n, w1, ldw1, b1, w2, ldw2, b2, mask, ldmask, hid_out, ldhid, out, ldout, add_act, relu_out, active};
   const double fl = 2.0 * n * ((double)K1 * HD + (double)HD * D2), by = 4.0 * n * ((double)K1 + 2.0 * HD + 2.0 * D2);
-  static int nw = -1;
-  if (nw < 0) {
-    const char* e = getenv("MMFT_MLP2_WAVES");         // tuning hook: 4 or 8 waves per workgroup
-    nw = (e && atoi(e) == 4) ? 4 : 8;
-  }
   const bool bf = math_mode() == MMFT_MATH_BF16;
-#define MMFT_M2(KM, NWV, BFV, NAME) \
-  MMFT_LAUNCH(NAME, fl, by, (mlp2_rows_kernel<KM, NWV, BFV>), dim3(cdiv(n, M2_BM)), dim3(NWV * 64), st, a)
+#define MMFT_M2(KM, BFV, NAME) \
+  MMFT_LAUNCH(NAME, fl, by, (mlp2_rows_kernel<KM, 8, BFV>), dim3(cdiv(n, M2_BM)), dim3(8 * 64), st, a)
   if (weights_kmajor) {
-    if (bf) { if (nw == 8) MMFT_M2(true, 8, true, "mlp2_rows_kernel<KM,bf16>"); else MMFT_M2(true, 4, true, "mlp2_rows_kernel<KM,bf16>"); }
-    else { if (nw == 8) MMFT_M2(true, 8, false, "mlp2_rows_kernel<KM>"); else MMFT_M2(true, 4, false, "mlp2_rows_kernel<KM>"); }
+    if (bf) MMFT_M2(true, true, "mlp2_rows_kernel<KM,bf16>");
+    else MMFT_M2(true, false, "mlp2_rows_kernel<KM>");
   } else {
-    if (bf) { if (nw == 8) MMFT_M2(false, 8, true, "mlp2_rows_kernel<MK,bf16>"); else MMFT_M2(false, 4, true, "mlp2_rows_kernel<MK,bf16>"); }
-    else { if (nw == 8) MMFT_M2(false, 8, false, "mlp2_rows_kernel<MK>"); else MMFT_M2(false, 4, false, "mlp2_rows_kernel<MK>"); }
+    if (bf) MMFT_M2(false, true, "mlp2_rows_kernel<MK,bf16>");
+    else MMFT_M2(false, false, "mlp2_rows_kernel<MK>");
   }
 #undef MMFT_M2
   return check_launch("mlp2_rows");

@@ -14,32 +14,12 @@
 //   * 8 waves per 32-row tile: wave w owns hidden columns [32w, 32w + 32) and output columns [16w, 16w + 16).
 // The reverse form (weights_kmajor in the fp32 kernel) is the same kernel fed with the transposed packs.
 #include <stdlib.h>
-#include "gemm_bf16.h"
+#include "mlp_tile_bf16.h"
 #include "fold_gather.h"
 
 namespace mmft {
 
-constexpr int L2_BM = 32, L2_K1 = 128, L2_HD = 256, L2_D2 = 128;
-constexpr int L2_XS = L2_K1 + 8, L2_HS = L2_HD + 8;        // LDS row strides in bf16 elements (multiples of 8)
-
-// Four consecutive columns of a row of the hidden tensors (fc_cell_neigh's hidden activations HN, their gradients DHN): fp32, or
-// - hid16 - bf16 (round to nearest even; `ld` counts elements of the stored type).  Every consumer rounds these values to
-// bf16 anyway (MFMA operands of the weight gradients) or only looks at their sign (the ReLU mask), so the bf16 form changes
-// no result and halves 2 KB of traffic per row and direction.
-__device__ __forceinline__ void hid_store4(float* base, long long off, f32x4 v, int hid16) {
-  if (hid16) {
-    const unsigned lo = pack_bf16(v.x, v.y), hi = pack_bf16(v.z, v.w);
-    *reinterpret_cast<unsigned long long*>(reinterpret_cast<unsigned short*>(base) + off) = ((unsigned long long)hi << 32) | lo;
-  } else {
-    *reinterpret_cast<f32x4*>(base + off) = v;
-  }
-}
-__device__ __forceinline__ f32x4 hid_load4(const float* base, long long off, int hid16) {
-  if (!hid16) return *reinterpret_cast<const f32x4*>(base + off);
-  const unsigned long long u = *reinterpret_cast<const unsigned long long*>(reinterpret_cast<const unsigned short*>(base) + off);
-  const unsigned lo = (unsigned)u, hi = (unsigned)(u >> 32);
-  return f32x4{__uint_as_float(lo << 16), __uint_as_float(lo & 0xffff0000u), __uint_as_float(hi << 16), __uint_as_float(hi & 0xffff0000u)};
-}
+constexpr int L2_BM = 32;
 
 struct Mlp2Bf16Args {
   const float* x1;
@@ -76,14 +56,8 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
 
   // ---- every global load of the kernel: the wave's weight fragments of both layers, then the gathered x rows
   bf16x8 w1f[2][4], w2f[8];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      w1f[j][ks] = *reinterpret_cast<const bf16x8*>(a.w1 + (long long)(wave * 32 + j * 16 + r16) * L2_K1 + ks * 32 + q * 8);
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-    w2f[ks] = *reinterpret_cast<const bf16x8*>(a.w2 + (long long)(wave * 16 + r16) * L2_HD + ks * 32 + q * 8);
+  load_w1_frags(w1f, a.w1, wave, r16, q);
+  load_w2_frags(w2f, a.w2, wave, r16, q);
   {
     // 32 rows x 128 floats = 1024 groups of 4 floats, 2 per thread: thread -> (row, 8 consecutive k)
     const int r = tid >> 4, k8 = (tid & 15) * 8;
@@ -100,20 +74,7 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
 
   // ---- phase 1: hidden columns [32 wave, 32 wave + 32) of the 32 rows
   f32x4 acc1[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    bf16x8 xf[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) xf[i] = *reinterpret_cast<const bf16x8*>(xs + (i * 16 + r16) * L2_XS + ks * 32 + q * 8);
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[j][ks], xf[i], acc1[i][j], 0, 0, 0);
-  }
+  tile_layer1<4, 2>(acc1, w1f, xs, L2_XS, r16, q);
   // lane holds hidden columns nn .. nn + 3 of row m: bias + ReLU, or the ReLU mask of the saved forward activations
 #pragma unroll
   for (int i = 0; i < 2; ++i)
@@ -126,30 +87,20 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
       if (a.mask) {
         f32x4 mk = {0.f, 0.f, 0.f, 0.f};
         if (live) mk = hid_load4(a.mask, row * a.ldmask + nn, a.hid16);
-        v.x = mk.x > 0.f ? v.x : 0.f; v.y = mk.y > 0.f ? v.y : 0.f;
-        v.z = mk.z > 0.f ? v.z : 0.f; v.w = mk.w > 0.f ? v.w : 0.f;
+        v = relu_mask4(v, mk);
       } else {
         if (a.b1) v += *reinterpret_cast<const f32x4*>(a.b1 + nn);
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
+        v = relu4(v);
       }
-      unsigned lo = pack_bf16(v.x, v.y), hi = pack_bf16(v.z, v.w);
-      *reinterpret_cast<unsigned long long*>(hs + m * L2_HS + nn) = ((unsigned long long)hi << 32) | lo;
+      st_bf16x4(hs + m * L2_HS + nn, v);
       if (a.hid_out && live) hid_store4(a.hid_out, row * a.ldhid + nn, v, a.hid16);
     }
   __syncthreads();
 
   // ---- phase 2: output columns [16 wave, 16 wave + 16)
   f32x4 acc2[2];
-  acc2[0] = acc2[1] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (i * 16 + r16) * L2_HS + ks * 32 + q * 8);
-      acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], hf, acc2[i], 0, 0, 0);
-    }
-  }
+  for (int i = 0; i < 2; ++i) acc2[i] = tile_layer2(w2f, hs, L2_HS, r16, q, i);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
     const int m = i * 16 + r16;
@@ -159,10 +110,7 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
     f32x4 v = acc2[i];
     if (a.b2) v += *reinterpret_cast<const f32x4*>(a.b2 + nn);
     if (a.add_act) v += *reinterpret_cast<const f32x4*>(o);
-    if (a.relu_out) {
-      v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-      v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-    }
+    if (a.relu_out) v = relu4(v);
     *reinterpret_cast<f32x4*>(o) = v;
   }
 }
@@ -170,8 +118,8 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
 // ------------------------------------------------------------------------------------------------------------------
 // Fused forward LEVEL kernel (bf16 mode): the folded gather of one (net level l - 1, cell level l) pair AND the cell
 // level's Linear-ReLU-Linear in one launch.
-//   blocks [0, cell_tiles):  32 cell rows each - the 512 threads first compute the softmax-weighted fan-in sums A[v]
-//       of their rows (two (row, 4-channel) items per thread, in-neighbours of level l - 1 recomputed from PRE and
+//   blocks [0, cell_tiles):  16 cell rows each - the 512 threads first compute the softmax-weighted fan-in sums A[v]
+//       of their rows (one (row, 4-channel) item per thread, in-neighbours of level l - 1 recomputed from PRE and
 //       their driver's row exactly as pair_fwd_gather does), store A / LSE for the reverse sweep and put the bf16 tile
 //       straight into LDS; then the two MFMA phases of mlp2_rows_bf16_kernel: h[v] = act(h[v] + fc_cell_neigh(A[v]));
 //   blocks [cell_tiles, ...): the net rows of level l - 1: h[u] = act(PRE[u] + mean h[driver]).
@@ -198,11 +146,10 @@ struct LevelFwdArgs {
   int cell_tiles;
 };
 
-// BM rows per tile (16: one gather item per thread, twice as many workgroups - the gather, not the MLP, sets the
-// duration of a level, and it wants the memory-level parallelism; 32: the tile of mlp2_rows_bf16_kernel)
-template <int BM>
+// 16 rows per tile: one gather item per thread and twice as many workgroups as the 32-row tile of mlp2_rows_bf16_kernel -
+// the gather, not the MLP, sets the duration of a level, and it wants the memory-level parallelism
 __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
-  constexpr int RT = BM / 16;
+  constexpr int BM = 16;
   __shared__ __attribute__((aligned(16))) unsigned short xs[BM * L2_XS];
   __shared__ __attribute__((aligned(16))) unsigned short hs[BM * L2_HS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -228,16 +175,11 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
   }
   const int r16 = lane & 15, q = lane >> 4;
   bf16x8 w1f[2][4], w2f[8];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      w1f[j][ks] = *reinterpret_cast<const bf16x8*>(a.w1 + (long long)(wave * 32 + j * 16 + r16) * L2_K1 + ks * 32 + q * 8);
+  load_w1_frags(w1f, a.w1, wave, r16, q);
 
-  // ---- gather: item = (row r, channel group cg), two items per thread
-#pragma unroll
-  for (int it = 0; it < BM / 16; ++it) {
-    const int item = tid + it * 512, r = item >> 5, c = (item & 31) * 4;
+  // ---- gather: the thread's item = (row r, channel group c)
+  {
+    const int r = tid >> 5, c = (tid & 31) * 4;
     f32x4 av = {0.f, 0.f, 0.f, 0.f};
     if (live_row(r)) {
       const int v = row_of(r);
@@ -256,75 +198,37 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
       *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + c) = av;
       *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + c) = lv;
     }
-    const unsigned lo = pack_bf16(av.x, av.y), hi = pack_bf16(av.z, av.w);
-    *reinterpret_cast<unsigned long long*>(xs + r * L2_XS + c) = ((unsigned long long)hi << 32) | lo;
+    st_bf16x4(xs + r * L2_XS + c, av);
   }
   // the second layer's fragments are requested only now: held across the gather they cost 32 registers and a wave of occupancy
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-    w2f[ks] = *reinterpret_cast<const bf16x8*>(a.w2 + (long long)(wave * 16 + r16) * L2_HD + ks * 32 + q * 8);
+  load_w2_frags(w2f, a.w2, wave, r16, q);
   __syncthreads();
 
-  // ---- phase 1 / epilogue 1 / phase 2 / epilogue 2: as mlp2_rows_bf16_kernel (forward form)
-  f32x4 acc1[RT][2];
+  // ---- phase 1 / epilogue 1 / phase 2 / epilogue 2: as mlp2_rows_bf16_kernel (forward form), one 16-row block
+  f32x4 acc1[1][2];
+  tile_layer1<4, 1>(acc1, w1f, xs, L2_XS, r16, q);
 #pragma unroll
-  for (int i = 0; i < RT; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-    bf16x8 xf[RT];
-#pragma unroll
-    for (int i = 0; i < RT; ++i) xf[i] = *reinterpret_cast<const bf16x8*>(xs + (i * 16 + r16) * L2_XS + ks * 32 + q * 8);
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[j][ks], xf[i], acc1[i][j], 0, 0, 0);
+  for (int j = 0; j < 2; ++j) {
+    const int nn = wave * 32 + j * 16 + q * 4;
+    f32x4 v = acc1[0][j];
+    if (a.b1) v += *reinterpret_cast<const f32x4*>(a.b1 + nn);
+    v = relu4(v);
+    st_bf16x4(hs + r16 * L2_HS + nn, v);
+    if (a.hid_out && live_row(r16)) hid_store4(a.hid_out, (long long)row_of(r16) * a.ldhid + nn, v, a.hid16);
   }
-#pragma unroll
-  for (int i = 0; i < RT; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const int m = i * 16 + r16, nn = wave * 32 + j * 16 + q * 4;
-      f32x4 v = acc1[i][j];
-      if (a.b1) v += *reinterpret_cast<const f32x4*>(a.b1 + nn);
-      v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-      v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-      unsigned lo = pack_bf16(v.x, v.y), hi = pack_bf16(v.z, v.w);
-      *reinterpret_cast<unsigned long long*>(hs + m * L2_HS + nn) = ((unsigned long long)hi << 32) | lo;
-      if (a.hid_out && live_row(m)) hid_store4(a.hid_out, (long long)row_of(m) * a.ldhid + nn, v, a.hid16);
-    }
   __syncthreads();
-  f32x4 acc2[RT];
-#pragma unroll
-  for (int i = 0; i < RT; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks) {
-#pragma unroll
-    for (int i = 0; i < RT; ++i) {
-      bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (i * 16 + r16) * L2_HS + ks * 32 + q * 8);
-      acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], hf, acc2[i], 0, 0, 0);
-    }
-  }
-#pragma unroll
-  for (int i = 0; i < RT; ++i) {
-    const int m = i * 16 + r16;
-    if (!live_row(m)) continue;
-    const int nn = wave * 16 + q * 4;
-    float* o = a.h + (long long)row_of(m) * a.ld + nn;
-    f32x4 v = acc2[i];
-    if (a.b2) v += *reinterpret_cast<const f32x4*>(a.b2 + nn);
-    v += *reinterpret_cast<const f32x4*>(o);
-    if (a.relu) {
-      v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-      v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-    }
-    *reinterpret_cast<f32x4*>(o) = v;
-  }
+  if (!live_row(r16)) return;
+  const int nn = wave * 16 + q * 4;
+  float* o = a.h + (long long)row_of(r16) * a.ld + nn;
+  f32x4 v = tile_layer2(w2f, hs, L2_HS, r16, q, 0);
+  if (a.b2) v += *reinterpret_cast<const f32x4*>(a.b2 + nn);
+  v += *reinterpret_cast<const f32x4*>(o);
+  if (a.relu) v = relu4(v);
+  *reinterpret_cast<f32x4*>(o) = v;
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// Fused forward level kernel, SLOT-TABLE form.  Same arithmetic as level_fwd_bf16_kernel<16> - every row
+// Fused forward level kernel, SLOT-TABLE form.  Same arithmetic as level_fwd_bf16_kernel - every row
 // bitwise equal - with the serial latencies of a tile's dependent chain cut:
 //   * `slots` (static, built on the host next to the CSR): per cell row of fan-in <= 4 the four (row of h to read, row of
 //     PRE to add or -1) pairs of its in-edges in edge order - ONE 32-byte load whose address is known at kernel entry
@@ -402,11 +306,7 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) 
     hold[rb] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   if (has_cell) {
-#pragma unroll
-    for (int j = 0; j < 2; ++j)
-#pragma unroll
-      for (int ks = 0; ks < 4; ++ks)
-        w1f[j][ks] = *reinterpret_cast<const bf16x8*>(a.w1 + (long long)(wave * 32 + j * 16 + r16) * L2_K1 + ks * 32 + q * 8);
+    load_w1_frags(w1f, a.w1, wave, r16, q);
 #pragma unroll
     for (int rb = 0; rb < RB; ++rb)
       if (elive[rb]) hold[rb] = *reinterpret_cast<const f32x4*>(a.h + (long long)(a.cell_row0 + m0 + r16 + 16 * rb) * a.ld + wave * 16 + q * 4);
@@ -465,28 +365,13 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) 
       *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + gc) = av;
       *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + gc) = lv;
     }
-    const unsigned lo = pack_bf16(av.x, av.y), hi = pack_bf16(av.z, av.w);
-    *reinterpret_cast<unsigned long long*>(xs + (gr + 16 * rb) * L2_XS + gc) = ((unsigned long long)hi << 32) | lo;
+    st_bf16x4(xs + (gr + 16 * rb) * L2_XS + gc, av);
   }
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-    w2f[ks] = *reinterpret_cast<const bf16x8*>(a.w2 + (long long)(wave * 16 + r16) * L2_HD + ks * 32 + q * 8);
+  load_w2_frags(w2f, a.w2, wave, r16, q);
   __syncthreads();
-  // ---- phase 1 / epilogue 1 / phase 2 / epilogue 2: as level_fwd_bf16_kernel<16>, per row block
+  // ---- phase 1 / epilogue 1 / phase 2 / epilogue 2: as level_fwd_bf16_kernel, per row block
   f32x4 acc1[RB][2];
-#pragma unroll
-  for (int rb = 0; rb < RB; ++rb)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) acc1[rb][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-    for (int rb = 0; rb < RB; ++rb) {
-      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xs + (r16 + 16 * rb) * L2_XS + ks * 32 + q * 8);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc1[rb][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[j][ks], xf, acc1[rb][j], 0, 0, 0);
-    }
-  }
+  tile_layer1<4, RB>(acc1, w1f, xs, L2_XS, r16, q);
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb)
 #pragma unroll
@@ -494,31 +379,20 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) 
       const int nn = wave * 32 + j * 16 + q * 4;
       f32x4 hv = acc1[rb][j];
       if (a.b1) hv += *reinterpret_cast<const f32x4*>(a.b1 + nn);
-      hv.x = hv.x > 0.f ? hv.x : 0.f; hv.y = hv.y > 0.f ? hv.y : 0.f;
-      hv.z = hv.z > 0.f ? hv.z : 0.f; hv.w = hv.w > 0.f ? hv.w : 0.f;
-      const unsigned lo = pack_bf16(hv.x, hv.y), hi = pack_bf16(hv.z, hv.w);
-      *reinterpret_cast<unsigned long long*>(hs + (r16 + 16 * rb) * L2_HS + nn) = ((unsigned long long)hi << 32) | lo;
+      hv = relu4(hv);
+      st_bf16x4(hs + (r16 + 16 * rb) * L2_HS + nn, hv);
       if (a.hid_out && elive[rb])
         hid_store4(a.hid_out, (long long)(a.cell_row0 + m0 + r16 + 16 * rb) * a.ldhid + nn, hv, a.hid16);
     }
   __syncthreads();
 #pragma unroll
   for (int rb = 0; rb < RB; ++rb) {
-    f32x4 acc2 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (r16 + 16 * rb) * L2_HS + ks * 32 + q * 8);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], hf, acc2, 0, 0, 0);
-    }
+    f32x4 o = tile_layer2(w2f, hs, L2_HS, r16, q, rb);
     if (elive[rb]) {
       const int nn = wave * 16 + q * 4;
-      f32x4 o = acc2;
       if (a.b2) o += *reinterpret_cast<const f32x4*>(a.b2 + nn);
       o += hold[rb];
-      if (a.relu) {
-        o.x = o.x > 0.f ? o.x : 0.f; o.y = o.y > 0.f ? o.y : 0.f;
-        o.z = o.z > 0.f ? o.z : 0.f; o.w = o.w > 0.f ? o.w : 0.f;
-      }
+      if (a.relu) o = relu4(o);
       *reinterpret_cast<f32x4*>(a.h + (long long)(a.cell_row0 + m0 + r16 + 16 * rb) * a.ld + nn) = o;
     }
   }
@@ -722,17 +596,10 @@ __global__ void __launch_bounds__(512) level_bwd_pair_kernel(LevelBwdPairArgs a)
   }
   if (!a.has_mlp) return;
 #pragma unroll
-  for (int d = 0; d < 2; ++d) {
-    const unsigned lo = pack_bf16(acc[d].x, acc[d].y), hi = pack_bf16(acc[d].z, acc[d].w);       // rows >= nd hold zeros
-    *reinterpret_cast<unsigned long long*>(xs + (gr + 16 * d) * L2_XS + gc) = ((unsigned long long)hi << 32) | lo;
-  }
-  const bool two = nd > 16;                                  // block-uniform: the second 16-row block holds drivers
+  for (int d = 0; d < 2; ++d) st_bf16x4(xs + (gr + 16 * d) * L2_XS + gc, acc[d]);       // rows >= nd hold zeros
+  const int nrb = nd > 16 ? 2 : 1;                          // block-uniform: the second 16-row block holds drivers
   bf16x8 w1f[2][4], w2f[8];
-#pragma unroll
-  for (int j = 0; j < 2; ++j)
-#pragma unroll
-    for (int ks = 0; ks < 4; ++ks)
-      w1f[j][ks] = *reinterpret_cast<const bf16x8*>(a.w1 + (long long)(wave * 32 + j * 16 + r16) * L2_K1 + ks * 32 + q * 8);
+  load_w1_frags(w1f, a.w1, wave, r16, q);
   // the ReLU mask of the hidden rows
   f32x4 mk[2][2];
 #pragma unroll
@@ -743,47 +610,28 @@ __global__ void __launch_bounds__(512) level_bwd_pair_kernel(LevelBwdPairArgs a)
       if (r16 + 16 * i < nd)
         mk[i][j] = hid_load4(a.mask, (long long)(v0 + r16 + 16 * i) * a.ldmask + wave * 32 + j * 16 + q * 4, a.hid16);
     }
-#pragma unroll
-  for (int ks = 0; ks < 8; ++ks)
-    w2f[ks] = *reinterpret_cast<const bf16x8*>(a.w2 + (long long)(wave * 16 + r16) * L2_HD + ks * 32 + q * 8);
+  load_w2_frags(w2f, a.w2, wave, r16, q);
   __syncthreads();
   // ---- hidden gradient = (G . W2g) * relu'(HN), DA = hidden gradient . W1g: the MFMA phases of mlp2_rows_bf16_kernel
-  f32x4 acc1[2][2] = {{zero, zero}, {zero, zero}};
-#pragma unroll
-  for (int ks = 0; ks < 4; ++ks) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      if (i == 1 && !two) continue;
-      const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xs + (i * 16 + r16) * L2_XS + ks * 32 + q * 8);
-#pragma unroll
-      for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[j][ks], xf, acc1[i][j], 0, 0, 0);
-    }
-  }
+  f32x4 acc1[2][2];
+  tile_layer1<4, 2>(acc1, w1f, xs, L2_XS, r16, q, nrb);
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    if (i == 1 && !two) continue;
+    if (i >= nrb) continue;
     const int row = r16 + 16 * i;
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int nn = wave * 32 + j * 16 + q * 4;
-      f32x4 hvv = acc1[i][j];
-      hvv.x = mk[i][j].x > 0.f ? hvv.x : 0.f; hvv.y = mk[i][j].y > 0.f ? hvv.y : 0.f;
-      hvv.z = mk[i][j].z > 0.f ? hvv.z : 0.f; hvv.w = mk[i][j].w > 0.f ? hvv.w : 0.f;
-      const unsigned lo = pack_bf16(hvv.x, hvv.y), hi = pack_bf16(hvv.z, hvv.w);
-      *reinterpret_cast<unsigned long long*>(hs + row * L2_HS + nn) = ((unsigned long long)hi << 32) | lo;
+      const f32x4 hvv = relu_mask4(acc1[i][j], mk[i][j]);
+      st_bf16x4(hs + row * L2_HS + nn, hvv);
       if (a.hid_out && row < nd) hid_store4(a.hid_out, (long long)(v0 + row) * a.ldhid + nn, hvv, a.hid16);
     }
   }
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < 2; ++i) {
-    if (i == 1 && !two) continue;
-    f32x4 acc2 = zero;
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks) {
-      const bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (i * 16 + r16) * L2_HS + ks * 32 + q * 8);
-      acc2 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], hf, acc2, 0, 0, 0);
-    }
+    if (i >= nrb) continue;
+    const f32x4 acc2 = tile_layer2(w2f, hs, L2_HS, r16, q, i);
     if (r16 + 16 * i < nd) *reinterpret_cast<f32x4*>(a.DA + (long long)(v0 + r16 + 16 * i) * a.ld + wave * 16 + q * 4) = acc2;
   }
 }
@@ -863,7 +711,7 @@ extern "C" int mmft_level_fwd_bf16(float* h, const float* pre, long long ld, int
                  cell_row0, n_cell, A, LSE, (const unsigned short*)w1_bf16, (const unsigned short*)w2_bf16, b1, b2, hid_out,
                  ldhid, hid_bf16 ? 1 : 0, relu, active, tiles};
   const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  MMFT_LAUNCH("level_fwd_bf16_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<LV_BM>,
+  MMFT_LAUNCH("level_fwd_bf16_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel,
               dim3(tiles + net_blocks), dim3(512), (hipStream_t)stream, a);
   return check_launch("level_fwd_bf16");
 }

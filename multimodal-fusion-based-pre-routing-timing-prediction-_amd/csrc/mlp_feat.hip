@@ -12,17 +12,15 @@
 //         dW2 += G^T H,  db2 += sum G,  dW1 += dH^T X,  db1 += sum dH
 //     in MFMA accumulators across the 32-row tiles of a persistent workgroup (the contractions over rows take their
 //     operands from transposed bf16 copies of the tile in LDS); one slab per workgroup, summed in a fixed order.
-// Lane layouts are those of mlp2_bf16.hip: A = weights / transposed tiles (lane = output feature, 8 consecutive k),
+// Lane layouts are those of mlp_tile_bf16.h: A = weights / transposed tiles (lane = output feature, 8 consecutive k),
 // B = row tiles (lane = row or feature, 8 consecutive k), D[m][n] at lane (n = lane & 15, q = lane >> 4) = rows 4q..4q+3.
 #include <stdlib.h>
-#include "gemm_bf16.h"
+#include "mlp_tile_bf16.h"
 #include "tr_read.h"
 
 namespace mmft {
 
 int launch_slab_reduce(const float* slabs, int splits, long long elems, float* out, int accumulate, hipStream_t st);
-
-constexpr int MF_HD = 256, MF_D2 = 128;
 
 __device__ __forceinline__ unsigned short mf_bf16(float v) { return (unsigned short)(pack_bf16(v, 0.f) & 0xffff); }
 
@@ -51,7 +49,7 @@ struct FeatFwdArgs {
 
 template <int KS>   // K steps of 32 for the first layer (fin <= 32 KS)
 __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
-  constexpr int BM = 64, RT = BM / 16, XS = KS * 32 + 8, HS = MF_HD + 8;
+  constexpr int BM = 64, RT = BM / 16, XS = KS * 32 + 8, HS = L2_HD + 8;
   __shared__ __attribute__((aligned(16))) unsigned short xs[BM * XS];
   __shared__ __attribute__((aligned(16))) unsigned short hs[BM * HS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -62,7 +60,7 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) w1f[j][ks] = mf_w1_frag(a.w1, a.fin, wave * 32 + j * 16 + r16, ks * 32 + q * 8);
 #pragma unroll
-  for (int ks = 0; ks < 8; ++ks) w2f[ks] = mf_pack8(a.w2 + (long long)(wave * 16 + r16) * MF_HD + ks * 32 + q * 8);
+  for (int ks = 0; ks < 8; ++ks) w2f[ks] = mf_pack8(a.w2 + (long long)(wave * 16 + r16) * L2_HD + ks * 32 + q * 8);
   const int nn2 = wave * 16 + q * 4;
   const f32x4 b2v = *reinterpret_cast<const f32x4*>(a.b2 + nn2);
   f32x4 b1v[2];
@@ -92,49 +90,21 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
     __syncthreads();
     if (tile + (int)gridDim.x < ntiles) request(tile + gridDim.x);
     f32x4 acc1[RT][2];
+    tile_layer1<KS, RT>(acc1, w1f, xs, XS, r16, q);
 #pragma unroll
     for (int i = 0; i < RT; ++i)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) acc1[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const bf16x8 xf = *reinterpret_cast<const bf16x8*>(xs + (i * 16 + r16) * XS + ks * 32 + q * 8);
-#pragma unroll
-        for (int j = 0; j < 2; ++j) acc1[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w1f[j][ks], xf, acc1[i][j], 0, 0, 0);
-      }
-#pragma unroll
-    for (int i = 0; i < RT; ++i)
-#pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int m = i * 16 + r16, nn = wave * 32 + j * 16 + q * 4;
-        f32x4 v = acc1[i][j] + b1v[j];
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-        const unsigned lo = pack_bf16(v.x, v.y), hi = pack_bf16(v.z, v.w);
-        *reinterpret_cast<unsigned long long*>(hs + m * HS + nn) = ((unsigned long long)hi << 32) | lo;
-      }
+      for (int j = 0; j < 2; ++j) st_bf16x4(hs + (i * 16 + r16) * HS + wave * 32 + j * 16 + q * 4, relu4(acc1[i][j] + b1v[j]));
     __syncthreads();
     f32x4 acc2[RT];
 #pragma unroll
-    for (int i = 0; i < RT; ++i) acc2[i] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-    for (int ks = 0; ks < 8; ++ks)
-#pragma unroll
-      for (int i = 0; i < RT; ++i) {
-        const bf16x8 hf = *reinterpret_cast<const bf16x8*>(hs + (i * 16 + r16) * HS + ks * 32 + q * 8);
-        acc2[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w2f[ks], hf, acc2[i], 0, 0, 0);
-      }
+    for (int i = 0; i < RT; ++i) acc2[i] = tile_layer2(w2f, hs, HS, r16, q, i);
 #pragma unroll
     for (int i = 0; i < RT; ++i) {
       const int m = m0 + i * 16 + r16;
       if (m >= a.n) continue;
       f32x4 v = acc2[i] + b2v;
-      if (a.relu_out) {
-        v.x = v.x > 0.f ? v.x : 0.f; v.y = v.y > 0.f ? v.y : 0.f;
-        v.z = v.z > 0.f ? v.z : 0.f; v.w = v.w > 0.f ? v.w : 0.f;
-      }
+      if (a.relu_out) v = relu4(v);
       *reinterpret_cast<f32x4*>(a.out + (long long)(a.row0 + m) * a.ldout + nn2) = v;
     }
     // the next deposit overwrites xs (last read before the barrier above) and the next epilogue hs (last read here)
@@ -157,7 +127,7 @@ template <int KS>
 __global__ void __launch_bounds__(512) mlp2_feat_bwd_kernel(FeatBwdArgs a) {
   // every tile lives in LDS in its natural [row][column] layout; the contractions over the tile's rows read their operands
   // with the hardware-transposed read (tr_read.h) - pitches of 16 x odd elements
-  constexpr int BM = 32, KP = KS * 32, XS = KP + 16, GS = MF_D2 + 16, HS = MF_HD + 16, KB = KP / 16;
+  constexpr int BM = 32, KP = KS * 32, XS = KP + 16, GS = L2_D2 + 16, HS = L2_HD + 16, KB = KP / 16;
   extern __shared__ __attribute__((aligned(16))) unsigned short lds[];
   unsigned short* xs = lds;                       // X tile  [row][k]
   unsigned short* gs = xs + BM * XS;              // G tile  [row][d2]
@@ -181,7 +151,7 @@ __global__ void __launch_bounds__(512) mlp2_feat_bwd_kernel(FeatBwdArgs a) {
     for (int ks = 0; ks < 4; ++ks) {         // A fragment of W2^T: W2T[col][d2] = w2[d2][col], d2 = 32 ks + 8 q ..
       float v[8];
 #pragma unroll
-      for (int t = 0; t < 8; ++t) v[t] = a.w2[(long long)(ks * 32 + q * 8 + t) * MF_HD + col];
+      for (int t = 0; t < 8; ++t) v[t] = a.w2[(long long)(ks * 32 + q * 8 + t) * L2_HD + col];
       w2tf[j][ks] = mf_pack8(v);
     }
     b1v[j] = *reinterpret_cast<const f32x4*>(a.b1 + wave * 32 + j * 16 + q * 4);
@@ -290,14 +260,14 @@ __global__ void __launch_bounds__(512) mlp2_feat_bwd_kernel(FeatBwdArgs a) {
   // ---- the workgroup's slab
   float* sl = a.slabs + (long long)blockIdx.x * a.slab;
   float* s_dw1 = sl;
-  float* s_db1 = s_dw1 + (long long)MF_HD * a.fin;
-  float* s_dw2 = s_db1 + MF_HD;
-  float* s_db2 = s_dw2 + (long long)MF_D2 * MF_HD;
+  float* s_db1 = s_dw1 + (long long)L2_HD * a.fin;
+  float* s_dw2 = s_db1 + L2_HD;
+  float* s_db2 = s_dw2 + (long long)L2_D2 * L2_HD;
 #pragma unroll
   for (int j = 0; j < 2; ++j) {
     const int colq = wave * 32 + j * 16 + q * 4;           // D[m = col][n]: lane (n = r16, q) holds cols colq .. colq + 3
 #pragma unroll
-    for (int d = 0; d < 8; ++d) *reinterpret_cast<f32x4*>(s_dw2 + (long long)(d * 16 + r16) * MF_HD + colq) = dw2[j][d];
+    for (int d = 0; d < 8; ++d) *reinterpret_cast<f32x4*>(s_dw2 + (long long)(d * 16 + r16) * L2_HD + colq) = dw2[j][d];
 #pragma unroll
     for (int k = 0; k < KB; ++k) {
       const int kk = k * 16 + r16;
@@ -328,11 +298,11 @@ __global__ void __launch_bounds__(512) mlp2_feat_bwd_kernel(FeatBwdArgs a) {
 
 template <int KS>
 constexpr int feat_bwd_lds() {
-  constexpr int BM = 32, KP = KS * 32, XS = KP + 16, GS = MF_D2 + 16, HS = MF_HD + 16;
+  constexpr int BM = 32, KP = KS * 32, XS = KP + 16, GS = L2_D2 + 16, HS = L2_HD + 16;
   return (BM * XS + BM * GS + 2 * BM * HS) * 2;
 }
 
-static inline long long feat_slab(int fin) { return (long long)MF_HD * fin + MF_HD + (long long)MF_D2 * MF_HD + MF_D2; }
+static inline long long feat_slab(int fin) { return (long long)L2_HD * fin + L2_HD + (long long)L2_D2 * L2_HD + L2_D2; }
 // One workgroup per CU (256 VGPRs) - on 192 of the 256 CUs: the two launches close the reverse sweep on its side stream while
 // the U-Net's backward, the stream that finishes last, still runs on the main one; a grid that takes every CU for 2 x 118 us
 // stalls it.  Measured on the replayed config-B step (ms): 256 -> 3.37, 224 -> 3.28, 192 -> 3.23, 160 -> 3.26, 128 -> 3.29.
@@ -358,7 +328,7 @@ extern "C" int mmft_mlp2_feat_fwd_bf16(const float* x, long long ldx, int row0, 
   if (n == 0) return MMFT_OK;
   DeviceGuard dg(device);
   FeatFwdArgs a{x, ldx, row0, n, fin, w1, b1, w2, b2, out, ldout, relu_out};
-  const double fl = 2.0 * n * ((double)fin * MF_HD + (double)MF_HD * MF_D2), by = 4.0 * n * ((double)fin + MF_D2);
+  const double fl = 2.0 * n * ((double)fin * L2_HD + (double)L2_HD * L2_D2), by = 4.0 * n * ((double)fin + L2_D2);
   int grid = cdiv(n, 64);
   if (grid > 768) grid = 768;                      // three workgroups per CU (43 KB of LDS each)
   if (fin <= 32)
@@ -378,7 +348,7 @@ extern "C" int mmft_mlp2_feat_bwd_bf16(const float* g, long long ldg, const floa
                                        float* db2, int accumulate, float* workspace, long long workspace_bytes, int device,
                                        void* stream) {
   MMFT_REQUIRE(g && x && w1 && b1 && w2 && dw1 && db1 && dw2 && db2, "mlp2_feat_bwd_bf16: null pointer");
-  MMFT_REQUIRE(n > 0 && row0 >= 0 && fin >= 1 && fin <= 64 && ldx >= fin && ldg >= MF_D2, "mlp2_feat_bwd_bf16: bad sizes (fin <= 64)");
+  MMFT_REQUIRE(n > 0 && row0 >= 0 && fin >= 1 && fin <= 64 && ldx >= fin && ldg >= L2_D2, "mlp2_feat_bwd_bf16: bad sizes (fin <= 64)");
   MMFT_REQUIRE(ldg % 4 == 0 && aligned16(g) && aligned16(b1), "mlp2_feat_bwd_bf16: g / b1 must be 16-byte aligned");
   MMFT_REQUIRE(workspace && aligned16(workspace) && workspace_bytes >= mmft_mlp2_feat_bwd_workspace_bytes(n, fin),
                "mlp2_feat_bwd_bf16: workspace too small");
@@ -387,7 +357,7 @@ extern "C" int mmft_mlp2_feat_bwd_bf16(const float* g, long long ldg, const floa
   const int grid = feat_bwd_grid(n);
   const long long slab = feat_slab(fin);
   FeatBwdArgs a{g, ldg, x, ldx, row0, n, fin, w1, b1, w2, workspace, slab};
-  const double fl = 2.0 * n * (2.0 * fin * MF_HD + 2.0 * MF_HD * MF_D2), by = 4.0 * n * ((double)fin + MF_D2);
+  const double fl = 2.0 * n * (2.0 * fin * L2_HD + 2.0 * L2_HD * L2_D2), by = 4.0 * n * ((double)fin + L2_D2);
   static DynLdsOnce once[2];
   int arc = fin <= 32 ? ensure_dyn_lds(once[0], reinterpret_cast<const void*>(&mlp2_feat_bwd_kernel<1>), feat_bwd_lds<1>(), "mlp2_feat_bwd_bf16")
                       : ensure_dyn_lds(once[1], reinterpret_cast<const void*>(&mlp2_feat_bwd_kernel<2>), feat_bwd_lds<2>(), "mlp2_feat_bwd_bf16");
@@ -400,14 +370,14 @@ extern "C" int mmft_mlp2_feat_bwd_bf16(const float* g, long long ldg, const floa
   if (rc) return rc;
   // The four gradients are the four segments of a slab.  In FlatAdam's gradient buffer they are neighbours in exactly that
   // order (weight, bias, weight, bias of one MLP), so ONE parallel slab reduction finishes all of them.
-  if (db1 == dw1 + (long long)MF_HD * fin && dw2 == db1 + MF_HD && db2 == dw2 + (long long)MF_D2 * MF_HD && aligned16(dw1))
+  if (db1 == dw1 + (long long)L2_HD * fin && dw2 == db1 + L2_HD && db2 == dw2 + (long long)L2_D2 * L2_HD && aligned16(dw1))
     return launch_slab_reduce(workspace, grid, slab, dw1, accumulate, st);
   // scattered outputs: the same four reductions as one batched launch - per element the summation order of the joined form,
   // so the gradients do not depend on where the caller's (or the allocator's) tensors happen to lie
-  const long long o1 = (long long)MF_HD * fin, o2 = o1 + MF_HD, o3 = o2 + (long long)MF_D2 * MF_HD;
+  const long long o1 = (long long)L2_HD * fin, o2 = o1 + L2_HD, o3 = o2 + (long long)L2_D2 * L2_HD;
   const SlabSeg segs[4] = {{workspace, dw1, slab, grid, (int)o1, 1, accumulate ? 1 : 0},
-                           {workspace + o1, db1, slab, grid, MF_HD, 1, accumulate ? 1 : 0},
-                           {workspace + o2, dw2, slab, grid, MF_D2 * MF_HD, 1, accumulate ? 1 : 0},
-                           {workspace + o3, db2, slab, grid, MF_D2, 1, accumulate ? 1 : 0}};
+                           {workspace + o1, db1, slab, grid, L2_HD, 1, accumulate ? 1 : 0},
+                           {workspace + o2, dw2, slab, grid, L2_D2 * L2_HD, 1, accumulate ? 1 : 0},
+                           {workspace + o3, db2, slab, grid, L2_D2, 1, accumulate ? 1 : 0}};
   return launch_slab_reduce_batch(segs, 4, st);
 }
