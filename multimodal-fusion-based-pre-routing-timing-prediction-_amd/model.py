@@ -317,7 +317,7 @@ class PathModel(nn.Module):
         (src/train.py:490-511), but level-invariant work is hoisted: fcn once over all sampled paths,
         mlp_alpha once over all level ids, mlp_fuse once over all endpoints, one autograd node for the sweep.
           level_nodes    list over levels of node-id lists (python ints or device int32 tensors)
-          targets        device int32 tensor [T]: endpoints ordered by level (the order forward() would emit)
+          targets        device int32 tensor [T]: endpoints, in any order (forward() would emit them ordered by level)
           target_levels  device int32 tensor [T]: level id of each endpoint
           path_map       MaskedPathMap / dense (T,P) tensor over the same T rows, or None
         Returns predictions (T,)."""
@@ -327,12 +327,15 @@ class PathModel(nn.Module):
                 _sweep.sweep_forward_all(self.gnn, graph, level_nodes, targets)
             return None
         h_gnn = _sweep.sweep_forward_all(self.gnn, graph, level_nodes, targets) if self.gnn is not None else None
-        return self.fuse_heads(h_gnn, path_map, target_levels, len(level_nodes))
+        # an outside caller's endpoints need not be ordered by level: the order-free gradient of the level gather
+        return self.fuse_heads(h_gnn, path_map, target_levels, len(level_nodes), levels_ascending=False)
 
-    def fuse_heads(self, h_gnn, path_map, target_levels, num_levels, h_cnn=None):
+    def fuse_heads(self, h_gnn, path_map, target_levels, num_levels, h_cnn=None, levels_ascending=True):
         """Fusion head over all T endpoints at once: fcn(path_map), mlp_alpha(level of each endpoint), mlp_fuse
         (src/model.py:271-292 with the level-invariant work hoisted).  `h_cnn` may be passed pre-computed
-        (= self._fcn(path_map)) so that the caller can overlap it with the tail of the sweep."""
+        (= self._fcn(path_map)) so that the caller can overlap it with the tail of the sweep.  levels_ascending: the caller
+        guarantees non-decreasing `target_levels` (DesignBatch.select sorts them); unchecked, the gradient into mlp_alpha
+        is wrong without it."""
         if h_cnn is None:
             h_cnn = self._fcn(path_map) if (self.fcn is not None and path_map is not None) else None
         cache = self.__dict__.setdefault('_level_ids', {})
@@ -340,8 +343,8 @@ class PathModel(nn.Module):
         lv = cache.get(key)
         if lv is None:
             lv = cache[key] = th.arange(num_levels, dtype=th.float32, device=target_levels.device).unsqueeze(1)
-        # endpoints arrive ordered by level (src/train.py:490-511 emits them level by level): the gradient of the gather is a
+        # endpoints ordered by level (src/train.py:490-511 emits them level by level): the gradient of the gather is a
         # segmented sum over contiguous runs
-        h_global = MF.gather_rows(self.mlp_alpha(lv), target_levels, ascending=True)   # (T, 32), row = alpha(level of t)
+        h_global = MF.gather_rows(self.mlp_alpha(lv), target_levels, ascending=levels_ascending)   # (T, 32), alpha(level of t)
         parts = [p for p in (h_gnn, h_cnn, h_global) if p is not None]
         return self.mlp_fuse(MF.concat_cols(*parts) if len(parts) > 1 else parts[0]).squeeze(-1)

@@ -387,6 +387,20 @@ class OracleTrainer:
         leaves = [v for v in self.pm.values() if v.requires_grad] + [v for v in self.pc.values() if v.requires_grad]
         self.optim = torch.optim.Adam(leaves, lr, weight_decay=weight_decay)
 
+    def leaf(self, name):
+        """The trainable tensor of a state-dict name (PathModel or CNN)."""
+        return self.pm[name] if name in self.pm else self.pc[name]
+
+    def load_adam(self, exp_avg, exp_avg_sq, step):
+        """Resume torch.optim.Adam mid-run: exp_avg / exp_avg_sq map state-dict names to the first / second moments and
+        `step` is the number of steps already taken (the bias corrections of the next step use step + 1).  Parameters not
+        named keep an empty state, which Adam fills with zero moments on their first step."""
+        for k, m in exp_avg.items():
+            p = self.leaf(k)
+            self.optim.state[p] = {'step': torch.tensor(float(step), dtype=torch.float32),
+                                   'exp_avg': torch.zeros_like(p).copy_(m.reshape(p.shape)),
+                                   'exp_avg_sq': torch.zeros_like(p).copy_(exp_avg_sq[k].reshape(p.shape))}
+
     def forward(self, design, csr, path_ids, feat_map=None):
         extra = dict(rounding=self.rounding) if self.rounding is not None else {}
         if feat_map is not None:

@@ -16,7 +16,7 @@ would fail, so the test sees where rounding happens) depends on the part of the 
   Measured on one MI355X (e_hip / e_32 / e_plain), config A: predictions 1.0e-3 / 6.4e-5 / 2.8e-2, loss 5.8e-6 / 3.7e-8 /
     3.1e-3, d loss / d feature map 1.6e-7 / 1.1e-7 / 2.9e-2; irregular fan-in: predictions 2.5e-6 / 2.9e-6 / 3.8e-3,
     loss 7.3e-8 / 7.3e-8 / 2.6e-3.  U-Net gradient means 0.175 / 0.157 / 0.345 (2 x 64²), 0.090 / 0.252 / 0.309
-    (3 x 40 x 96 avg), 0.167 / 0.155 / 0.325 (1 x 256²).
+    (3 x 40 x 96 avg), 0.167 / 0.155 / 0.325 (1 x 256²), 0.14 / 0.13 / 0.33 (8 x 64²).
   * U-Net.  A last-bit difference in front of a bf16 rounding moves the stored value by a whole bf16 step once it crosses
     a rounding boundary and every later layer rounds again, so through 14 BatchNorm layers fp32 arithmetic (the kernels'
     and the fp32 oracle's) is promoted to bf16-sized differences: the fp32 rounding oracle sits 0.03 - 0.18 relative L2
@@ -253,12 +253,13 @@ UNET_KERNELS = {'u16_pack_kernel', 'u16_conv3x3_kernel', 'u16_conv3x3_wgrad_kern
                 'u16_pool_bwd_kernel', 'u16_outconv_fwd_kernel', 'u16_outconv_bwd_kernel'}
 
 
-@pytest.mark.parametrize('N,H,W,pooling', [(2, 64, 64, 'max'), (3, 40, 96, 'avg'), (1, 256, 256, 'max')])
+@pytest.mark.parametrize('N,H,W,pooling', [(2, 64, 64, 'max'), (3, 40, 96, 'avg'), (1, 256, 256, 'max'), (8, 64, 64, 'max')])
 def test_unet_module_vs_rounding_oracle(dev, N, H, W, pooling):
     """The bf16-storage U-Net on its own: output, every parameter gradient (relative L2 per tensor and the mean over all
     tensors) and the running statistics against the fp64 rounding oracle.  The convolutions take 4 x 64 pixel tiles where
     a level is at least 64 wide and 8 x 32 tiles below (unet16_conv.hip:13): 64 x 64 uses both, 40 x 96 adds partial tiles
-    of both kinds, 256 x 256 (one image, the benched tile size) is the bench's shape."""
+    of both kinds, 256 x 256 (one image, the benched tile size) is the bench's shape, 8 x 64 x 64 the bench's image count
+    (per-image BatchNorm statistics of images 4-7)."""
     hip, names, gy, o64, o32, op = unet_case(dev, N, H, W, pooling)
     assert UNET_KERNELS <= names, sorted(UNET_KERNELS - names)
     q = Bounds(f'U-Net {N}x{H}x{W} {pooling}', hip, o32, op)

@@ -870,3 +870,37 @@ def test_dropin_replayed_graphs_own_their_scratch_and_tables(dev):
         S.SWEEP_REPLAY, unet16.REPLAY = saved
     assert out[True][0] == out[False][0]
     assert torch.equal(out[True][1], out[False][1])
+
+
+def test_forward_sweep_takes_endpoints_in_any_order(dev):
+    """PathModel.forward_sweep is a public entry: the same endpoints shuffled (with their levels, path-map rows and loss
+    weights) give the predictions of the level-ordered call, permuted, and the same mlp_alpha gradients.  fuse_heads'
+    sorted segment sum (gather_rows(..., ascending=True)) is only right for callers that order the endpoints by level."""
+    from mmft.synth import synth_design
+    from mmft.train import build_models
+    d = synth_design(N=2048, L=12, tile=32, seed=61, end_frac=0.25)
+    pmodel, _ = build_models(map_size=d.map_size, device=dev, seed=5)
+    g = PinGraph.from_synth(d, out_dim=128).to(dev)
+    levels = [l.tolist() for l in d.levels]
+    rng = np.random.default_rng(3)
+    pids = rng.permutation(d.num_paths)[:64]
+    pids = pids[np.argsort(d.path2level[pids], kind='stable')]
+    ends = torch.from_numpy(d.path2endpoint[pids].astype(np.int32))
+    lvs = torch.from_numpy(d.path2level[pids].astype(np.int32))
+    assert len(set(lvs.tolist())) > 3
+    pmap = torch.rand(len(pids), d.map_size ** 2, generator=torch.Generator().manual_seed(4))
+    w = torch.randn(len(pids), generator=torch.Generator().manual_seed(5))
+
+    def run(perm):
+        g.ndata['h'] = torch.zeros((d.N, 128), device=dev)
+        pmodel.zero_grad()
+        hats = pmodel.forward_sweep(g, levels, ends[perm].to(dev), lvs[perm].to(dev), pmap[perm].to(dev))
+        (hats * w[perm].to(dev)).sum().backward()
+        return hats.detach(), {k: p.grad.detach().clone() for k, p in pmodel.mlp_alpha.named_parameters()}
+    perm = torch.from_numpy(rng.permutation(len(pids)))
+    assert not bool((lvs[perm][1:] >= lvs[perm][:-1]).all())
+    h0, g0 = run(torch.arange(len(pids)))
+    h1, g1 = run(perm)
+    assert rel_err(h1, h0[perm.to(dev)]) < 1e-6
+    for k in g0:
+        assert float(g0[k].abs().max()) > 0 and rel_err(g1[k], g0[k]) < 1e-6, k

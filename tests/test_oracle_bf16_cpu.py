@@ -298,3 +298,43 @@ def test_oracle_trainer_step_with_rounding():
             continue
         big = g.abs() > 1e-4
         assert torch.allclose((now - v)[big], -1e-3 * g[big].sign(), rtol=1e-3, atol=0), k
+
+
+def test_oracle_trainer_resumes_adam_mid_run():
+    """OracleTrainer.load_adam (the GPU trajectory tests start the oracle from the HIP optimizer's moments and step counter):
+    a trainer built from the parameters and running statistics after one step, its Adam state loaded, and stepped twice
+    equals three uninterrupted torch.optim.Adam steps bit for bit; loaded with the wrong step count it does not.  In fp64:
+    the fp32 CPU oracle is not bitwise repeatable run to run (threaded weight-gradient GEMMs), so bit for bit means fp64."""
+    dtype = torch.float64
+    from mmft.synth import config_design
+    from mmft.train import build_models
+    d = config_design('A', L=8)
+    csr = R.design_csr(d)
+    pmodel, cnn = build_models(map_size=d.map_size, device='cpu', seed=9294)
+    pm_state = {k: v.detach().clone() for k, v in pmodel.state_dict().items()}
+    pc_state = {k: v.detach().clone() for k, v in cnn.state_dict().items()}
+    rng = np.random.default_rng(8)
+    batches = [rng.permutation(d.num_paths)[:30].tolist() for _ in range(3)]
+    whole = R.OracleTrainer(pm_state, pc_state, dtype=dtype)
+    for ids in batches:
+        whole.step(d, csr, ids)
+    first = R.OracleTrainer(pm_state, pc_state, dtype=dtype)
+    first.step(d, csr, batches[0])
+    names = [k for k, v in list(first.pm.items()) + list(first.pc.items()) if first.optim.state.get(v)]
+    assert names and all(int(first.optim.state[first.leaf(k)]['step']) == 1 for k in names)
+    m = {k: first.optim.state[first.leaf(k)]['exp_avg'] for k in names}
+    v = {k: first.optim.state[first.leaf(k)]['exp_avg_sq'] for k in names}
+    state = lambda t: ({k: x.detach().clone() for k, x in t.pm.items()}, {k: x.detach().clone() for k, x in t.pc.items()})
+
+    def resumed(step):
+        t = R.OracleTrainer(*state(first), dtype=dtype)
+        t.load_adam(m, v, step)
+        for ids in batches[1:]:
+            t.step(d, csr, ids)
+        return t
+    r = resumed(1)
+    for k in list(whole.pm) + list(whole.pc):
+        a, b = whole.pm.get(k, whole.pc.get(k)), r.pm.get(k, r.pc.get(k))
+        assert torch.equal(a.detach(), b.detach()), k
+    wrong = resumed(0)
+    assert not all(torch.equal(whole.leaf(k).detach(), wrong.leaf(k).detach()) for k in names)
