@@ -1,7 +1,7 @@
 """bench.py - train-step throughput of the multimodal-fusion hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
-    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+    python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W [--full]
 
 One "step" = one reference-shaped mini-batch (src/train.py:475-562) over a batch of synthetic designs:
 U-Net forward, L-level netlist sweep, fusion head, MSE, full backward, Adam (plus one RCCL all-reduce of the
@@ -11,10 +11,16 @@ names it: bf16 operands / fp32 accumulate on the MFMA-bound contractions (--dtyp
 Inputs (graphs, features, masks, images) are resident in HBM before the timed region.  Data parallel =
 designs sharded over ranks (weak scaling: every rank steps its own 8 designs).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with two extra objects:
+Rank 0 prints ONE JSON line: metric, value (designs/s over the timed steps), unit, higher_is_better, dtype,
+ms_per_step, the workload, and the loss and training MAE of the last timed step.  A plain run does only that: it
+sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  `--full` measures everything else
+after the timed steps (each part can be left out with its --no-* option); without it these are null or absent:
   roofline      dominant kernel by device time: algorithmic flops (or bytes) / launch duration, both from
                 HIP events recorded by the library on the launch stream (mmft_prof_*), in a separate
                 instrumented region of the same steps so that `value` is not perturbed by the events;
+  heldout_eval  endpoint-slack MAE on a held-out synthetic design; in bf16 mode also
+                heldout_eval_f32_same_schedule, the same schedule replayed in exact fp32 (the MAE drift);
+  dropin_*      step time of the per-level drop-in API, with the masked path map and with the dense one;
   cpu_baseline  the CPU oracle (oracle/restatement.py, kind "port") timed on this host on a bounded
                 sample (one design per step as the reference does; 2 warm-up + 10 timed steps, median, anomaly
                 detection off, plus 3 timed steps with torch.autograd.set_detect_anomaly(True) as the reference
@@ -268,12 +274,15 @@ def main():
                     help="'one': the step is ONE HIP graph (in-graph two-stream fork); 'five': five single-stream graphs "
                          "replayed on two streams (gradient buckets handed to the communication stream at the cuts); "
                          "'auto': one on a single GPU, five under data parallelism")
+    ap.add_argument('--full', action='store_true',
+                    help='after the timed steps also measure the roofline, the held-out MAE (and its fp32 drift in bf16 '
+                         'mode), the drop-in API timings and the CPU oracle baseline; the --no-* options below trim it')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-roofline', action='store_true')
     ap.add_argument('--dtype', default='bf16', choices=['f32', 'bf16'],
                     help='bf16 (default: BASELINE.json configs[1] is quoted as "1xMI355X bf16"): bf16 operands / fp32 '
-                         'accumulate on the MFMA-bound contractions, U-Net activations stored bf16; the same schedule is then replayed '
-                         'in exact fp32 for the held-out MAE drift and the fp32 step time.  f32: exact fp32 MFMA everywhere '
+                         'accumulate on the MFMA-bound contractions, U-Net activations stored bf16; with --full the same schedule is '
+                         'then replayed in exact fp32 for the held-out MAE drift and the fp32 step time.  f32: exact fp32 MFMA everywhere '
                          '(the 1e-4 parity mode the GPU tests run in)')
     ap.add_argument('--cpu-steps', type=int, default=10)
     ap.add_argument('--no-drift', action='store_true', help='bf16: skip the fp32 replay of the schedule (MAE drift)')
@@ -286,6 +295,8 @@ def main():
     args = ap.parse_args()
     if args.steps < 1:
         ap.error('--steps must be at least 1')
+    if not args.full:       # a plain run: the headline figure (and --dump-outputs) only
+        args.no_roofline = args.no_drift = args.no_dropin = args.no_cpu_baseline = True
 
     if args.gpus > 1 and 'WORLD_SIZE' not in os.environ:
         sys.exit(self_launch(args))
@@ -321,8 +332,10 @@ def main():
                for sd in design_seeds(rank, args.designs)]
     log(f'rank {rank}: {len(designs)} designs generated')
     pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=9294)
-    pm_state = {k: v.detach().cpu().clone() for k, v in pmodel.state_dict().items()}
-    pc_state = {k: v.detach().cpu().clone() for k, v in cnn.state_dict().items()}
+    pm_state = pc_state = None      # the initial parameters, for the fp32 replay and the CPU oracle of a --full run
+    if args.full:
+        pm_state = {k: v.detach().cpu().clone() for k, v in pmodel.state_dict().items()}
+        pc_state = {k: v.detach().cpu().clone() for k, v in cnn.state_dict().items()}
     ts = TrainStep(pmodel, cnn, designs, dev, world_size=world, mode=args.mode, overlap=not args.no_overlap, cone=args.cone,
                    keep_grads=False)
     rng = np.random.default_rng(1234 + rank)
@@ -439,7 +452,7 @@ def main():
 
     # accuracy half of BASELINE.json's metric: endpoint-slack MAE on a held-out synthetic design after the steps above
     heldout_mae = None
-    if rank == 0:
+    if rank == 0 and args.full:
         from mmft.evaluate import validate
         held = synth_design(N=args.nodes, L=args.levels, tile=args.tile, seed=9294 + 100003)
         ev = TrainStep(pmodel, cnn, [held], dev, mode=args.mode, overlap=False, with_optimizer=False)
@@ -533,6 +546,7 @@ def main():
             'vs_baseline': None,
             'dtype': args.dtype,
             'data': 'synthetic',
+            'full': bool(args.full),
             'config': {
                 'workload': f'{"config B" if (args.designs, args.nodes, args.levels, args.tile) == (8, 65536, 64, 256) else "custom"}: {args.designs} designs/step/GPU, {args.nodes}-node netlist, {args.levels} levels, '
                             f'{args.tile}x{args.tile} tile, {args.batch_paths} endpoints/design, UNet(max), '

@@ -3,7 +3,7 @@
 OUT=gpurun_out/pairtrace
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
-rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python3 bench.py --no-graph --no-overlap --no-cpu-baseline --no-roofline --no-drift --no-dropin --steps 3 --warmup 2 > $OUT/run.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -- python3 bench.py --full --no-graph --no-overlap --no-cpu-baseline --no-roofline --no-drift --no-dropin --steps 3 --warmup 2 > $OUT/run.log 2>&1 || exit 1
 python3 - <<'PY'
 import csv, glob
 f = glob.glob('gpurun_out/pairtrace/tr/*/*_kernel_trace.csv')[0]
