@@ -64,8 +64,21 @@ class PinGraph:
         self._csr_host = {}
         self._csr_dev = {}
         self._level_cache = {}
-        self._sweep = None          # per-sweep state, owned by mmft.sweep
+        self._reset_sweep_state()
         self._build_csr()
+
+    def _reset_sweep_state(self):
+        """What the sweep and the deferred head keep on a graph between calls.  None of it follows a graph to another device."""
+        self._sweep = None                      # mmft.sweep: SweepState of the sweep in flight (or the last one)
+        self._sweep_bufs = {}                   # mmft.sweep: named device buffers, 'key' (their shape), 'replay' (_SweepRecord)
+        self._seen_lists = []                   # mmft.sweep.level_forward: host level lists of the per-level sweep in flight
+        self._spec_lists = None                 # ... the lists the next level-0 call sweeps speculatively
+        self._spec_disabled = False             # ... True for good once a training step arrived with other lists
+        self._spec_stream = None                # ... side stream of the speculative sweep
+        self._cone_mask = None                  # mmft.sweep.sweep_forward_all: per-node fan-in-cone flags, reused every step
+        self._head_takes_gradients = False      # model.PathModel.forward: True around its gnn call (deferred head)
+        self._head_level_th = None              # model._HeadBatch: level-id tensors of the previous step's level calls
+        self.targets_unique = None              # mmft.train.TrainStep: True when the step's endpoints hold no duplicate
 
     # ------------------------------------------------------------------ DGL-like surface
     @property
@@ -113,7 +126,7 @@ class PinGraph:
         g._csr_host = self._csr_host
         g._csr_dev = {}
         g._level_cache = {}
-        g._sweep = None
+        g._reset_sweep_state()
         return g
 
     def in_degrees(self, etype):

@@ -23,6 +23,24 @@ _MLP_KEYS = ('fc_cell_self', 'fc_net_self', 'fc_cell_neigh')
 
 
 class SweepState:
+    """State of one sweep of one graph.  Every field is declared here; __init__ gives each the value of a per-level sweep,
+    the whole-sweep entry (_run_sweep, SweepFn) and the deferred head (model.py) overwrite theirs."""
+    __slots__ = ('graph', 'h', 'N', 'D', 'Hd', 'relu', 'cell_feat', 'net_feat', 'params', 'need_grad', '_bufs',
+                 'A', 'LSE', 'HS', 'HN', 'G', 'DA', 'DHN', 'tflag', 'level_meta', 'levels', 'token', 'next_level',
+                 'bwd_active', 'complete', 'fold', 'level_lists', 'PRE', 'attn', 'wpack', 'active', 'record',
+                 'spec_lists', 'spec_token', 'spec_tix', 'target_order', 'targets_unique',
+                 'hid16', 'feat_fused', 'prep', 'row_sets', 'head_batch', '_empty_rows')
+    # what a forward sweep decides and its backward needs: a replayed forward skips the code that sets these
+    DECIDED = ('levels', 'wpack', 'hid16', 'HN', 'DHN', 'prep', 'row_sets', 'feat_fused', 'PRE', 'attn')
+    assert set(DECIDED) <= set(__slots__)
+
+    def decided(self):
+        return {k: getattr(self, k) for k in self.DECIDED}
+
+    def adopt(self, decided):
+        for k, v in decided.items():
+            setattr(self, k, v)
+
     def __init__(self, graph, conv):
         self.graph = graph
         h = graph.ndata['h']
@@ -40,7 +58,7 @@ class SweepState:
         self.net_feat = _feat(graph, 'net_feat', conv.net_feat_dim)
         self.params = [p for k in _MLP_KEYS for p in _mlp2_params(getattr(conv, k))]
         self.need_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.params)
-        bufs = graph.__dict__.setdefault('_sweep_bufs', {})
+        bufs = graph._sweep_bufs
         key = (self.N, self.D, self.Hd, h.device)
         if bufs.get('key') != key:
             bufs.clear()
@@ -69,6 +87,9 @@ class SweepState:
         self.spec_tix = []
         self.target_order = None
         self.targets_unique = None
+        self.hid16 = self.feat_fused = False        # whole-sweep entry, bf16 mode: HN / DHN stored as bf16; *_self MLPs without HS
+        self.prep = self.row_sets = None            # ... recorded launches (record.calls); rows of the (cell, net, cell >= 2) levels
+        self.head_batch = self._empty_rows = None   # deferred head: model._HeadBatch of the step; [0, D] result of a level without endpoints
 
     def _buf(self, name, width, dtype=torch.float32):
         b = self._bufs.get(name)
@@ -79,10 +100,30 @@ class SweepState:
             self._bufs[name] = b
         return b
 
-    def begin_backward(self, zero_da=True, zero_g=True):
-        """zero_da=False (whole-sweep entry): every DA row the reverse pull reads belongs to a cell node of a level >= 2,
-        and the reverse sweep writes that row (fc_cell_neigh's input gradient) before any lower level pulls from it,
-        so the 268 MB fill per step is skipped; the per-level drop-in form keeps it (a caller may stop a sweep early)."""
+    def hidden_grads(self):
+        """DHN, the hidden gradients of fc_cell_neigh, in the format the forward chose for HN; allocated on first use."""
+        if self.DHN is None:
+            self.DHN = self._buf('DHN16', self.Hd, torch.bfloat16) if self.hid16 else self._buf('DHN', self.Hd)
+        return self.DHN
+
+    @property
+    def fast(self):
+        """The reverse sweep may skip the fills of G / DA (2 x 268 MB per step at config B): the level lists are a complete
+        schedule of the graph, so every row a pull reads was rewritten earlier in the same reverse sweep (a DA row by
+        fc_cell_neigh's input gradient of its cell level >= 2).  A partial schedule (truncated lists; a per-level sweep may
+        stop early) leaves consumers outside it with rows of an earlier step - or uninitialised memory - and fan-in-cone
+        pruning skips rows, which must read as zero: both buffers are zero-filled, the own-gradient flags not used."""
+        return self.complete and self.active is None
+
+    def seed_targets(self, tix, gout, order=None, unique=None):
+        """Zero / flag / fill the endpoint rows `tix` of G with `gout` (tix None or empty: only start the reverse sweep)."""
+        self.begin_backward()
+        if tix is not None and tix.numel():
+            if self.fast:
+                ops.target_rows_begin(self.G, tix, self.tflag)
+            ops.scatter_add_targets(self.G, tix, ops.strided_rows(gout), order=order, unique=unique)
+
+    def begin_backward(self):
         if not self.bwd_active:
             if self.G is None:
                 self.G = self._buf('G', self.D)
@@ -90,15 +131,13 @@ class SweepState:
                 self.DA = self._buf('DA', self.D)
                 if fresh:
                     self.DA.zero_()
-            if zero_g:
-                self.G.zero_()
-            else:
-                # whole-sweep entry: only the sampled endpoints start with a gradient of their own; the reverse pull
-                # takes zero for every other row (flag per node), so the 268 MB fill of G per step is skipped too
+            if self.fast:
+                # only the sampled endpoints start with a gradient of their own; the reverse pull takes zero for every other row (flag per node)
                 if 'tflag' not in self._bufs:
                     self._bufs['tflag'] = torch.zeros(self.N, dtype=torch.uint8, device=self.h.device)
                 self.tflag = self._bufs['tflag']
-            if zero_da:
+            else:
+                self.G.zero_()
                 self.DA.zero_()
             self.bwd_active = True
 
@@ -195,11 +234,7 @@ def _cell_neigh_bwd(st, rows, w1g, w2g, keep_dhn=False):
     """DA[rows] = ((G[rows] W2g) * relu'(HN[rows])) W1g.  With keep_dhn the hidden gradient rows are also written to
     st.DHN, so the batched weight-gradient pass does not recompute them."""
     if ops.mlp2_fusable(st.D, st.Hd, st.D):
-        dhn_out = None
-        if keep_dhn:
-            if st.DHN is None:
-                st.DHN = st._buf('DHN16', st.Hd, torch.bfloat16) if getattr(st, 'hid16', False) else st._buf('DHN', st.Hd)
-            dhn_out = st.DHN
+        dhn_out = st.hidden_grads() if keep_dhn else None
         if st.wpack is not None:
             ops.mlp2_rows_bf16(st.G, rows, st.wpack[2], None, st.wpack[3], None, st.DA, mask=st.HN, hid_out=dhn_out,
                                active=st.active)
@@ -247,10 +282,7 @@ class LevelFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gtoken, gout):
         st, g, level_id, rows = ctx.state, ctx.state.graph, ctx.level_id, ctx.rows
-        st.begin_backward()
-        if ctx.tix.numel() and gout is not None:
-            go = ops.strided_rows(gout)
-            ops.scatter_add_targets(st.G, ctx.tix, go, unique=g.__dict__.get('targets_unique'))
+        st.seed_targets(ctx.tix if gout is not None else None, gout, unique=g.targets_unique)
         P = [_w(p) for p in st.params]
         (w1c, b1c, w2c, b2c, w1n, b1n, w2n, b2n, w1g, b1g, w2g, b2g) = P
         dc = None
@@ -330,7 +362,7 @@ def _batched_param_grads(st, P, dhn_ready=False):
     rn = _cat_rows(st, lambda l: l % 2 == 1)
     rc2 = _cat_rows(st, lambda l: l % 2 == 0 and l > 0)
     zeros = lambda ps: [torch.zeros_like(p) for p in ps]
-    if getattr(st, 'feat_fused', False):
+    if st.feat_fused:
         feat = lambda sinks, rows, X, w1, b1, w2: gradsink.deliver_many(
             sinks, lambda o1, ob1, o2, ob2: ops.mlp2_feat_bwd_bf16(st.G, X, rows, w1, b1, w2, dw1=o1, db1=ob1, dw2=o2, db2=ob2))
         gc = feat(S[0:4], rc, st.cell_feat, w1c, b1c, w2c) if rc is not None else zeros(P[0:4])
@@ -353,93 +385,88 @@ def attention_coefficients(conv):
 
 
 def level_forward(conv, graph, cur_nodes, targets, level_id):
-    """Body of PathConv.forward (both branches)."""
-    seen = graph.__dict__.setdefault('_seen_lists', [])
-    spec_active = False
-    if level_id == 0:
-        spec = graph.__dict__.get('_spec_lists')
-        if len(seen) >= 2 and (spec is None or len(seen) >= len(spec)):
-            spec = graph.__dict__['_spec_lists'] = list(seen)            # the previous sweep's lists, levels 0 .. k
-        del seen[:]
-        if SPECULATE and spec is not None and not graph.__dict__.get('_spec_disabled') and not torch.is_tensor(cur_nodes) \
-                and _same_list(cur_nodes, spec[0]):
-            dev_ = graph.ndata['h'].device
-            # (only with gradient sinks on every parameter - FlatAdam: parameters that accumulate through autograd's own
-            # AccumulateGrad nodes, created under the caller's stream, would be fed from another stream)
-            sinks_ = all(gradsink.of(p) is not None for k in _MLP_KEYS for p in _mlp2_params(getattr(conv, k)))
-            if SPEC_SIDE_STREAM and sinks_ and not torch.cuda.is_current_stream_capturing():
-                # the whole sweep runs on a stream of its own: its autograd node then runs its backward there as well, next
-                # to the U-Net's backward on the caller's stream (the caller's loop has one stream; inside a captured step
-                # TrainStep forks the streams itself).  The caller's stream waits for the sweep right away - every later level
-                # call reads h.
-                side = graph.__dict__.get('_spec_stream')
-                if side is None or side.device != dev_:
-                    side = graph.__dict__['_spec_stream'] = torch.cuda.Stream(device=dev_)
-                cur_ = torch.cuda.current_stream(dev_)
-                side.wait_stream(cur_)
-                with torch.cuda.stream(side):
-                    st, token = _run_sweep(conv, graph, spec, None)
-                cur_.wait_stream(side)
-            else:
-                st, token = _run_sweep(conv, graph, spec, None)
-            st.spec_lists, st.spec_token, st.spec_tix, st.next_level = spec, token, [], 0
-            spec_active = True
-    else:
-        spec_active = graph._sweep is not None and graph._sweep.spec_lists is not None
+    """Body of PathConv.forward (both branches): one level of a speculative or of a strict per-level sweep."""
+    spec = _start_sweep(conv, graph, cur_nodes) if level_id == 0 else (graph._sweep is not None and graph._sweep.spec_lists is not None)
     if not torch.is_tensor(cur_nodes):
-        seen.append(cur_nodes)
-    if spec_active:
-        st = graph._sweep
-        if st.h is not graph.ndata['h']:
-            raise RuntimeError("graph.ndata['h'] was replaced in the middle of a sweep; restart from level 0")
-        if level_id != st.next_level:
-            raise RuntimeError(f'PathConv: levels must arrive in increasing order (got {level_id}, expected {st.next_level})')
-        st.next_level = level_id + 1
-        mismatch = level_id >= len(st.spec_lists) or torch.is_tensor(cur_nodes) or not _same_list(cur_nodes, st.spec_lists[level_id])
-        if mismatch and not st.need_grad:
-            # inference with other lists than last time (e.g. validate() after a truncated sweep): the levels below this
-            # one were computed from identical lists, so the sweep simply continues level by level from here
-            graph.__dict__['_spec_lists'] = None
-            nst = SweepState(graph, conv)
-            nst.next_level = level_id
-            graph._sweep = st = nst
-            spec_active = False
-        elif mismatch:
-            # training: the levels below were computed from identical lists, but the autograd node of the speculative sweep
-            # covers the recorded lists of ALL levels - this step cannot be completed.  Speculation is switched off for the
-            # graph, so re-running the step (and every later one) takes the strict per-level path.
-            graph.__dict__['_spec_lists'] = None
-            graph.__dict__['_spec_disabled'] = True
-            graph._sweep = None
-            raise RuntimeError(f'PathConv: level {level_id} arrived with a node list that differs from the one this graph was '
-                               f'swept with before - the speculative whole-sweep of the level-0 call used the recorded lists. '
-                               f'Speculation is now disabled for this graph: zero graph.ndata["h"] and run the step again '
-                               f'(mmft.sweep.SPECULATE = False avoids the first failure for loops whose level lists change).')
-    if spec_active:
-        tix = graph.level_rows(level_id, targets, 'targets')
-        if not tix.numel():
-            e = st.__dict__.get('_empty_rows')
-            if e is None:
-                e = st.__dict__['_empty_rows'] = st.h.new_zeros((0, st.D))
-            return e
-        if st.need_grad:
-            st.spec_tix.append(tix)
-            if graph.__dict__.get('_head_takes_gradients'):
-                # the caller (PathModel's deferred head) gathers h[targets] inside its one-call level head and scatters the
-                # endpoint gradients itself from its root node: no launch, no autograd node here
-                return st.h.new_empty((tix.numel(), 0))
-            return TargetGatherFn.apply(st.spec_token, st, tix, graph.__dict__.get('targets_unique'))
-        return ops.gather_rows(st.h, tix)
-    if level_id == 0 or graph._sweep is None:
+        graph._seen_lists.append(cur_nodes)
+    if not spec and (level_id == 0 or graph._sweep is None):
         if level_id != 0:
             raise RuntimeError('PathConv: a sweep must start at level 0 (src/train.py:489-490)')
         graph._sweep = SweepState(graph, conv)
     st = graph._sweep
-    if graph.ndata['h'] is not st.h:
+    if st.h is not graph.ndata['h']:
         raise RuntimeError("graph.ndata['h'] was replaced in the middle of a sweep; restart from level 0")
     if level_id != st.next_level:
         raise RuntimeError(f'PathConv: levels must arrive in increasing order (got {level_id}, expected {st.next_level})')
     st.next_level = level_id + 1
+    return (_spec_level if spec else _strict_level)(conv, graph, st, cur_nodes, targets, level_id)
+
+
+def _start_sweep(conv, graph, cur_nodes):
+    """Level-0 call: the lists the graph was just swept with become the ones to speculate with, and when this call's list
+    is the first of them the WHOLE sweep runs now (SPECULATE below).  True when it did."""
+    seen, spec = graph._seen_lists, graph._spec_lists
+    if len(seen) >= 2 and (spec is None or len(seen) >= len(spec)):
+        spec = graph._spec_lists = list(seen)            # the previous sweep's lists, levels 0 .. k
+    del seen[:]
+    if not (SPECULATE and spec is not None and not graph._spec_disabled and not torch.is_tensor(cur_nodes) and _same_list(cur_nodes, spec[0])):
+        return False
+    dev_ = graph.ndata['h'].device
+    # (only with gradient sinks on every parameter - FlatAdam: parameters that accumulate through autograd's own
+    # AccumulateGrad nodes, created under the caller's stream, would be fed from another stream)
+    sinks_ = all(gradsink.of(p) is not None for k in _MLP_KEYS for p in _mlp2_params(getattr(conv, k)))
+    if SPEC_SIDE_STREAM and sinks_ and not torch.cuda.is_current_stream_capturing():
+        # the whole sweep runs on a stream of its own: its autograd node then runs its backward there as well, next to the
+        # U-Net's backward on the caller's stream (the caller's loop has one stream; inside a captured step TrainStep forks
+        # the streams itself).  The caller's stream waits for the sweep right away - every later level call reads h.
+        side = graph._spec_stream
+        if side is None or side.device != dev_:
+            side = graph._spec_stream = torch.cuda.Stream(device=dev_)
+        cur_ = torch.cuda.current_stream(dev_)
+        side.wait_stream(cur_)
+        with torch.cuda.stream(side):
+            st, token = _run_sweep(conv, graph, spec, None)
+        cur_.wait_stream(side)
+    else:
+        st, token = _run_sweep(conv, graph, spec, None)
+    st.spec_lists, st.spec_token, st.spec_tix, st.next_level = spec, token, [], 0
+    return True
+
+
+def _spec_level(conv, graph, st, cur_nodes, targets, level_id):
+    """One level of a speculative sweep: checks that the list is the one the level-0 call swept with, returns h[targets]."""
+    if level_id >= len(st.spec_lists) or torch.is_tensor(cur_nodes) or not _same_list(cur_nodes, st.spec_lists[level_id]):
+        graph._spec_lists = None
+        if not st.need_grad:
+            # inference with other lists than last time (e.g. validate() after a truncated sweep): the levels below this
+            # one were computed from identical lists, so the sweep simply continues level by level from here
+            graph._sweep = st = SweepState(graph, conv)
+            st.next_level = level_id + 1
+            return _strict_level(conv, graph, st, cur_nodes, targets, level_id)
+        # training: the autograd node of the speculative sweep covers the recorded lists of ALL levels
+        graph._spec_disabled = True
+        graph._sweep = None
+        raise RuntimeError(f'PathConv: level {level_id} arrived with a node list that differs from the one this graph was '
+                           f'swept with before - the speculative whole-sweep of the level-0 call used the recorded lists. '
+                           f'Speculation is now disabled for this graph: zero graph.ndata["h"] and run the step again '
+                           f'(mmft.sweep.SPECULATE = False avoids the first failure for loops whose level lists change).')
+    tix = graph.level_rows(level_id, targets, 'targets')
+    if not tix.numel():
+        if st._empty_rows is None:
+            st._empty_rows = st.h.new_zeros((0, st.D))
+        return st._empty_rows
+    if st.need_grad:
+        st.spec_tix.append(tix)
+        if graph._head_takes_gradients:
+            # the caller (PathModel's deferred head) gathers h[targets] inside its one-call level head and scatters the
+            # endpoint gradients itself from its root node: no launch, no autograd node here
+            return st.h.new_empty((tix.numel(), 0))
+        return TargetGatherFn.apply(st.spec_token, st, tix, graph.targets_unique)
+    return ops.gather_rows(st.h, tix)
+
+
+def _strict_level(conv, graph, st, cur_nodes, targets, level_id):
+    """One level of a strict per-level sweep: a LevelFn node on the sweep's token chain."""
     rows = graph.level_rows(level_id, cur_nodes, 'nodes')
     tix = graph.level_rows(level_id, targets, 'targets')
     c12 = None
@@ -485,8 +512,6 @@ FUSED_FIRST_LAYER_GRADS = True      # mmft_mlp2_first_layer_grads for the *_self
 SWEEP_REPLAY = True      # drop-in loop: the speculative sweep's forward / reverse launches replayed from captured HIP graphs
 # (tools/ab_dropin.py, flags toggled inside one process, config B, ms per drop-in step: plain 7.31, recorded launches
 #  6.69, + own stream 6.59, + replay 5.94)
-
-_REPLAY_STATE = ('levels', 'wpack', 'hid16', 'HN', 'DHN', 'prep', 'row_sets', 'feat_fused', 'PRE', 'attn')
 
 
 class _SweepRecord:
@@ -538,9 +563,9 @@ class SweepFn(torch.autograd.Function):
             launches()
         else:
             if rec.fwd.graph is not None:
-                st.__dict__.update(rec.state)
+                st.adopt(rec.state)
             rec.fwd.run(launches)
-            rec.state = {k: st.__dict__.get(k) for k in _REPLAY_STATE}
+            rec.state = st.decided()
         if tix is None:
             # speculative drop-in sweep: the per-level target gathers (TargetGatherFn) hang off this token
             return st.h.new_zeros(1)
@@ -671,30 +696,19 @@ class SweepFn(torch.autograd.Function):
         st, g = ctx.state, ctx.state.graph
         if ctx.tix is not None:
             st.bwd_active = False
-        # The fills of G / DA (2 x 268 MB per step at config B) may only be skipped when the level lists are a complete
-        # schedule of the graph: then every row a pull reads was rewritten earlier in this reverse sweep.  With a
-        # partial schedule (fan-in cone, truncated lists) consumers outside it keep rows from an earlier step - or
-        # uninitialised memory - so both buffers are zero-filled and the own-gradient flags are not used.
-        # fan-in-cone pruning: rows outside the cone are skipped, so G / DA are zero-filled (their rows must read as zero)
-        fast = st.complete and st.active is None
-        st.begin_backward(zero_da=not fast, zero_g=not fast)
+        fast, tix = st.fast, ctx.tix
+        st.seed_targets(tix, gout, st.target_order, st.targets_unique)
         own = st.tflag if fast else None
-        tix = ctx.tix
         if tix is None:
             # the TargetGatherFn nodes of this sweep have already zeroed / flagged / filled their rows of G
             tix = torch.cat(st.spec_tix) if st.spec_tix else st.h.new_zeros(0, dtype=torch.int32)
-        elif tix.numel():
-            if fast:
-                ops.target_rows_begin(st.G, tix, st.tflag)
-            ops.scatter_add_targets(st.G, tix, ops.strided_rows(gout),
-                                    order=st.target_order, unique=st.targets_unique)
         rec, sinks = ctx.replay, [gradsink.of(p) for p in st.params]
         launches = lambda: SweepFn._backward_launches(ctx, st, g, fast, own)
         if not (rec is not None and fast and ctx.nparams == len(st.params) and not torch.cuda.is_current_stream_capturing()
                 and not lib.PROF_ON and all(r is not None and r[1] != gradsink._epoch[0] for r in sinks)):   # sinks fresh
             grads = launches()
         elif rec.bwd.graph is not None:
-            st.DHN = st._bufs.get('DHN16' if getattr(st, 'hid16', False) else 'DHN')
+            st.DHN = st._bufs.get('DHN16' if st.hid16 else 'DHN')
             rec.bwd.run(launches)
             for r in sinks:
                 gradsink._mark(r)
@@ -724,12 +738,11 @@ class SweepFn(torch.autograd.Function):
                 and st.level_lists is not None:
             pairs = _pinned(st, 1, g.level_bwd_pairs)
         paired = set()
-        prep = getattr(st, 'prep', None) if fast else None
+        prep = st.prep if fast else None
         dev_b, stream_b = lib.stream_args(st.h)
         if pairs is not None:
             cslots, plist, pscratch, pcounters = pairs
-            if st.DHN is None:
-                st.DHN = st._buf('DHN16', st.Hd, torch.bfloat16) if getattr(st, 'hid16', False) else st._buf('DHN', st.Hd)
+            st.hidden_grads()
         for level_id, rows in reversed(st.levels):
             if level_id in paired:
                 continue
@@ -779,19 +792,13 @@ class TargetGatherFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        st = ctx.state
-        fast = st.complete and st.active is None
-        st.begin_backward(zero_da=not fast, zero_g=not fast)
-        if fast:
-            ops.target_rows_begin(st.G, ctx.tix, st.tflag)
-        ops.scatter_add_targets(st.G, ctx.tix, ops.strided_rows(gout), unique=ctx.unique)
-        return st.h.new_zeros(1), None, None, None
+        ctx.state.seed_targets(ctx.tix, gout, unique=ctx.unique)
+        return ctx.state.h.new_zeros(1), None, None, None
 
 
 def _run_sweep(conv, graph, level_nodes, tix, target_order=None, targets_unique=None, active=None):
     """Build the sweep state for the given level lists and run SweepFn (tix None: deferred per-level target gathers)."""
-    st = SweepState(graph, conv)
-    graph._sweep = st
+    graph._sweep = st = SweepState(graph, conv)
     st.active = active
     st.complete = graph.level_set_is_complete(level_nodes)
     st.fold = graph.fold_schedule(level_nodes) if (FOLD_LEVELS and st.complete and not getattr(conv, 'flag_attn', False)) else None
@@ -837,9 +844,7 @@ def sweep_forward_all(conv, graph, level_nodes, targets, target_order=None, targ
         for l, nodes in enumerate(level_nodes):
             meta = graph.level_meta(l, nodes) if not torch.is_tensor(nodes) else None
             specs.append(meta['range'] if (meta and meta['range']) else graph.level_rows(l, nodes, 'nodes'))
-        active = prep.cone_mask([graph.csr('in', 'net'), graph.csr('in', 'cell')], specs, tix,
-                                out=graph.__dict__.get('_cone_mask'))
-        graph.__dict__['_cone_mask'] = active
+        active = graph._cone_mask = prep.cone_mask([graph.csr('in', 'net'), graph.csr('in', 'cell')], specs, tix, out=graph._cone_mask)
     return _run_sweep(conv, graph, level_nodes, tix, target_order, targets_unique, active)[1]
 
 

@@ -146,7 +146,7 @@ class _HeadBatch:
         # mlp_alpha of every level in one launch pair: the level-id tensors of the previous step's calls are tried first
         # (the reference loop and TrainStep pass the same objects every step); a call with another tensor computes its own
         self.fast = HeadLevelCtx(st.h, feat_map, masks, model.fcn, model.mlp_fuse, model.global_dim)
-        prev = graph.__dict__.get('_head_level_th')
+        prev = graph._head_level_th
         self.alpha_src, self.alpha = None, None
         if prev and all(t.numel() == 1 for t in prev):
             with th.no_grad():
@@ -187,19 +187,14 @@ class _HeadBatch:
             params = [p for p in list(m.fcn.parameters()) + list(m.mlp_alpha.parameters()) + list(m.mlp_fuse.parameters())
                       if p.requires_grad]
             th.autograd.backward(hats, gr.reshape(hats.shape), inputs=[h_all, feat] + params)
-        # the endpoint rows of the reverse sweep's gradient buffer, as TargetGatherFn.backward fills them
-        fast = st.complete and st.active is None
-        st.begin_backward(zero_da=not fast, zero_g=not fast)
-        if fast:
-            ops.target_rows_begin(st.G, tix, st.tflag)
-        ops.scatter_add_targets(st.G, tix, h_all.grad, unique=self.graph.__dict__.get('targets_unique'))
-        self.graph.__dict__['_head_level_th'] = list(self.level_th)
+        st.seed_targets(tix, h_all.grad, unique=self.graph.targets_unique)
+        self.graph._head_level_th = list(self.level_th)
         # break the reference cycles batch <-> root node and batch <-> sweep state: the batch holds the CNN feature map, whose
         # autograd node keeps the U-Net's activation arena (260 MB at config B) alive until a full garbage collection otherwise
         dfeat = feat.grad
         self.token = None
-        if st.__dict__.get('head_batch') is self:
-            del st.__dict__['head_batch']
+        if st.head_batch is self:
+            st.head_batch = None
         self.st = self.feat_map = self.masks = self.graph = self.fast = None
         return dfeat
 
@@ -261,19 +256,19 @@ class PathModel(nn.Module):
 
     def forward(self, graph, nodes, eids, target_list, level_id, level_id_th, path_map):
         if self._lazy_ok(graph, target_list, path_map):
-            graph.__dict__['_head_takes_gradients'] = True                     # speculative sweep: plain gather of h[targets]
+            graph._head_takes_gradients = True                     # speculative sweep: plain gather of h[targets]
             try:
                 # advances the (speculative) sweep; the module's forward is called directly when no hooks are registered
                 # (64 calls per step: nn.Module.__call__ costs as much as the level bookkeeping itself)
                 gnn = self.gnn
                 h_gnn = (gnn.forward if not (gnn._forward_hooks or gnn._forward_pre_hooks) else gnn)(graph, nodes, eids, target_list, level_id)
             finally:
-                graph.__dict__['_head_takes_gradients'] = False
+                graph._head_takes_gradients = False
             st = graph._sweep
             if st is not None and st.spec_token is not None and st.need_grad and not h_gnn.requires_grad:
-                hb = st.__dict__.get('head_batch')
+                hb = st.head_batch
                 if hb is None or hb.feat_map is not path_map.feat_map or hb.model is not self:
-                    hb = st.__dict__['head_batch'] = _HeadBatch(self, graph, st, path_map.feat_map, path_map.masks)
+                    hb = st.head_batch = _HeadBatch(self, graph, st, path_map.feat_map, path_map.masks)
                 slot = len(hb.grads)
                 hb.tix.append(st.spec_tix[-1])
                 hb.paths.append(path_map.paths)

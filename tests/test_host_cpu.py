@@ -105,6 +105,40 @@ def test_pingraph_csr_and_surface():
     assert g2.ndata['h'].shape == (10, 4)
 
 
+def test_pingraph_declares_the_sweep_state_and_does_not_carry_it_to_a_copy():
+    """Every per-graph field of the sweep and the deferred head exists, empty, on a fresh graph and on its .to() copy, and
+    the copy shares no container with the original - also after the original's were filled."""
+    empty = dict(_sweep=None, _sweep_bufs={}, _seen_lists=[], _spec_lists=None, _spec_disabled=False, _spec_stream=None,
+                 _cone_mask=None, _head_takes_gradients=False, _head_level_th=None, targets_unique=None)
+
+    def check(g):
+        for k, v in empty.items():
+            assert k in g.__dict__ and type(getattr(g, k)) is type(v) and getattr(g, k) == v, k
+
+    g = PinGraph(3, {'net': ((0, 1), (2, 2)), 'cell': ((), ())})
+    c = g.to('cpu')
+    for x in (g, c):
+        check(x)
+    assert c._sweep_bufs is not g._sweep_bufs and c._seen_lists is not g._seen_lists
+    g._sweep_bufs['key'] = (3, 4, 8, 'cpu')
+    g._seen_lists.append([0, 1])
+    g._spec_lists, g._spec_disabled, g._head_level_th, g.targets_unique = [[0, 1], [2]], True, [torch.zeros(1)], True
+    c2 = g.to('cpu')
+    for x in (c, c2):
+        check(x)
+    assert c2._sweep_bufs is not g._sweep_bufs and c2._seen_lists is not g._seen_lists
+    assert g._sweep_bufs == {'key': (3, 4, 8, 'cpu')} and g._seen_lists == [[0, 1]] and g._spec_disabled
+
+
+def test_sweep_state_refuses_undeclared_fields():
+    from mmft.sweep import SweepState
+    st = object.__new__(SweepState)
+    assert not hasattr(st, '__dict__') and set(SweepState.DECIDED) <= set(SweepState.__slots__)
+    st.hid16 = True
+    with pytest.raises(AttributeError):
+        st.hid_16 = True
+
+
 def test_batch_links_and_transposed_masks():
     first, nxt = batch_links([3, 1, 3, 0, 3, 1], 5)
     assert first.tolist() == [3, 1, -1, 0, -1] and nxt.tolist() == [2, 5, 4, -1, -1, -1]
