@@ -337,6 +337,11 @@ int mmft_bn_train_fwd(const float* x, float* y, const float* gamma, const float*
                       float* running_var, float momentum, float eps, int groups, long long rows, int C,
                       float* save_mean, float* save_invstd, int relu, float* workspace,
                       long long workspace_bytes, int device, void* stream);
+/* BatchNorm2d in EVAL mode + optional ReLU (src/Unet.py:16-21 after .eval()): y = (x - running_mean) / sqrt(running_var + eps)
+ * * gamma + beta over x [rows][C] (NHWC), one element-wise pass; nothing but y is written - the running statistics and the
+ * batch counter stay as they are. */
+int mmft_bn_eval_fwd(const float* x, float* y, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, long long rows, int C, int relu, int device, void* stream);
 /* g = gy * (y > 0 if relu); dgamma = sum g*xhat; dbeta = sum g;
  * dx = gamma*invstd*(g - mean(g) - xhat*mean(g*xhat)) with means per group.  With `beta` given the ReLU mask is
  * recomputed from x by the forward's own affine (same rounding sequence) and y may be NULL: 5 tensor passes, not 7 */
@@ -553,6 +558,15 @@ int mmft_u16_pack_weights(const void* descs, int n, long long max_frag_lanes, lo
 int mmft_u16_conv_tiles(int N, int H, int W, int* per_image);
 int mmft_u16_conv3x3(const void* x, int rgb_f32, const void* wpk, void* y, float* stats, int N, int H, int W, int Ci, int Co,
                      int device, void* stream);
+/* The same convolution followed by BatchNorm2d in EVAL mode and ReLU (src/Unet.py:16-21 after .eval()) in its epilogue:
+ * invstd = 1 / sqrtf(running_var + eps); scale = gamma * invstd; shift = fmaf(-running_mean, scale, beta);
+ * a = bf16(relu(fmaf(acc, scale, shift))) on the fp32 accumulator - the pre-activation is never stored and no statistic is
+ * taken or written.  wpk: the SAME mode-0 pack as mmft_u16_conv3x3 (BatchNorm is not folded into the weights).  a: pixel
+ * pitch lda >= Co elements (a channel slice of the concatenation of src/Unet.py:67); pooled != NULL: the 2x2 pooling of
+ * src/Unet.py:33-36 of the ROUNDED activations, [N][H/2][W/2][Co] (H, W even). */
+int mmft_u16_conv3x3_eval(const void* x, int rgb_f32, const void* wpk, const float* gamma, const float* beta, const float* running_mean,
+                          const float* running_var, float eps, void* a, int lda, void* pooled, int pool_mode, int N, int H, int W,
+                          int Ci, int Co, int device, void* stream);
 /* Weight gradients: every workgroup leaves one partial result (a SLAB) in `workspace`; with dw != NULL the call also adds
  * the slabs up (in a fixed order) into dw, with dw == NULL they stay in `workspace` and the caller reduces several layers'
  * slabs with ONE mmft_slab_reduce_batch launch (nothing needs a U-Net weight gradient before the optimizer).

@@ -9,8 +9,11 @@ ConvTranspose2d as GEMM + pixel shuffle).  Activations travel between ops as cha
 
 Reference behaviours kept on purpose:
   D3  forward accepts (C,H,W) as well as (N,C,H,W);
-  D5  BatchNorm always uses batch statistics (the reference never calls eval()); running stats are
-      still updated;
+  D5  in train mode - the default, and the only mode the reference's scripts ever use (they never call
+      eval()) - BatchNorm uses batch statistics and updates its running statistics.  eval() is honoured
+      exactly as nn.BatchNorm2d does (src/Unet.py:16-21): every layer normalises with running_mean /
+      running_var and neither they nor num_batches_tracked are written.  Eval mode is forward-only: with
+      grad mode on and anything requiring grad it raises NotImplementedError (use torch.no_grad());
   D10 one pooling module instance is shared by down1/2/3 and outc;
   D12 UNet(pooling, bilinear=True) cannot run in the reference either: up3 then has 16 // 2 = 8 output channels while
       OutConv is built for 16 (src/Unet.py:103-104,108) - "expected input ... to have 16 channels, but got 8".  The Up
@@ -164,11 +167,30 @@ class UNet(nn.Module):
         if x.dim() == 3:                       # train() feeds (C,H,W), validate()/test() (1,C,H,W): SURVEY D3
             x = x.unsqueeze(0)
         per_sample = self.inc.per_sample_stats
-        if _lib.get_math_mode() == 'bf16' and _u16.supported(self, x):
-            # bf16 math mode: the whole network as one autograd node on bf16-STORAGE kernels (mmft/unet16.py); the batch
-            # counters ride in its first launch
-            return _u16.unet_forward(self, x)
-        self._count_batches(x.shape[0] if per_sample else 1)
+        bns = self.__dict__.get('_bn_list')        # cached: walking the module tree on every call costs more than the checks
+        if bns is None:
+            bns = self.__dict__['_bn_list'] = [m for m in self.modules() if isinstance(m, nn.BatchNorm2d)]
+        frozen = [C.bn_uses_running_stats(bn) for bn in bns]
+        if any(frozen) and torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            raise NotImplementedError('UNet: ' + C.EVAL_GRAD_MSG)
+        bf16 = _lib.get_math_mode() == 'bf16'
+        if all(frozen):
+            # eval(): frozen statistics, nothing is counted or written.  bf16 math mode: convolutions with the BatchNorm
+            # affine in their epilogue (mmft/unet16.py); per_sample_stats has no meaning here
+            if bf16 and _u16.supported(self, x, frozen_stats=True):
+                return _u16.unet_forward_eval(self, x)
+        elif not any(frozen):
+            if bf16 and _u16.supported(self, x):
+                # bf16 math mode: the whole network as one autograd node on bf16-STORAGE kernels (mmft/unet16.py); the
+                # batch counters ride in its first launch
+                return _u16.unet_forward(self, x)
+            self._count_batches(x.shape[0] if per_sample else 1)
+        else:
+            # some layers in eval mode: the per-operator path decides layer by layer; only the train-mode layers count
+            self._batch_counters()
+            for bn, fz in zip(bns, frozen):
+                if not fz and bn.num_batches_tracked is not None:
+                    bn.num_batches_tracked += x.shape[0] if per_sample else 1
         x1 = self.inc(x)
         x2 = self.down1(x1)
         x3 = self.down2(x2)

@@ -233,6 +233,64 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const float* __restrict__
   }
 }
 
+// BatchNorm2d in EVAL mode (+ ReLU): the same affine with mean = running_mean, invstd = 1 / sqrt(running_var + eps) formed per
+// thread at entry; one pass, nothing is written but y.  As in bn_apply_kernel a thread keeps one channel group for the whole
+// launch whenever the grid stride is a multiple of C.
+template <int VEC>
+__global__ void __launch_bounds__(256) bn_eval_kernel(const float* __restrict__ x, float* __restrict__ y,
+                                                      const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                      const float* __restrict__ running_mean, const float* __restrict__ running_var,
+                                                      float eps, int C, long long total, int relu) {
+  const long long stride = (long long)gridDim.x * blockDim.x * VEC;
+  long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
+  auto invstd_of = [&](int c) { return __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(running_var[c], eps))); };
+  if (VEC == 4 && stride % C == 0) {
+    if (i >= total) return;
+    const int c = (int)(i % C);
+    float mu[4], is[4], ga[4], be[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      mu[j] = running_mean[c + j]; is[j] = invstd_of(c + j); ga[j] = gamma[c + j]; be[j] = beta[c + j];
+    }
+    for (; i + stride < total; i += 2 * stride) {                // two independent 16-byte streams per thread
+      f32x4 v0 = *reinterpret_cast<const f32x4*>(x + i), v1 = *reinterpret_cast<const f32x4*>(x + i + stride);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t0 = bn_affine(v0[j], mu[j], is[j], ga[j], be[j]), t1 = bn_affine(v1[j], mu[j], is[j], ga[j], be[j]);
+        v0[j] = (relu && !(t0 > 0.f)) ? 0.f : t0;
+        v1[j] = (relu && !(t1 > 0.f)) ? 0.f : t1;
+      }
+      *reinterpret_cast<f32x4*>(y + i) = v0;
+      *reinterpret_cast<f32x4*>(y + i + stride) = v1;
+    }
+    for (; i < total; i += stride) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t = bn_affine(v[j], mu[j], is[j], ga[j], be[j]);
+        v[j] = (relu && !(t > 0.f)) ? 0.f : t;
+      }
+      *reinterpret_cast<f32x4*>(y + i) = v;
+    }
+    return;
+  }
+  for (; i < total; i += stride) {
+    const int c = (int)(i % C);
+    if (VEC == 4) {
+      f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const float t = bn_affine(v[j], running_mean[c + j], invstd_of(c + j), gamma[c + j], beta[c + j]);
+        v[j] = (relu && !(t > 0.f)) ? 0.f : t;
+      }
+      *reinterpret_cast<f32x4*>(y + i) = v;
+    } else {
+      const float t = bn_affine(x[i], running_mean[c], invstd_of(c), gamma[c], beta[c]);
+      y[i] = (relu && !(t > 0.f)) ? 0.f : t;
+    }
+  }
+}
+
 // backward stage 1: partial sums of g and g*xhat (g = gy masked by the ReLU output)
 template <int VEC>
 __global__ void __launch_bounds__(256) bn_bwd_partial_kernel(const float* __restrict__ gy, const float* __restrict__ x,
@@ -735,6 +793,24 @@ int mmft_bn_train_fwd(const float* x, float* y, const float* gamma, const float*
     hipLaunchKernelGGL(bn_apply_kernel<1>, dim3(gx(rows * C), groups), dim3(256), 0, st, x, y, gamma, beta, save_mean,
                        save_invstd, rows, C, total, relu, run);
   return check_launch("bn_train_fwd");
+}
+
+int mmft_bn_eval_fwd(const float* x, float* y, const float* gamma, const float* beta, const float* running_mean,
+                     const float* running_var, float eps, long long rows, int C, int relu, int device, void* stream) {
+  MMFT_REQUIRE(x && y && gamma && beta && running_mean && running_var, "bn_eval_fwd: null pointer");
+  MMFT_REQUIRE(rows > 0 && C > 0 && C <= 256 && eps >= 0.f, "bn_eval_fwd: bad sizes (C <= 256 supported)");
+  DeviceGuard dg(device);
+  hipStream_t st = (hipStream_t)stream;
+  const long long total = rows * C;
+  const bool v4 = (C % 4 == 0) && aligned16(x) && aligned16(y);
+  auto gx = [&](long long items) { long long b = cdiv(items, 256 * 2); return (unsigned)(b < 1 ? 1 : b > 2048 ? 2048 : b); };
+  if (v4)
+    MMFT_LAUNCH("bn_eval_kernel", 0.0, 2.0 * 4.0 * total, bn_eval_kernel<4>, dim3(gx(total / 4)), dim3(256), st, x, y, gamma, beta,
+                running_mean, running_var, eps, C, total, relu);
+  else
+    MMFT_LAUNCH("bn_eval_kernel", 0.0, 2.0 * 4.0 * total, bn_eval_kernel<1>, dim3(gx(total)), dim3(256), st, x, y, gamma, beta,
+                running_mean, running_var, eps, C, total, relu);
+  return check_launch("bn_eval_fwd");
 }
 
 int mmft_bn_train_bwd(const float* gy, const float* x, const float* y, const float* gamma, const float* beta,

@@ -75,6 +75,15 @@ struct U16ConvArgs {
   float* stats;        // [tiles][2][CO] or null
   int N, H, W, CO;
   int tiles_x, tiles_y, tiles;
+  // EVAL epilogue only (BatchNorm2d in eval mode, src/Unet.py:16-21): y is the ACTIVATION buffer, pixel pitch lda
+  const float* gamma;  // [CO] BatchNorm weight
+  const float* beta;   // [CO] BatchNorm bias
+  const float* rmean;  // [CO] running_mean
+  const float* rvar;   // [CO] running_var
+  float eps;
+  int lda;
+  u16* pooled;         // bf16 [N][H/2][W/2][CO] or null
+  int pool_mode;
 };
 
 // Input channels >= 32: the 32-channel chunk is ONE v_mfma_f32_16x16x32_bf16 per tap (8 consecutive channels per lane = one
@@ -88,7 +97,13 @@ struct U16ConvCfg {
   static constexpr int LDS_BYTES = XS_BYTES + RED_BYTES;
 };
 
-template <int CI, int COB, int TH, int TW, bool RGB>
+// EVAL: the epilogue of a layer whose BatchNorm2d is in eval mode (src/Unet.py:16-21 after .eval()) - the per-channel affine
+// of the RUNNING statistics and the ReLU are applied to the fp32 accumulator, the activation is rounded once and stored with
+// pixel pitch lda, and the 2x2 pooling of the following Down block (src/Unet.py:33-36) is taken of the rounded values in
+// registers.  Nothing is reduced and the pre-activation never reaches HBM.  The strips are dealt so that a wave owns FOUR
+// CONSECUTIVE ROWS of one 16-pixel column block in both tile shapes: a window's vertical pair is then two registers of one
+// lane and its horizontal pair the lanes r, r ^ 1.  (A pixel's summation order does not depend on which wave owns it.)
+template <int CI, int COB, int TH, int TW, bool RGB, bool EVAL = false>
 __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
   using C = U16ConvCfg<CI, TH, TW>;
   constexpr int XR = C::XR, XC = C::XC, PIX = C::PIX, MB = COB / 16;
@@ -96,6 +111,7 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
   constexpr int KC = K32 ? 32 : 16, NCH = CI / KC;
   constexpr int STEPS = TH * TW / 16, SPR = TW / 16, SPW = STEPS / 4;
   static_assert(TW % 16 == 0 && CI % 16 == 0 && COB % 16 == 0 && STEPS % 4 == 0 && (!RGB || CI == 16), "granularity");
+  static_assert(!EVAL || (SPR <= 4 && (4 / SPR) * SPW == TH && SPW % 2 == 0), "eval epilogue: a wave owns SPW consecutive rows");
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   u16* xs = reinterpret_cast<u16*>(smem);                                   // [XR][XC][PIX]
   float* red = reinterpret_cast<float*>(smem + C::XS_BYTES);               // [4 waves][2][32]
@@ -103,6 +119,17 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
   const int r = lane & 15, q = lane >> 4;
   const int mb0 = blockIdx.y * MB, co0 = mb0 * 16;
   const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  // strip s of this wave: tile row and first column
+  auto strip = [&](int s, int& row, int& c0) {
+    if constexpr (EVAL) {
+      row = (wave / SPR) * SPW + s;
+      c0 = (wave % SPR) * 16;
+    } else {
+      const int st = wave + 4 * s;
+      row = st / SPR;
+      c0 = (st % SPR) * 16;
+    }
+  };
 
   // fragments of chunk ch: [(mb0 + m)][t][ch][lane][KC / 4 elements]
   typedef typename std::conditional<K32, u16_bf16x8, s16x4>::type wfrag_t;
@@ -163,6 +190,20 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
     }
   };
 
+  // EVAL: scale / shift of this lane's 4 MB channels, formed once in fp32 with a fixed rounding sequence
+  float sc[EVAL ? MB : 1][4], sh[EVAL ? MB : 1][4];
+  if constexpr (EVAL) {
+#pragma unroll
+    for (int m = 0; m < MB; ++m)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int c = co0 + m * 16 + 4 * q + j;
+        const float invstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(a.rvar[c], a.eps)));
+        sc[m][j] = __fmul_rn(a.gamma[c], invstd);
+        sh[m][j] = __fmaf_rn(-a.rmean[c], sc[m][j], a.beta[c]);
+      }
+  }
+
   if ((int)blockIdx.x < a.tiles) request(blockIdx.x);
   for (int tile = blockIdx.x; tile < a.tiles; tile += gridDim.x) {
     deposit();
@@ -180,7 +221,8 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
       if constexpr (NCH > 1) load_weights(ch);
 #pragma unroll
       for (int s = 0; s < SPW; ++s) {
-        const int st = wave + 4 * s, row = st / SPR, c0 = (st % SPR) * 16;
+        int row, c0;
+        strip(s, row, c0);
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky)
 #pragma unroll
@@ -200,6 +242,63 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
       }
     }
     // acc[s][m] at lane (pixel r, q) = output channels co0 + 16 m + 4 q .. + 3 of pixel (y0 + row, x0 + c0 + r)
+    if constexpr (EVAL) {
+      u32x2 pk[SPW][MB];                       // the stored (rounded) activations: what the pooling sees
+#pragma unroll
+      for (int s = 0; s < SPW; ++s) {
+        int row, c0;
+        strip(s, row, c0);
+        const int yy = y0 + row, xx = x0 + c0 + r;
+        const bool valid = yy < a.H && xx < a.W;
+        u16* out = a.y + (((long long)img * a.H + yy) * a.W + xx) * a.lda + co0;
+#pragma unroll
+        for (int m = 0; m < MB; ++m) {
+          float v[4];
+#pragma unroll
+          for (int j = 0; j < 4; ++j) {
+            const float t = bn_pre(acc[s][m][j], sc[m][j], sh[m][j]);
+            v[j] = t > 0.f ? t : 0.f;
+          }
+          const s16x4 p4 = pack_bf16x4(v[0], v[1], v[2], v[3]);
+          if (valid) *reinterpret_cast<s16x4*>(out + m * 16 + 4 * q) = p4;
+          pk[s][m] = as_u32x2(p4);
+        }
+      }
+      if (a.pooled) {                          // H, W even: a window is valid or masked as a whole
+        const int H2 = a.H / 2, W2 = a.W / 2;
+        int row0, c0;
+        strip(0, row0, c0);
+        const int xx = x0 + c0 + r;
+#pragma unroll
+        for (int s = 0; s < SPW; s += 2) {
+          const int yy = y0 + row0 + s;
+          const bool store = (r & 1) == 0 && yy < a.H && xx < a.W;
+          u16* out = a.pooled + (((long long)img * H2 + yy / 2) * W2 + xx / 2) * a.CO + co0;
+#pragma unroll
+          for (int m = 0; m < MB; ++m) {
+            u32x2 nb0, nb1;                    // the same rows of the horizontal neighbour (lane r ^ 1)
+#pragma unroll
+            for (int i = 0; i < 2; ++i) {
+              nb0[i] = __shfl_xor(pk[s][m][i], 1, 64);
+              nb1[i] = __shfl_xor(pk[s + 1][m][i], 1, 64);
+            }
+            float f00[4], f01[4], f10[4], f11[4], o[4];
+            unpack4(pk[s][m], f00);
+            unpack4(nb0, f01);
+            unpack4(pk[s + 1][m], f10);
+            unpack4(nb1, f11);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+              if (a.pool_mode == MMFT_POOL_MAX) o[j] = fmaxf(fmaxf(f00[j], f01[j]), fmaxf(f10[j], f11[j]));   // >= 0, no NaN: a selection
+              else o[j] = (((f00[j] + f01[j]) + f10[j]) + f11[j]) * 0.25f;
+            }
+            if (store) *reinterpret_cast<s16x4*>(out + m * 16 + 4 * q) = pack_bf16x4(o[0], o[1], o[2], o[3]);
+          }
+        }
+      }
+      __syncthreads();
+      continue;
+    }
     float sm[MB][4], sq[MB][4];
 #pragma unroll
     for (int m = 0; m < MB; ++m)
@@ -207,7 +306,8 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
       for (int j = 0; j < 4; ++j) sm[m][j] = sq[m][j] = 0.f;
 #pragma unroll
     for (int s = 0; s < SPW; ++s) {
-      const int st = wave + 4 * s, row = st / SPR, c0 = (st % SPR) * 16;
+      int row, c0;
+      strip(s, row, c0);
       const int yy = y0 + row, xx = x0 + c0 + r;
       const bool valid = yy < a.H && xx < a.W;
       u16* out = a.y + (((long long)img * a.H + yy) * a.W + xx) * a.CO + co0;
@@ -433,17 +533,47 @@ static inline void u16_tile_shape(int W, int* th, int* tw) {
   *th = 256 / *tw;
 }
 
-template <int CI, int COB, int TH, int TW, bool RGB>
+template <int CI, int COB, int TH, int TW, bool RGB, bool EVAL = false>
 static int u16_conv_launch_t(const U16ConvArgs& a, int grid_x, hipStream_t st, double flops, double bytes) {
   using C = U16ConvCfg<CI, TH, TW>;
   static DynLdsOnce once;
-  int rc = ensure_dyn_lds(once, reinterpret_cast<const void*>(&u16_conv3x3_kernel<CI, COB, TH, TW, RGB>), C::LDS_BYTES, "u16_conv3x3");
+  int rc = ensure_dyn_lds(once, reinterpret_cast<const void*>(&u16_conv3x3_kernel<CI, COB, TH, TW, RGB, EVAL>), C::LDS_BYTES, "u16_conv3x3");
   if (rc) return rc;
   static char name[64];                                  // per instantiation; written with the same bytes by every caller
-  if (!name[0]) snprintf(name, sizeof(name), "u16_conv3x3_kernel<%d,%d,%dx%d%s>", RGB ? 3 : CI, COB, TH, TW, a.stats ? "" : "");
-  MMFT_LAUNCH_LDS(name, flops, bytes, (u16_conv3x3_kernel<CI, COB, TH, TW, RGB>), dim3(grid_x, a.CO / COB), dim3(256),
+  if (!name[0])
+    snprintf(name, sizeof(name), EVAL ? "u16_conv3x3_eval_kernel<%d,%d,%dx%d%s>" : "u16_conv3x3_kernel<%d,%d,%dx%d%s>", RGB ? 3 : CI, COB,
+             TH, TW, a.stats ? "" : "");
+  MMFT_LAUNCH_LDS(name, flops, bytes, (u16_conv3x3_kernel<CI, COB, TH, TW, RGB, EVAL>), dim3(grid_x, a.CO / COB), dim3(256),
                   C::LDS_BYTES, st, a);
-  return check_launch("u16_conv3x3");
+  return check_launch(EVAL ? "u16_conv3x3_eval" : "u16_conv3x3");
+}
+
+// tile shape, workgroup grid and kernel instantiation of one forward-type launch (shared by the train and eval entry points)
+template <bool EVAL>
+static int u16_conv_dispatch(U16ConvArgs& a, int rgb_f32, int Ci, hipStream_t st, double flops, double bytes) {
+  int th, tw;
+  u16_tile_shape(a.W, &th, &tw);
+  a.tiles_x = (a.W + tw - 1) / tw;
+  a.tiles_y = (a.H + th - 1) / th;
+  a.tiles = a.N * a.tiles_x * a.tiles_y;
+  const int cob = a.CO % 32 == 0 ? 32 : 16, gy = a.CO / cob;
+  int cap = 2048 / gy;
+  const int gx = a.tiles < cap ? a.tiles : cap;
+#define U16_CONV(CIV, COBV, RGBV)                                                                           \
+  (tw == 64 ? u16_conv_launch_t<CIV, COBV, 4, 64, RGBV, EVAL>(a, gx, st, flops, bytes)                      \
+            : u16_conv_launch_t<CIV, COBV, 8, 32, RGBV, EVAL>(a, gx, st, flops, bytes))
+  if (rgb_f32) return U16_CONV(16, 16, true);
+  if (cob == 16) {
+    if (Ci == 16) return U16_CONV(16, 16, false);
+    if (Ci == 32) return U16_CONV(32, 16, false);
+    if (Ci == 64) return U16_CONV(64, 16, false);
+    return U16_CONV(128, 16, false);
+  }
+  if (Ci == 16) return U16_CONV(16, 32, false);
+  if (Ci == 32) return U16_CONV(32, 32, false);
+  if (Ci == 64) return U16_CONV(64, 32, false);
+  return U16_CONV(128, 32, false);
+#undef U16_CONV
 }
 
 template <int CIB, int COB, int TH, int TW, bool RGB>
@@ -505,31 +635,36 @@ int mmft_u16_conv3x3(const void* x, int rgb_f32, const void* wpk, void* y, float
                "u16_conv3x3: channels must be 16 / 32 / 64 / 128 (or the 3 -> 16 RGB layer)");
   MMFT_REQUIRE(aligned16(x) && aligned16(wpk) && aligned16(y), "u16_conv3x3: 16-byte alignment");
   DeviceGuard dg(device);
-  hipStream_t st = (hipStream_t)stream;
-  int th, tw;
-  u16_tile_shape(W, &th, &tw);
-  U16ConvArgs a{x, reinterpret_cast<const u16*>(wpk), reinterpret_cast<u16*>(y), stats, N, H, W, Co, (W + tw - 1) / tw, (H + th - 1) / th, 0};
-  a.tiles = N * a.tiles_x * a.tiles_y;
-  const int cob = Co % 32 == 0 ? 32 : 16, gy = Co / cob;
-  int cap = 2048 / gy;
-  const int gx = a.tiles < cap ? a.tiles : cap;
+  U16ConvArgs a{x, reinterpret_cast<const u16*>(wpk), reinterpret_cast<u16*>(y), stats, N, H, W, Co};
   const double flops = 2.0 * N * H * W * Co * 9.0 * Ci;
   const double bytes = (rgb_f32 ? 4.0 : 2.0) * N * H * W * Ci + 2.0 * N * H * W * Co + 2.0 * Co * 9 * Ci;
-#define U16_CONV(CIV, COBV, RGBV)                                                                           \
-  (tw == 64 ? u16_conv_launch_t<CIV, COBV, 4, 64, RGBV>(a, gx, st, flops, bytes)                            \
-            : u16_conv_launch_t<CIV, COBV, 8, 32, RGBV>(a, gx, st, flops, bytes))
-  if (rgb_f32) return U16_CONV(16, 16, true);
-  if (cob == 16) {
-    if (Ci == 16) return U16_CONV(16, 16, false);
-    if (Ci == 32) return U16_CONV(32, 16, false);
-    if (Ci == 64) return U16_CONV(64, 16, false);
-    return U16_CONV(128, 16, false);
-  }
-  if (Ci == 16) return U16_CONV(16, 32, false);
-  if (Ci == 32) return U16_CONV(32, 32, false);
-  if (Ci == 64) return U16_CONV(64, 32, false);
-  return U16_CONV(128, 32, false);
-#undef U16_CONV
+  return u16_conv_dispatch<false>(a, rgb_f32, Ci, (hipStream_t)stream, flops, bytes);
+}
+
+int mmft_u16_conv3x3_eval(const void* x, int rgb_f32, const void* wpk, const float* gamma, const float* beta, const float* running_mean,
+                          const float* running_var, float eps, void* a, int lda, void* pooled, int pool_mode, int N, int H, int W,
+                          int Ci, int Co, int device, void* stream) {
+  MMFT_REQUIRE(x && wpk && a && gamma && beta && running_mean && running_var && N > 0 && H > 0 && W > 0 && eps >= 0.f,
+               "u16_conv3x3_eval: bad arguments");
+  MMFT_REQUIRE(u16_channels_ok(Co) && (rgb_f32 ? (Ci == 3 && Co == 16) : u16_channels_ok(Ci)),
+               "u16_conv3x3_eval: channels must be 16 / 32 / 64 / 128 (or the 3 -> 16 RGB layer)");
+  MMFT_REQUIRE(lda >= Co && lda % 8 == 0, "u16_conv3x3_eval: the pixel pitch must hold Co channels and be a multiple of 8");
+  MMFT_REQUIRE(!pooled || (H % 2 == 0 && W % 2 == 0 && (pool_mode == MMFT_POOL_MAX || pool_mode == MMFT_POOL_AVG)),
+               "u16_conv3x3_eval: pooling needs even H, W and a pooling mode");
+  MMFT_REQUIRE(aligned16(x) && aligned16(wpk) && aligned16(a) && (!pooled || aligned16(pooled)), "u16_conv3x3_eval: 16-byte alignment");
+  DeviceGuard dg(device);
+  U16ConvArgs p{x, reinterpret_cast<const u16*>(wpk), reinterpret_cast<u16*>(a), nullptr, N, H, W, Co};
+  p.gamma = gamma;
+  p.beta = beta;
+  p.rmean = running_mean;
+  p.rvar = running_var;
+  p.eps = eps;
+  p.lda = lda;
+  p.pooled = reinterpret_cast<u16*>(pooled);
+  p.pool_mode = pool_mode;
+  const double flops = 2.0 * N * H * W * Co * 9.0 * Ci;
+  const double bytes = (rgb_f32 ? 4.0 : 2.0) * N * H * W * Ci + 2.0 * N * H * W * Co * (pooled ? 1.25 : 1.0) + 2.0 * Co * 9 * Ci;
+  return u16_conv_dispatch<true>(p, rgb_f32, Ci, (hipStream_t)stream, flops, bytes);
 }
 
 long long mmft_u16_conv3x3_wgrad_workspace_bytes(int N, int H, int W, int Ci, int Co) {

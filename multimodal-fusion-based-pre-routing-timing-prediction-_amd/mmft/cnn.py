@@ -75,8 +75,25 @@ class BnReluFn(torch.autograd.Function):
         return dx, dgamma, dbeta, None, None, None, None, None, None
 
 
+EVAL_GRAD_MSG = ('BatchNorm2d in eval mode is a forward-only path here (no backward through frozen statistics): '
+                 'call it under torch.no_grad(), or put the module back in train() mode')
+
+
+def bn_uses_running_stats(bn):
+    """nn.BatchNorm2d's own rule: eval mode AND tracked running statistics -> normalise with them, write nothing."""
+    return not bn.training and bn.track_running_stats and bn.running_mean is not None
+
+
 def bn_relu(x, bn, relu=True, per_sample=False, count=True):
-    """`bn` is an nn.BatchNorm2d holding the parameters/buffers; always batch statistics."""
+    """`bn` is an nn.BatchNorm2d holding the parameters/buffers.  In train mode (the reference scripts' only mode, SURVEY
+    D5): batch statistics, running statistics updated.  In eval mode: the running statistics, nothing written,
+    `per_sample` / `count` without meaning (src/Unet.py:16-21 after .eval())."""
+    if bn_uses_running_stats(bn):
+        if not bn.affine:
+            raise NotImplementedError('BatchNorm2d without affine is not on the reference path')
+        if torch.is_grad_enabled() and (x.requires_grad or bn.weight.requires_grad or bn.bias.requires_grad):
+            raise NotImplementedError(EVAL_GRAD_MSG)
+        return ops.bn_eval_fwd(ops.to_nhwc(x), bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, bn.eps, relu)
     if bn.momentum is None or not bn.affine:
         raise NotImplementedError('BatchNorm2d without momentum/affine is not on the reference path')
     if count and bn.track_running_stats and bn.num_batches_tracked is not None:

@@ -2,14 +2,34 @@
 with every metric the reference prints derived from ONE fp64 sums kernel and one device->host copy, instead of
 the reference's seven `.item()` syncs per batch (src/train.py:525-541).
 
-As in the reference, modules stay in train mode (BatchNorm uses batch statistics and updates its running stats:
-SURVEY D5) and the whole design is evaluated as one batch over all of its paths (src/train.py:188, src/test.py:176).
+As in the reference, modules stay in train mode by default (BatchNorm uses batch statistics and updates its running
+stats: SURVEY D5) and the whole design is evaluated as one batch over all of its paths (src/train.py:188,
+src/test.py:176).  `frozen_stats=True` is the inference variant the reference's scripts do not have: the CNN is put in
+eval mode for the call, so BatchNorm normalises with its running statistics and the model is left untouched.
 `endpoint_slack_mae` = mean |(required - y_hat) - (required - arrival)| = mean |y_hat - arrival| is the accuracy
 metric BASELINE.json names.
 """
+import contextlib
+
 import numpy as np
 import torch
 from . import lib, ops
+
+
+@contextlib.contextmanager
+def frozen_statistics(cnn, on=True):
+    """with frozen_statistics(cnn): ...  - the CNN in eval mode (BatchNorm from its running statistics, nothing written),
+    every module back in the mode it was in afterwards, also when the body raises."""
+    if not on or cnn is None:
+        yield cnn
+        return
+    modes = [(m, m.training) for m in cnn.modules()]
+    cnn.eval()
+    try:
+        yield cnn
+    finally:
+        for m, was in modes:
+            m.training = was
 
 
 def eval_sums(pred, arrival, required, label):
@@ -61,15 +81,18 @@ def level_metrics_from_sums(rows):
 
 
 @torch.no_grad()
-def validate(train_step, path_ids_per_design=None, per_level=False):
+def validate(train_step, path_ids_per_design=None, per_level=False, frozen_stats=False):
     """Forward over all (or the given) paths of the designs held by `train_step` (a mmft.train.TrainStep) and
     return the metric dict; per_level=True adds 'levels': R2 / MAPE of every topological level (src/test.py:211-216).
-    One device->host copy."""
+    One device->host copy.  frozen_stats=False (default) is the reference's behaviour: the modules stay in train mode
+    (SURVEY D5).  frozen_stats=True: the CNN runs in eval mode for this call (running statistics, no buffer written) and is
+    returned to the mode it was in."""
     b = train_step.batch
     if path_ids_per_design is None:
         path_ids_per_design = [np.arange(d.num_paths) for d in b.designs]
     sel = b.select(path_ids_per_design)
-    hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
+    with frozen_statistics(train_step.cnn, frozen_stats):
+        hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
     idx = ends_d.long()
     arrival = b.arrival[idx].squeeze(-1).contiguous()
     required = b.required[idx].squeeze(-1).contiguous()
@@ -94,16 +117,24 @@ def validate(train_step, path_ids_per_design=None, per_level=False):
     return m
 
 
-def validate_designs(pmodel, cnn, designs, device, per_level=True, mode='sweep'):
+def validate_designs(pmodel, cnn, designs, device, per_level=True, mode='sweep', frozen_stats=False):
     """The per-design loop of validate() / test() (src/train.py:137-291, src/test.py:124-318): every design is evaluated
-    on its own as ONE batch over all of its paths (modules stay in train mode), the reference's per-case line
+    on its own as ONE batch over all of its paths (modules stay in train mode, SURVEY D5, unless frozen_stats=True puts
+    the CNN in eval mode for each call), the reference's per-case line
     (loss, r2, acc, recall, precision, F1 + per-level R2 / MAPE) is returned per design together with the averages over
     the designs that the loops print at the end (src/train.py:280-290)."""
     from .train import TrainStep
     cases = []
-    for d in designs:
-        ts = TrainStep(pmodel, cnn, [d], device, mode=mode, overlap=False, with_optimizer=False)
-        cases.append(validate(ts, per_level=per_level))
+    # (TrainStep puts the modules in train mode, as the reference's loops have them; with frozen_stats the CNN is handed
+    # back in the mode it came in, also on an exception)
+    modes = [(m, m.training) for m in cnn.modules()] if (frozen_stats and cnn is not None) else []
+    try:
+        for d in designs:
+            ts = TrainStep(pmodel, cnn, [d], device, mode=mode, overlap=False, with_optimizer=False)
+            cases.append(validate(ts, per_level=per_level, frozen_stats=frozen_stats))
+    finally:
+        for m, was in modes:
+            m.training = was
     keys = ('loss', 'r2', 'acc', 'recall', 'precision', 'f1', 'endpoint_slack_mae', 'mape')
     overall = {k: float(np.mean([c[k] for c in cases])) for k in keys} if cases else {}
     return dict(cases=cases, overall=overall)

@@ -867,6 +867,20 @@ def bn_train_fwd(x, gamma, beta, running_mean, running_var, momentum, eps, relu,
     return y, mean, invstd
 
 
+def bn_eval_fwd(x, gamma, beta, running_mean, running_var, eps, relu):
+    """BatchNorm2d in eval mode (+ ReLU) from the running statistics (src/Unet.py:16-21 after .eval()); writes only y."""
+    _nhwc(x, 'x')
+    N, C, H, W = x.shape
+    for t, nm in ((gamma, 'gamma'), (beta, 'beta'), (running_mean, 'running_mean'), (running_var, 'running_var')):
+        _chk(t, nm)
+        if t.numel() != C or not t.is_contiguous():
+            raise ValueError(f'bn: {nm} shape')
+    y = empty_nhwc(N, C, H, W, x.device)
+    dev, st = lib.stream_args(x)
+    lib.call('mmft_bn_eval_fwd', x, y, gamma, beta, running_mean, running_var, float(eps), N * H * W, C, int(relu), dev, st)
+    return y
+
+
 def bn_train_bwd(gy, x, y, gamma, mean, invstd, relu, dgamma=None, dbeta=None, beta=None):
     _nhwc(gy, 'gy'); _nhwc(x, 'x')
     N, C, H, W = x.shape

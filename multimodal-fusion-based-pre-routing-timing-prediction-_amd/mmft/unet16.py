@@ -27,12 +27,13 @@ from . import gradsink, lib, ops
 ENABLED = True          # False: UNet.forward keeps the per-operator fp32-storage path in bf16 mode as well (comparison runs)
 
 
-def supported(net, x):
+def supported(net, x, frozen_stats=False):
     """The fused path covers the reference's own configuration: UNet(pooling, bilinear=False) on an fp32 (N,3,H,W) batch
-    whose sides survive three 2x2 poolings and the OutConv kernel's 32-pixel row segments."""
+    whose sides survive three 2x2 poolings and the OutConv kernel's 32-pixel row segments.  frozen_stats: the eval-mode
+    forward, in which no statistic couples the images of a batch."""
     if not ENABLED or net.bilinear or x.dim() != 4 or x.shape[1] != 3 or x.dtype != torch.float32 or not x.is_cuda:
         return False
-    if x.shape[0] > 1 and not net.inc.per_sample_stats:
+    if x.shape[0] > 1 and not net.inc.per_sample_stats and not frozen_stats:
         return False                    # batch statistics over several images: the fp32 operators handle that
     H, W = x.shape[2], x.shape[3]
     return H % 8 == 0 and W % 32 == 0 and H >= 8
@@ -284,6 +285,60 @@ def _run_forward(net, xn, pool_mode, packs, T, F, out, geom):
     oc = net.outc.conv[0]
     lib.call('mmft_u16_outconv_fwd', T['a14'], oc.weight.detach(), oc.bias.detach() if oc.bias is not None else None, out, N, H, W,
              pool_mode, dev, st)
+
+
+@functools.lru_cache(maxsize=16)
+def _eval_sizes(N, H, W):
+    """Arena of the eval-mode forward: activations only - no pre-activations, statistics or BatchNorm coefficients."""
+    return [(name, n) for name, n in _fwd_sizes(N, H, W)[0] if not name.startswith('z')]
+
+
+def _run_forward_eval(net, xn, pool_mode, packs, T, out, geom):
+    """Every launch of UNet.forward (src/Unet.py:110-119) with all BatchNorm layers in eval mode (src/Unet.py:16-21 after
+    .eval()): the weight pack, 14 convolutions with the frozen affine + ReLU (+ pooling) in their epilogue, the 3 transposed
+    convolutions and OutConv - 19 launches, no host synchronisation, nothing written but T and out."""
+    N, H, W = geom
+    dev, st = lib.stream_args(out)
+    lv, _ = _geometry(N, H, W)
+    convs = _layers(net)
+    ups = [net.up1.up, net.up2.up, net.up3.up]
+    packs.refresh(net)                                   # no counters: num_batches_tracked stays as it is
+    for i in range(1, 15):
+        Ci, Co, l, inp = _CONV[i]
+        h, w = lv[l]
+        _, bn = convs[i - 1]
+        abuf_name, lda, pooled = _ACT[i]
+        lib.call('mmft_u16_conv3x3_eval', xn if inp == 'x' else T[inp], 1 if inp == 'x' else 0, packs.ptr('f%d' % (i - 1)),
+                 bn.weight.detach(), bn.bias.detach(), bn.running_mean, bn.running_var, float(bn.eps), T[abuf_name], lda,
+                 T[pooled] if pooled else None, pool_mode, N, h, w, Ci, Co, dev, st)
+        for k, (uCi, uin, cat, coff, ul) in _UP.items():
+            if uin == abuf_name:                        # the Up block's transposed convolution follows this layer
+                up = ups[k]
+                uh, uw = lv[ul]
+                lib.call('mmft_u16_convt_fwd', T[uin], packs.ptr('tf%d' % k), up.bias.detach() if up.bias is not None else None,
+                         T[cat].data_ptr() + coff * 2, 2 * (uCi // 2), N, uh, uw, uCi, dev, st)
+    oc = net.outc.conv[0]
+    lib.call('mmft_u16_outconv_fwd', T['a14'], oc.weight.detach(), oc.bias.detach() if oc.bias is not None else None, out, N, H, W,
+             pool_mode, dev, st)
+
+
+def unet_forward_eval(net, x):
+    """UNet.forward in eval mode on the bf16-storage kernels; x: fp32 (N,3,H,W).  Forward only: no autograd node, no replay
+    bookkeeping - the launch sequence has no host decision that depends on data, so a caller may capture it
+    (torch.cuda.graph) after one eager call has built the weight-pack table."""
+    N, _, H, W = x.shape
+    if not all(bn.affine for _, bn in _layers(net)):
+        raise NotImplementedError('unet16: BatchNorm2d without affine is not on the reference path')
+    pooling = net.down1.maxpool_conv[0]
+    pool_mode = ops.POOL_MAX if isinstance(pooling, nn.MaxPool2d) else ops.POOL_AVG
+    packs = net.__dict__.get('_u16_packs')
+    if packs is None or packs.device != x.device:
+        packs = net.__dict__['_u16_packs'] = _Packs(net, x.device)
+    xn = ops.to_nhwc(x.detach())                        # fp32 [N][H][W][3]
+    _abuf, T = _arena(_eval_sizes(N, H, W), torch.bfloat16, x.device)
+    out = torch.empty((N, 1, H // 2, W // 2), dtype=torch.float32, device=x.device)
+    _run_forward_eval(net, xn, pool_mode, packs, T, out, (N, H, W))
+    return out
 
 
 def _make_sinks(net):
