@@ -151,6 +151,19 @@ int mmft_level_fwd_slots(float* h, const float* pre, long long ld, int D, const 
                          int n_net, int cell_row0, int n_cell, float* A, float* LSE, const void* w1_bf16, const float* b1,
                          const void* w2_bf16, const float* b2, float* hid_out, long long ldhid, int relu,
                          const unsigned char* active, long long alg_bytes, int hid_bf16, int device, void* stream);
+/* Forward-only forms of the two level launches above (inference: no reverse sweep follows).  h receives bit for bit what the
+ * training forms write - same gather order, same softmax accumulation, same MFMA tiles, same epilogues, same `active` handling and
+ * the same choice of row blocks - but A, LSE and the hidden rows are neither stored nor have an address here, and the log of
+ * LSE is not evaluated.  alg_bytes: the training value minus 8 D + the hidden row per cell row. */
+int mmft_level_fwd_bf16_infer(float* h, const float* pre, long long ld, int D, const int* in_net_indptr, const int* in_net_indices,
+                              const int* in_cell_indptr, const int* in_cell_indices, int net_row0, int n_net, const int* cell_rows,
+                              int cell_row0, int n_cell, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2,
+                              int relu, const unsigned char* active, const int* in_cell_driver, long long alg_bytes, int device,
+                              void* stream);
+int mmft_level_fwd_slots_infer(float* h, const float* pre, long long ld, int D, const int* slots, const int* net_driver,
+                               int net_row0, int n_net, int cell_row0, int n_cell, const void* w1_bf16, const float* b1,
+                               const void* w2_bf16, const float* b2, int relu, const unsigned char* active, long long alg_bytes,
+                               int device, void* stream);
 /* Reverse sweep of one (cell level l, net level l + 1) pair in ONE launch (three before: mmft_level_bwd_pull on each level and
  * mmft_mlp2_rows_bf16 in its reverse form) - the autograd mirror of graph.pull + the cell MLP, src/model.py:100-117,138-146,186-187:
  *   net rows w (sinks):   G[w] = relu'(h[w]) ((own[w] ? G[w] : 0) + sum_c DA[c] exp(h[w] - LSE[c]) (1 + h[w] - A[c]))

@@ -14,6 +14,7 @@
 //   * 8 waves per 32-row tile: wave w owns hidden columns [32w, 32w + 32) and output columns [16w, 16w + 16).
 // The reverse form (weights_kmajor in the fp32 kernel) is the same kernel fed with the transposed packs.
 #include <stdlib.h>
+#include <type_traits>
 #include "mlp_tile_bf16.h"
 #include "fold_gather.h"
 
@@ -146,9 +147,32 @@ struct LevelFwdArgs {
   int cell_tiles;
 };
 
+// Forward-only form (KEEP = false, mmft_level_fwd_bf16_infer): nothing of the cell rows is kept for a reverse sweep, so A, LSE
+// and the hidden rows have no address here
+struct LevelFwdInferArgs {
+  float* h;
+  const float* pre;
+  long long ld;
+  const int *in_ptr, *in_idx, *ic_ptr, *ic_idx, *ic_drv;
+  int net_row0, n_net;
+  const int* rows;
+  int cell_row0, n_cell;
+  const unsigned short *w1, *w2;
+  const float *b1, *b2;
+  int relu;
+  const unsigned char* active;
+  int cell_tiles;
+};
+
+template <bool KEEP>
+using LevelFwdArgsOf = typename std::conditional<KEEP, LevelFwdArgs, LevelFwdInferArgs>::type;
+
 // 16 rows per tile: one gather item per thread and twice as many workgroups as the 32-row tile of mlp2_rows_bf16_kernel -
-// the gather, not the MLP, sets the duration of a level, and it wants the memory-level parallelism
-__global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
+// the gather, not the MLP, sets the duration of a level, and it wants the memory-level parallelism.
+// KEEP = false: h alone is the result - no store of A / LSE / the hidden rows and no log for LSE; every instruction that
+// decides a value of h is the one of KEEP = true (the bf16 tile of A still goes to LDS: it is the MLP's input).
+template <bool KEEP>
+__global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgsOf<KEEP> a) {
   constexpr int BM = 16;
   __shared__ __attribute__((aligned(16))) unsigned short xs[BM * L2_XS];
   __shared__ __attribute__((aligned(16))) unsigned short hs[BM * L2_HS];
@@ -187,16 +211,18 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
       SoftAccT<true> sa;
       sa.init();
       fold_gather_edges(fs, e0, e1, 1, c, sa);
-      f32x4 lv = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] f32x4 lv = {0.f, 0.f, 0.f, 0.f};
       if (e1 > e0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           av[j] = sa.acc[j] / sa.s[j];
-          lv[j] = sa.mx[j] + fg_log<true>(sa.s[j]);
+          if constexpr (KEEP) lv[j] = sa.mx[j] + fg_log<true>(sa.s[j]);
         }
       }
-      *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + c) = av;
-      *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + c) = lv;
+      if constexpr (KEEP) {
+        *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + c) = av;
+        *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + c) = lv;
+      }
     }
     st_bf16x4(xs + r * L2_XS + c, av);
   }
@@ -214,7 +240,9 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs a) {
     if (a.b1) v += *reinterpret_cast<const f32x4*>(a.b1 + nn);
     v = relu4(v);
     st_bf16x4(hs + r16 * L2_HS + nn, v);
-    if (a.hid_out && live_row(r16)) hid_store4(a.hid_out, (long long)row_of(r16) * a.ldhid + nn, v, a.hid16);
+    if constexpr (KEEP) {
+      if (a.hid_out && live_row(r16)) hid_store4(a.hid_out, (long long)row_of(r16) * a.ldhid + nn, v, a.hid16);
+    }
   }
   __syncthreads();
   if (!live_row(r16)) return;
@@ -257,8 +285,26 @@ struct LevelSlotsArgs {
   int cell_tiles;
 };
 
-template <int RB>
-__global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) {
+// Forward-only form (KEEP = false, mmft_level_fwd_slots_infer), as LevelFwdInferArgs
+struct LevelSlotsInferArgs {
+  float* h;
+  const float* pre;
+  long long ld;
+  const int* slots;
+  const int* net_drv;
+  int net_row0, n_net, cell_row0, n_cell;
+  const unsigned short *w1, *w2;
+  const float *b1, *b2;
+  int relu;
+  const unsigned char* active;
+  int cell_tiles;
+};
+
+template <bool KEEP>
+using LevelSlotsArgsOf = typename std::conditional<KEEP, LevelSlotsArgs, LevelSlotsInferArgs>::type;
+
+template <int RB, bool KEEP>
+__global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgsOf<KEEP> a) {
   // RB row blocks of 16 cell rows per workgroup: thread group g gathers rows g, g + 16, ..; with RB = 2 half as many workgroups
   // fetch the 128 KB of packed weights (64 MB of L2 traffic per launch at RB = 1)
   constexpr int BM = 16 * RB;
@@ -354,16 +400,18 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) 
           sa.acc[j] = ok ? nx.acc[j] : sa.acc[j];
         }
       }
-      f32x4 lv = {0.f, 0.f, 0.f, 0.f};
+      [[maybe_unused]] f32x4 lv = {0.f, 0.f, 0.f, 0.f};
       if (hrow[rb][0] >= 0) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
           av[j] = sa.acc[j] / sa.s[j];
-          lv[j] = sa.mx[j] + fg_log<true>(sa.s[j]);
+          if constexpr (KEEP) lv[j] = sa.mx[j] + fg_log<true>(sa.s[j]);
         }
       }
-      *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + gc) = av;
-      *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + gc) = lv;
+      if constexpr (KEEP) {
+        *reinterpret_cast<f32x4*>(a.A + (long long)v * a.ld + gc) = av;
+        *reinterpret_cast<f32x4*>(a.LSE + (long long)v * a.ld + gc) = lv;
+      }
     }
     st_bf16x4(xs + (gr + 16 * rb) * L2_XS + gc, av);
   }
@@ -381,8 +429,10 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs a) 
       if (a.b1) hv += *reinterpret_cast<const f32x4*>(a.b1 + nn);
       hv = relu4(hv);
       st_bf16x4(hs + (r16 + 16 * rb) * L2_HS + nn, hv);
-      if (a.hid_out && elive[rb])
-        hid_store4(a.hid_out, (long long)(a.cell_row0 + m0 + r16 + 16 * rb) * a.ldhid + nn, hv, a.hid16);
+      if constexpr (KEEP) {
+        if (a.hid_out && elive[rb])
+          hid_store4(a.hid_out, (long long)(a.cell_row0 + m0 + r16 + 16 * rb) * a.ldhid + nn, hv, a.hid16);
+      }
     }
   __syncthreads();
 #pragma unroll
@@ -711,9 +761,49 @@ extern "C" int mmft_level_fwd_bf16(float* h, const float* pre, long long ld, int
                  cell_row0, n_cell, A, LSE, (const unsigned short*)w1_bf16, (const unsigned short*)w2_bf16, b1, b2, hid_out,
                  ldhid, hid_bf16 ? 1 : 0, relu, active, tiles};
   const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  MMFT_LAUNCH("level_fwd_bf16_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel,
+  MMFT_LAUNCH("level_fwd_bf16_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<true>,
               dim3(tiles + net_blocks), dim3(512), (hipStream_t)stream, a);
   return check_launch("level_fwd_bf16");
+}
+
+/* Forward-only form of mmft_level_fwd_bf16: the same h, nothing kept for a reverse sweep (level_fwd_bf16_kernel<false>). */
+extern "C" int mmft_level_fwd_bf16_infer(float* h, const float* pre, long long ld, int D, const int* in_net_indptr,
+                                         const int* in_net_indices, const int* in_cell_indptr, const int* in_cell_indices,
+                                         int net_row0, int n_net, const int* cell_rows, int cell_row0, int n_cell,
+                                         const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int relu,
+                                         const unsigned char* active, const int* in_cell_driver, long long alg_bytes, int device,
+                                         void* stream) {
+  MMFT_REQUIRE(D == L2_K1, "level_fwd_bf16_infer: D must be %d", L2_K1);
+  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_bf16_infer: negative row count / offset");
+  if (n_net + n_cell == 0) return MMFT_OK;
+  MMFT_REQUIRE(h && pre && in_net_indptr && in_cell_indptr && (n_cell == 0 || (w1_bf16 && w2_bf16)),
+               "level_fwd_bf16_infer: null pointer");
+  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && (!w1_bf16 || aligned16(w1_bf16)) &&
+                   (!w2_bf16 || aligned16(w2_bf16)) && (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)),
+               "level_fwd_bf16_infer: operands must be 16-byte aligned");
+  DeviceGuard dg(device);
+  constexpr int LV_BM = 16;
+  const int tiles = cdiv(n_cell, LV_BM);
+  int net_blocks = cdiv((long long)n_net * 32, 512);
+  if (net_blocks > 1024) net_blocks = 1024;
+  LevelFwdInferArgs a{h, pre, ld, in_net_indptr, in_net_indices, in_cell_indptr, in_cell_indices, in_cell_driver, net_row0, n_net,
+                      cell_rows, cell_row0, n_cell, (const unsigned short*)w1_bf16, (const unsigned short*)w2_bf16, b1, b2, relu,
+                      active, tiles};
+  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
+  MMFT_LAUNCH("level_fwd_bf16_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<false>,
+              dim3(tiles + net_blocks), dim3(512), (hipStream_t)stream, a);
+  return check_launch("level_fwd_bf16_infer");
+}
+
+// Row blocks per workgroup of the slot-form level kernels (both the training and the forward-only form choose here).
+// Two 16-row blocks per workgroup when that still gives every CU a workgroup: the kernel takes the same 16.7 us at config B and
+// the replayed step is 0.06 ms faster (half the workgroups fetch the packed weights while the U-Net runs beside them); a
+// small level (config C: 1 250 cell rows = 78 blocks) is bound by the latency of one workgroup and takes 13.8 instead of
+// 9.7 us in that form.  MMFT_FWD_RB=1 / 2 forces one form.
+static int level_slots_rb(int n_net, int n_cell) {
+  static const int rb_env = getenv("MMFT_FWD_RB") ? atoi(getenv("MMFT_FWD_RB")) : 0;
+  const int rows_max = n_cell > n_net ? n_cell : n_net;
+  return rb_env ? rb_env : (rows_max >= 32 * 192 ? 2 : 1);
 }
 
 extern "C" int mmft_level_fwd_slots(float* h, const float* pre, long long ld, int D, const int* slots, const int* net_driver,
@@ -729,25 +819,47 @@ extern "C" int mmft_level_fwd_slots(float* h, const float* pre, long long ld, in
                    (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)) && (!hid_out || (aligned16(hid_out) && ldhid % 4 == 0)),
                "level_fwd_slots: operands must be 16-byte aligned");
   DeviceGuard dg(device);
-  // two 16-row blocks per workgroup when that still gives every CU a workgroup: the kernel takes the same 16.7 us at config B and
-  // the replayed step is 0.06 ms faster (half the workgroups fetch the packed weights while the U-Net runs beside them); a
-  // small level (config C: 1 250 cell rows = 78 blocks) is bound by the latency of one workgroup and takes 13.8 instead of
-  // 9.7 us in that form.  MMFT_FWD_RB=1 / 2 forces one form.
-  static const int rb_env = getenv("MMFT_FWD_RB") ? atoi(getenv("MMFT_FWD_RB")) : 0;
-  const int rows_max = n_cell > n_net ? n_cell : n_net;
-  const int rb = rb_env ? rb_env : (rows_max >= 32 * 192 ? 2 : 1);
+  const int rb = level_slots_rb(n_net, n_cell);
   const int bm = rb == 2 ? 32 : 16;
   const int tiles = cdiv(n_cell, bm), net_tiles = cdiv(n_net, bm);
   LevelSlotsArgs a{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, A, LSE, (const unsigned short*)w1_bf16,
                    (const unsigned short*)w2_bf16, b1, b2, hid_out, ldhid, hid_bf16 ? 1 : 0, relu, active, tiles};
   const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
   if (rb == 2)
-    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_slots_kernel<2>,
+    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<2, true>),
                 dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
   else
-    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_slots_kernel<1>,
+    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<1, true>),
                 dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
   return check_launch("level_fwd_slots");
+}
+
+/* Forward-only form of mmft_level_fwd_slots: the same h, nothing kept for a reverse sweep (level_fwd_slots_kernel<RB, false>). */
+extern "C" int mmft_level_fwd_slots_infer(float* h, const float* pre, long long ld, int D, const int* slots, const int* net_driver,
+                                          int net_row0, int n_net, int cell_row0, int n_cell, const void* w1_bf16, const float* b1,
+                                          const void* w2_bf16, const float* b2, int relu, const unsigned char* active,
+                                          long long alg_bytes, int device, void* stream) {
+  MMFT_REQUIRE(D == L2_K1, "level_fwd_slots_infer: D must be %d", L2_K1);
+  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_slots_infer: negative row count / offset");
+  if (n_net + n_cell == 0) return MMFT_OK;
+  MMFT_REQUIRE(h && pre && slots && net_driver && (n_cell == 0 || (w1_bf16 && w2_bf16)), "level_fwd_slots_infer: null pointer");
+  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && aligned16(slots) && (!w1_bf16 || aligned16(w1_bf16)) &&
+                   (!w2_bf16 || aligned16(w2_bf16)) && (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)),
+               "level_fwd_slots_infer: operands must be 16-byte aligned");
+  DeviceGuard dg(device);
+  const int rb = level_slots_rb(n_net, n_cell);
+  const int bm = rb == 2 ? 32 : 16;
+  const int tiles = cdiv(n_cell, bm), net_tiles = cdiv(n_net, bm);
+  LevelSlotsInferArgs a{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, (const unsigned short*)w1_bf16,
+                        (const unsigned short*)w2_bf16, b1, b2, relu, active, tiles};
+  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
+  if (rb == 2)
+    MMFT_LAUNCH("level_fwd_slots_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<2, false>),
+                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
+  else
+    MMFT_LAUNCH("level_fwd_slots_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<1, false>),
+                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
+  return check_launch("level_fwd_slots_infer");
 }
 
 /* Reverse sweep of one (cell level l, net level l + 1) pair, see level_bwd_pair_kernel: tiles int32[ntiles][8] (first driver id,

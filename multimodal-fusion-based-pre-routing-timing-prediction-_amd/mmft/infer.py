@@ -1,0 +1,171 @@
+"""Inference on resident designs: `Predictor` holds a batch of designs on the device, returns the predicted arrival time of
+their endpoints and lets the caller push new features / layout images (a placement that keeps changing under one netlist).
+
+The arithmetic is TrainStep.forward's whole-sweep form under torch.no_grad(): the netlist sweep in its forward-only form
+(mmft.sweep.FORWARD_ONLY: nothing kept for a reverse sweep), the U-Net from its running statistics
+(evaluate.frozen_statistics; 19 launches in bf16 mode), masked projection, fusion head.  Nothing of the model is written: no
+statistic, no counter, no gradient, no module mode.  In bf16 mode the whole call is captured once and replayed.
+"""
+import contextlib
+
+import numpy as np
+import torch
+
+from . import lib
+from .evaluate import frozen_statistics
+from .fusion import MaskedPathMap
+from .train import DesignBatch
+
+
+def design_permutations(old_of_new, node_off):
+    """Per design i the int64 array p_i with p_i[k] = row of the batch's node tensors that holds node k of design i
+    (DesignBatch renumbers the merged nodes level-major: row r holds merged node old_of_new[r])."""
+    old_of_new = np.asarray(old_of_new, dtype=np.int64)
+    new_of_old = np.empty_like(old_of_new)
+    new_of_old[old_of_new] = np.arange(old_of_new.shape[0], dtype=np.int64)
+    return [new_of_old[int(node_off[i]):int(node_off[i + 1])] for i in range(len(node_off) - 1)]
+
+
+def _as_rows(x, name, shape, device):
+    t = torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+    if not torch.is_tensor(t):
+        raise TypeError(f'update: {name} must be a numpy array or a tensor')
+    if t.dtype != torch.float32:
+        raise TypeError(f'update: {name} must be float32, got {t.dtype}')
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError(f'update: {name} has shape {tuple(t.shape)}, design expects {tuple(shape)}')
+    return t.to(device, non_blocking=True)
+
+
+def update_design(batch, perm, i, cell_feat=None, net_feat=None, image=None):
+    """Copy new features (rows in design i's own node order) / a new layout image of design i into the batch's static
+    buffers, in place: addresses stay, the copies are ordered on the current stream.  perm = design_permutations(...)[i] as
+    an int64 tensor on the batch's device.  Everything is validated before anything is written."""
+    if not 0 <= i < batch.B:
+        raise IndexError(f'update: design {i} of {batch.B}')
+    nd, n = batch.graph.ndata, int(batch.node_off[i + 1] - batch.node_off[i])
+    todo = []
+    for name, x in (('cell_feat', cell_feat), ('net_feat', net_feat)):
+        if x is not None:
+            todo.append((nd[name], _as_rows(x, name, (n, nd[name].shape[1]), nd[name].device)))
+    img = _as_rows(image, 'image', batch.images.shape[1:], batch.images.device) if image is not None else None
+    for dst, rows in todo:
+        dst.index_copy_(0, perm, rows)
+    if img is not None:
+        batch.images[i].copy_(img)
+
+
+class Predictor:
+    """Predictor(pmodel, cnn, designs, device).predict() -> (predictions, endpoint ids).
+
+    path_ids_per_design   per design the paths whose endpoints are predicted (None: every path of every design); fixed for
+                          the life of the object - one static selection, made here
+    frozen_stats          the U-Net normalises with its running statistics for the call (evaluate.frozen_statistics)
+    graphed               bf16 mode: the first predict() runs eagerly (builds weight packs, slot tables, sizes the scratch),
+                          the second is captured, later ones replay.  Eager instead: launch profiler on, an outer capture,
+                          fp32 mode, a U-Net that does not take its fused eval path.  Same results either way
+    overlap               the netlist sweep on a side stream under the U-Net (as TrainStep)
+    cone                  the sweep skips nodes outside the endpoints' fan-in cone (few endpoints of a large design)
+
+    Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
+
+    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
+                 cone=False):
+        self.pmodel, self.cnn = pmodel, cnn
+        self.device = torch.device(device)
+        self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
+        self.overlap = bool(overlap) and pmodel.gnn is not None
+        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
+        b = self.batch = DesignBatch(designs, device, pmodel.gnn.out_feat_dim if pmodel.gnn is not None else 128)
+        if path_ids_per_design is None:
+            path_ids_per_design = [np.arange(d.num_paths) for d in designs]
+        T = int(sum(len(p) for p in path_ids_per_design))
+        if T == 0:
+            raise ValueError('Predictor: no path selected')
+        self._static_idx = torch.zeros(6 * T + b.path2level.shape[0], dtype=torch.int32, device=self.device)
+        self._sel = b.select(path_ids_per_design, static=self._static_idx)
+        self._links, self._end_order = b.links, b.end_order
+        self.endpoints = np.asarray(self._sel[4])           # the caller's numbering: node_off[design] + the design's own node id
+        self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
+        self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
+        self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
+        self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
+        self._tensors = [t for root in (pmodel, cnn) if root is not None for t in list(root.parameters()) + list(root.buffers())]
+        self._replay = self._sig = self._out = None
+
+    @contextlib.contextmanager
+    def _modes_kept(self):
+        """Module modes and the U-Net's statistics-per-image switch (set for the call, as TrainStep sets it for good: with it
+        a train-mode U-Net treats every design's image as the batch of one the reference feeds) back as found, also on an
+        exception."""
+        modes = [(m, m.training) for m in self._modules]
+        per = [(m, m.per_sample_stats) for m in self._per_sample]
+        try:
+            for m in self._per_sample:
+                m.per_sample_stats = True
+            yield
+        finally:
+            for m, was in per:
+                m.per_sample_stats = was
+            for m, was in modes:
+                m.training = was
+
+    def _unet_is_fused_eval(self):
+        """Inside frozen_statistics: the U-Net call is unet16's eval forward (19 launches, nothing written)."""
+        cnn = self.cnn
+        if cnn is None:
+            return True
+        from . import cnn as C, unet16
+        bns = [m for m in cnn.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        return bool(bns) and hasattr(cnn, 'inc') and all(C.bn_uses_running_stats(bn) for bn in bns) and \
+            unet16.supported(cnn, self.batch.images, frozen_stats=True)
+
+    def _launches(self):
+        from . import sweep as _sweep
+        b, g, pm_ = self.batch, self.batch.graph, self.pmodel
+        ends_d, paths_d, foff_d, _, _, lv_d = self._sel
+        g.ndata['h'] = self.h
+        cur = torch.cuda.current_stream(self.device)
+        h_gnn = None
+        if pm_.gnn is not None:
+            if self.overlap:
+                self.side.wait_stream(cur)
+                with torch.cuda.stream(self.side):
+                    h_gnn = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
+            else:
+                h_gnn = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
+        feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
+        pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
+        if h_gnn is not None and self.overlap:
+            # joined BEFORE the masked projection, as TrainStep.forward does
+            cur.wait_stream(self.side)
+            h_gnn.record_stream(cur)
+        h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
+        return pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+
+    @torch.no_grad()
+    def predict(self):
+        """(pred, endpoints): pred [T] (or [T, nlabels]) on the device, one row per selected path in level order;
+        endpoints: host int64 array [T], the rows' endpoint nodes in the caller's numbering (node offset of the design in
+        the batch + the design's own node id).  A replayed call returns a STATIC buffer: the next predict() overwrites it -
+        clone what must survive."""
+        with self._modes_kept(), frozen_statistics(self.cnn, self.frozen_stats):
+            replay = self.graphed and not lib.PROF_ON and not torch.cuda.is_current_stream_capturing() and \
+                lib.get_math_mode() == 'bf16' and self._unet_is_fused_eval()
+            if not replay:
+                return self._launches(), self.endpoints
+            # the graph bakes in where the model lives and which modes it ran in
+            sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
+            if self._replay is None or sig != self._sig:
+                self._sig = sig
+                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors))
+            out = self._replay.run(self._launches)
+            if out is not None:                                  # an eager or the capturing call
+                self._out = out
+            return self._out, self.endpoints
+
+    def update(self, i, cell_feat=None, net_feat=None, image=None):
+        """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the
+        design's image shape) for design i; numpy arrays or tensors.  Copied into the resident buffers on the current stream:
+        the next predict() sees them, eager or replayed."""
+        update_design(self.batch, self._perm[i] if 0 <= i < len(self._perm) else None, i, cell_feat, net_feat, image)

@@ -60,6 +60,17 @@ def _launch(name, args):
     return [a.data_ptr() if torch.is_tensor(a) else a for a in args]
 
 
+class _Recorded:
+    """`_launch` spelled `recorded.call('mmft_x', a, b, ...)`: the form whose argument count the static check of the call sites
+    (tests/test_host_cpu.py) compares with the header."""
+    @staticmethod
+    def call(name, *args):
+        return _launch(name, list(args))
+
+
+recorded = _Recorded
+
+
 def relaunch(name, raw, dev, stream):
     """Repeat a launch recorded by `_launch` on the given stream (the last two arguments of every entry point)."""
     lib.call(name, *raw[:-2], dev, stream)
@@ -292,22 +303,29 @@ def mlp2_rows_bf16(x1, rows, w1p, b1, w2p, b2, out, mask=None, hid_out=None, add
     return out
 
 
-def level_fwd_bf16(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
-                   alg_bytes=0, in_cell_driver=None):
-    """Fused forward level kernel of the bf16 mode (mmft_level_fwd_bf16): folded gather + fc_cell_neigh in one launch."""
-    for t, nm in ((h, 'h'), (pre, 'pre'), (A, 'A'), (LSE, 'LSE')):
+def _level_fwd_bf16_operands(fn, h, pre, kept, in_net, in_cell, net_range, cell_rows, w1p, w2p):
+    """Checks shared by level_fwd_bf16 and its forward-only twin; `kept` = the (tensor, name) pairs with the layout of h."""
+    for t, nm in ((h, 'h'), (pre, 'pre')) + tuple(kept):
         _rows2d(t, nm)
         if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'level_fwd_bf16: {nm} must have the layout of h')
+            raise ValueError(f'{fn}: {nm} must have the layout of h')
     N = h.shape[0]
     if h.shape[1] != 128:
-        raise ValueError('level_fwd_bf16: D = 128 only')
+        raise ValueError(f'{fn}: D = 128 only')
     _csr(in_net[0], in_net[1], N, 'in_net'); _csr(in_cell[0], in_cell[1], N, 'in_cell')
     _, nrow0, nn = _rowspec(net_range if net_range is not None else (0, 0), N, 'net_range')
     ct, crow0, nc = _rowspec(cell_rows, N, 'cell_rows')
     for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'level_fwd_bf16: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+            raise ValueError(f'{fn}: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+    return N, nrow0, nn, ct, crow0, nc
+
+
+def level_fwd_bf16(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
+                   alg_bytes=0, in_cell_driver=None):
+    """Fused forward level kernel of the bf16 mode (mmft_level_fwd_bf16): folded gather + fc_cell_neigh in one launch."""
+    N, nrow0, nn, ct, crow0, nc = _level_fwd_bf16_operands('level_fwd_bf16', h, pre, ((A, 'A'), (LSE, 'LSE')), in_net, in_cell,
+                                                           net_range, cell_rows, w1p, w2p)
     _hid2d(hid_out, 'hid_out')
     if hid_out.shape != (N, 256):
         raise ValueError('level_fwd_bf16: hid_out must be [N, 256]')
@@ -317,26 +335,45 @@ def level_fwd_bf16(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, w1p, b
              _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), _same_hid_dtype(hid_out), dev, st)
 
 
-def level_fwd_slots(h, pre, slots, net_driver, net_range, cell_range, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
-                    alg_bytes=0):
-    """Slot-table form of level_fwd_bf16 (mmft_level_fwd_slots): contiguous net / cell row ranges, fan-in <= 4."""
-    for t, nm in ((h, 'h'), (pre, 'pre'), (A, 'A'), (LSE, 'LSE')):
+def level_fwd_bf16_infer(h, pre, in_net, in_cell, net_range, cell_rows, w1p, b1, w2p, b2, relu=True, active=None, alg_bytes=0,
+                         in_cell_driver=None):
+    """Forward-only twin of level_fwd_bf16 (mmft_level_fwd_bf16_infer): the same h, nothing kept for a reverse sweep.  Returns
+    the recorded launch (relaunch)."""
+    N, nrow0, nn, ct, crow0, nc = _level_fwd_bf16_operands('level_fwd_bf16_infer', h, pre, (), in_net, in_cell, net_range, cell_rows,
+                                                           w1p, w2p)
+    dev, st = lib.stream_args(h)
+    return recorded.call('mmft_level_fwd_bf16_infer', h, pre, h.stride(0), 128, in_net[0], in_net[1], in_cell[0], in_cell[1], nrow0,
+                         nn, ct, crow0, nc, w1p, b1, w2p, b2, int(relu), _active(active, N),
+                         _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), dev, st)
+
+
+def _level_fwd_slots_operands(fn, h, pre, kept, slots, net_driver, net_range, cell_range, w1p, w2p):
+    """Checks shared by level_fwd_slots and its forward-only twin."""
+    for t, nm in ((h, 'h'), (pre, 'pre')) + tuple(kept):
         _rows2d(t, nm)
         if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'level_fwd_slots: {nm} must have the layout of h')
+            raise ValueError(f'{fn}: {nm} must have the layout of h')
     N = h.shape[0]
     if h.shape[1] != 128:
-        raise ValueError('level_fwd_slots: D = 128 only')
+        raise ValueError(f'{fn}: D = 128 only')
     for t, nm, shape in ((slots, 'slots', (N, 8)), (net_driver, 'net_driver', (N,))):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'level_fwd_slots: {nm} must be a contiguous int32 CUDA tensor of shape {shape}')
+            raise ValueError(f'{fn}: {nm} must be a contiguous int32 CUDA tensor of shape {shape}')
     nrow0, nn = net_range if net_range is not None else (0, 0)
     crow0, nc = cell_range
     if min(nrow0, nn, crow0, nc) < 0 or nrow0 + nn > N or crow0 + nc > N:
-        raise ValueError('level_fwd_slots: row range outside the graph')
+        raise ValueError(f'{fn}: row range outside the graph')
     for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'level_fwd_slots: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+            raise ValueError(f'{fn}: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+    return N, nrow0, nn, crow0, nc
+
+
+def level_fwd_slots(h, pre, slots, net_driver, net_range, cell_range, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
+                    alg_bytes=0):
+    """Slot-table form of level_fwd_bf16 (mmft_level_fwd_slots): contiguous net / cell row ranges, fan-in <= 4."""
+    N, nrow0, nn, crow0, nc = _level_fwd_slots_operands('level_fwd_slots', h, pre, ((A, 'A'), (LSE, 'LSE')), slots, net_driver,
+                                                        net_range, cell_range, w1p, w2p)
     _hid2d(hid_out, 'hid_out')
     if hid_out.shape != (N, 256):
         raise ValueError('level_fwd_slots: hid_out must be [N, 256]')
@@ -344,6 +381,15 @@ def level_fwd_slots(h, pre, slots, net_driver, net_range, cell_range, A, LSE, w1
     return _launch('mmft_level_fwd_slots', [h, pre, h.stride(0), 128, slots, net_driver, nrow0, nn, crow0, nc, A, LSE, w1p, b1, w2p, b2,
                                             hid_out, hid_out.stride(0), int(relu), _active(active, N), int(alg_bytes),
                                             _same_hid_dtype(hid_out), dev, st])
+
+
+def level_fwd_slots_infer(h, pre, slots, net_driver, net_range, cell_range, w1p, b1, w2p, b2, relu=True, active=None, alg_bytes=0):
+    """Forward-only twin of level_fwd_slots (mmft_level_fwd_slots_infer): the same h, nothing kept for a reverse sweep."""
+    N, nrow0, nn, crow0, nc = _level_fwd_slots_operands('level_fwd_slots_infer', h, pre, (), slots, net_driver, net_range, cell_range,
+                                                        w1p, w2p)
+    dev, st = lib.stream_args(h)
+    return recorded.call('mmft_level_fwd_slots_infer', h, pre, h.stride(0), 128, slots, net_driver, nrow0, nn, crow0, nc, w1p, b1, w2p,
+                         b2, int(relu), _active(active, N), int(alg_bytes), dev, st)
 
 
 def level_bwd_pair(G, h, A, LSE, DA, own, tiles, ntiles, out_net_indptr, sink_shift, cslots, out_cell, scratch, counters, w1p, w2p,
@@ -636,8 +682,10 @@ def pair_fwd_gather(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, relu=
         ct, crow0, nc = None, 0, 0
     else:
         ct, crow0, nc = _rowspec(cell_rows, N, 'cell_rows')
-        _rows2d(A, 'A'); _rows2d(LSE, 'LSE')
-        if A.shape != h.shape or LSE.shape != h.shape or LSE.stride(0) != A.stride(0):
+        _rows2d(A, 'A')
+        if LSE is not None:                      # LSE None: a forward-only sweep, the log-sum-exp is not written
+            _rows2d(LSE, 'LSE')
+        if A.shape != h.shape or (LSE is not None and (LSE.shape != h.shape or LSE.stride(0) != A.stride(0))):
             raise ValueError('pair_fwd_gather: A / LSE must match h')
     if heavy is not None:
         _idx(heavy, 'heavy')

@@ -9,6 +9,9 @@ instead of DGL's out-of-place frame update per pull:
     HS  [N, Hd]  hidden activations of the *_self MLPs                 HN  [N, Hd] of fc_cell_neigh
     G   [N, D]   d loss / d pre-activation (reverse sweep)             DA  [N, D]  d loss / d A
 
+Every buffer but h is allocated by the first launch that needs it: a forward-only sweep (FORWARD_ONLY, under no_grad) of a
+schedule whose cell levels all take a fused level kernel holds h and PRE alone.
+
 Autograd sees a chain of LevelFn nodes linked by a 1-element token, so the engine runs the levels'
 backward in strictly decreasing level order.  Each backward does: scatter the target gradients,
 one pull kernel over the level's OUT-edges (no atomics, bitwise reproducible), and for cell levels the
@@ -26,7 +29,7 @@ class SweepState:
     """State of one sweep of one graph.  Every field is declared here; __init__ gives each the value of a per-level sweep,
     the whole-sweep entry (_run_sweep, SweepFn) and the deferred head (model.py) overwrite theirs."""
     __slots__ = ('graph', 'h', 'N', 'D', 'Hd', 'relu', 'cell_feat', 'net_feat', 'params', 'need_grad', '_bufs',
-                 'A', 'LSE', 'HS', 'HN', 'G', 'DA', 'DHN', 'tflag', 'level_meta', 'levels', 'token', 'next_level',
+                 'HN', 'G', 'DA', 'DHN', 'tflag', 'level_meta', 'levels', 'token', 'next_level',
                  'bwd_active', 'complete', 'fold', 'level_lists', 'PRE', 'attn', 'wpack', 'active', 'record',
                  'spec_lists', 'spec_token', 'spec_tix', 'target_order', 'targets_unique',
                  'hid16', 'feat_fused', 'prep', 'row_sets', 'head_batch', '_empty_rows')
@@ -64,10 +67,7 @@ class SweepState:
             bufs.clear()
             bufs['key'] = key
         self._bufs = bufs
-        self.A = self._buf('A', self.D)
-        self.LSE = self._buf('LSE', self.D)
-        self.HS = self._buf('HS', self.Hd)
-        self.HN = self._buf('HN', self.Hd)
+        self.HN = None              # fc_cell_neigh's hidden rows: hidden_rows() / the whole-sweep entry; None: nothing kept
         self.G = self.DA = self.DHN = self.tflag = None
         self.level_meta = None      # per-level static facts (contiguous range, algorithmic bytes), whole-sweep entry
         self.levels = []            # (level_id, rows) in forward order
@@ -99,6 +99,17 @@ class SweepState:
             b = torch.zeros((self.N, width), dtype=dtype, device=self.h.device)
             self._bufs[name] = b
         return b
+
+    # allocated by the first launch that names them (a forward-only sweep of fused levels never does)
+    A = property(lambda self: self._buf('A', self.D))
+    LSE = property(lambda self: self._buf('LSE', self.D))
+    HS = property(lambda self: self._buf('HS', self.Hd))
+
+    def hidden_rows(self):
+        """HN, the hidden activations of fc_cell_neigh: what the whole-sweep entry chose, else the fp32 buffer (first use allocates)."""
+        if self.HN is None:
+            self.HN = self._buf('HN', self.Hd)
+        return self.HN
 
     def hidden_grads(self):
         """DHN, the hidden gradients of fc_cell_neigh, in the format the forward chose for HN; allocated on first use."""
@@ -217,16 +228,17 @@ def _w(p):
     return d if d.is_contiguous() else d.contiguous()
 
 
-def _cell_neigh_fwd(st, rows, w1g, b1g, w2g, b2g, act):
-    """h[rows] = act(h[rows] + fc_cell_neigh(A[rows])), HN[rows] saved: one fused launch when the widths allow."""
+def _cell_neigh_fwd(st, rows, w1g, b1g, w2g, b2g, act, keep=True):
+    """h[rows] = act(h[rows] + fc_cell_neigh(A[rows])), HN[rows] saved: one fused launch when the widths allow.
+    keep=False (forward-only sweep, bf16 mode): the hidden rows are not stored."""
     if st.wpack is not None:
-        ops.mlp2_rows_bf16(st.A, rows, st.wpack[0], b1g, st.wpack[1], b2g, st.h, hid_out=st.HN, add_act=True,
-                           relu_out=(act == ops.ACT_RELU), active=st.active)
+        ops.mlp2_rows_bf16(st.A, rows, st.wpack[0], b1g, st.wpack[1], b2g, st.h, hid_out=st.hidden_rows() if keep else None,
+                           add_act=True, relu_out=(act == ops.ACT_RELU), active=st.active)
     elif ops.mlp2_fusable(st.D, st.Hd, st.D):
-        ops.mlp2_rows(st.A, rows, w1g, b1g, w2g, b2g, st.h, kmajor=False, hid_out=st.HN, add_act=True,
+        ops.mlp2_rows(st.A, rows, w1g, b1g, w2g, b2g, st.h, kmajor=False, hid_out=st.hidden_rows(), add_act=True,
                       relu_out=(act == ops.ACT_RELU), active=st.active)
     else:
-        ops.linear_fwd(st.A, w1g, b1g, y=st.HN, xidx=rows, yidx=rows, act=ops.ACT_RELU)
+        ops.linear_fwd(st.A, w1g, b1g, y=st.hidden_rows(), xidx=rows, yidx=rows, act=ops.ACT_RELU)
         ops.linear_fwd(st.HN, w2g, b2g, y=st.h, xidx=rows, yidx=rows, epi=ops.EPI_ADD_ACT, act=act)
 
 
@@ -507,6 +519,9 @@ LEVEL_BWD_PAIRS = True              # reverse sweep: one launch per (cell level,
                                     # allows it (PinGraph.level_bwd_pairs; mmft_level_bwd_pair)
 FOLD_LEVELS = True                  # folded forward chain (one gather per (net, cell) level PAIR) when the graph allows it
 FUSED_FIRST_LAYER_GRADS = True      # mmft_mlp2_first_layer_grads for the *_self MLPs (False: dgrad GEMM + wgrad GEMM)
+FORWARD_ONLY = True                 # a sweep without a backward (no_grad / frozen parameters, no attention branch) keeps nothing for
+                                    # one: bf16 mode, folded chain - the fused levels run the *_infer kernels (no A / LSE / hidden
+                                    # rows stored), heavy fan-in levels gather without LSE and run the MLP without hid_out
 
 
 SWEEP_REPLAY = True      # drop-in loop: the speculative sweep's forward / reverse launches replayed from captured HIP graphs
@@ -595,7 +610,11 @@ class SweepFn(torch.autograd.Function):
         # consumer rounds them to bf16 anyway (MFMA operands of the weight gradients) or reads the sign only (ReLU mask); only
         # the first layer's bias gradient now sums the rounded hidden gradients instead of the fp32 ones
         st.hid16 = bool(HIDDEN_BF16 and st.wpack is not None and isinstance(rc2, tuple) and st.attn is None)
-        st.HN = st._buf('HN16', st.Hd, torch.bfloat16) if st.hid16 else st._buf('HN', st.Hd)
+        fold = st.fold if (FOLD_LEVELS and st.attn is None) else None
+        # forward-only: nobody will ask for this sweep's backward.  Only the bf16 folded chain has launches that keep less;
+        # fp32 mode, the attention branch and unfolded schedules run what they always ran
+        fwd_only = bool(FORWARD_ONLY and not st.need_grad and c12 is None and st.wpack is not None and fold is not None)
+        st.HN = None if fwd_only else (st._buf('HN16', st.Hd, torch.bfloat16) if st.hid16 else st._buf('HN', st.Hd))
         st.DHN = None
         # recorded launches of the two per-level kernels (ops.relaunch), kept in the sweep's record
         st.prep = prep = st.record.calls if (RECORD_LAUNCHES and st.record is not None) else None
@@ -621,7 +640,6 @@ class SweepFn(torch.autograd.Function):
             else:
                 _linear_rows(st.cell_feat, w1c, b1c, st.HS, rc2, act=ops.ACT_RELU)
                 _linear_rows(st.HS, w2c, b2c, st.h, rc2)
-        fold = st.fold if (FOLD_LEVELS and st.attn is None) else None
         if fold is not None:
             st.PRE = st._buf('PRE', st.D)     # fc_net_self outputs live apart from h: the folded gather updates h in place
         if rn is not None:                                                               # fc_net_self, all net nodes
@@ -650,11 +668,24 @@ class SweepFn(torch.autograd.Function):
                 fused = has_cell and st.wpack is not None and fold[level_id]['heavy_in'] is None and FUSE_LEVEL_FWD
                 # gather bytes of the pair + what the MLP part must move per cell row: h read and written (2 x 4 D) and the
                 # hidden row kept for the reverse sweep (4 Hd or 2 Hd)
-                level_bytes = (meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if meta_c else 0) + \
-                    (level_rows[level_id].numel() * (8 * st.D + (2 if st.hid16 else 4) * st.Hd) if (meta_c and has_cell) else 0)
+                kept_bytes = level_rows[level_id].numel() * (8 * st.D + (2 if st.hid16 else 4) * st.Hd) if (meta_c and has_cell) else 0
+                level_bytes = (meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if meta_c else 0) + kept_bytes
                 if fused and slot_tabs is not None and fold[level_id]['range'] is not None and slot_tabs[2][level_id] <= 4 and \
                         (fold[net_l]['range'] is not None or not fold[net_l]['n']):
                     # ... with the static slot table instead of the per-edge index chain, net rows inside the cell workgroups
+                    if fwd_only:
+                        # (a key of its own: a training step after this sweep must not re-issue a launch that leaves A / LSE stale;
+                        #  bytes: A and LSE - which happen to weigh what h read + written does - and the hidden row are not moved)
+                        rec = prep.get(('fi', level_id)) if prep is not None else None
+                        if rec is not None:
+                            ops.relaunch('mmft_level_fwd_slots_infer', rec, dev_, stream_)
+                            continue
+                        rec = ops.level_fwd_slots_infer(st.h, st.PRE, slot_tabs[0], slot_tabs[1], fold[net_l]['range'] or (0, 0),
+                                                        fold[level_id]['range'], st.wpack[0], b1g, st.wpack[1], b2g, relu=st.relu,
+                                                        active=st.active, alg_bytes=level_bytes - kept_bytes)
+                        if prep is not None:
+                            prep[('fi', level_id)] = rec
+                        continue
                     rec = prep.get(('f', level_id)) if prep is not None else None
                     if rec is not None:
                         ops.relaunch('mmft_level_fwd_slots', rec, dev_, stream_)
@@ -665,18 +696,24 @@ class SweepFn(torch.autograd.Function):
                     if prep is not None:
                         prep[('f', level_id)] = rec
                     continue
+                if fused and fwd_only:
+                    ops.level_fwd_bf16_infer(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.wpack[0], b1g,
+                                             st.wpack[1], b2g, relu=st.relu, active=st.active, in_cell_driver=drv,
+                                             alg_bytes=level_bytes - kept_bytes)
+                    continue
                 if fused:
                     # bf16 mode: gather + fc_cell_neigh of the pair in ONE launch
                     ops.level_fwd_bf16(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.A, st.LSE,
                                        st.wpack[0], b1g, st.wpack[1], b2g, st.HN, relu=st.relu, active=st.active, in_cell_driver=drv,
                                        alg_bytes=level_bytes)
                     continue
-                ops.pair_fwd_gather(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.A, st.LSE,
-                                    relu=st.relu, heavy=fold[level_id]['heavy_in'] if has_cell else None, active=st.active,
-                                    in_cell_driver=drv,
+                # (forward-only: A is the transient between the two launches, LSE is not written, the hidden rows are not stored)
+                ops.pair_fwd_gather(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow,
+                                    st.A if has_cell else None, None if (fwd_only or not has_cell) else st.LSE, relu=st.relu,
+                                    heavy=fold[level_id]['heavy_in'] if has_cell else None, active=st.active, in_cell_driver=drv,
                                     alg_bytes=(meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if (meta_c and has_cell) else 0))
                 if has_cell:
-                    _cell_neigh_fwd(st, level_rows[level_id], w1g, b1g, w2g, b2g, act)
+                    _cell_neigh_fwd(st, level_rows[level_id], w1g, b1g, w2g, b2g, act, keep=not fwd_only)
         for level_id, rows in enumerate(level_rows):
             if fold is not None or level_id == 0 or not rows.numel():
                 continue

@@ -1,0 +1,116 @@
+"""Host side of the inference path (mmft.infer, the forward-only sweep): what can be checked without a GPU."""
+import ast
+import os
+import re
+
+import numpy as np
+import pytest
+import torch
+
+from mmft import lib
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+INFER_ENTRIES = ('mmft_level_fwd_slots_infer', 'mmft_level_fwd_bf16_infer')
+DROPPED = ('A', 'LSE', 'hid_out', 'ldhid', 'hid_bf16')
+
+
+def _protos():
+    hdr = open(lib.HEADER_PATH).read()
+    out = {}
+    for m in re.finditer(r'\bint\s+(mmft_\w+)\s*\(([^;]*?)\)\s*;', hdr, re.S):
+        out[m.group(1)] = [a.split()[-1].lstrip('*') for a in m.group(2).split(',')]
+    return out
+
+
+def test_header_declares_the_forward_only_entry_points_as_their_twins_minus_what_is_kept():
+    protos = _protos()
+    for name in INFER_ENTRIES:
+        assert name in lib.header_symbols(), name
+        twin = protos[name[:-len('_infer')]]
+        assert protos[name] == [a for a in twin if a not in DROPPED], name
+        assert all(a in twin for a in DROPPED)
+
+
+def test_library_exports_the_forward_only_entry_points():
+    if not os.path.exists(lib.LIB_PATH):
+        pytest.skip('needs the built library')
+    L = lib.load()
+    for name in INFER_ENTRIES:
+        assert hasattr(L, name), name
+
+
+def test_ops_wrappers_pass_the_declared_number_of_arguments_in_the_checked_spelling():
+    """The wrappers record their launch (ops._launch) through `recorded.call('mmft_x', ...)`: the spelling that
+    test_every_call_site_matches_the_header recognises, so that test covers them; counted here as well."""
+    protos = _protos()
+    src = open(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', 'mmft', 'ops.py')).read()
+    seen = {}
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ('call', 'query') and node.args \
+                and isinstance(node.args[0], ast.Constant) and node.args[0].value in INFER_ENTRIES:
+            assert not any(isinstance(a, ast.Starred) for a in node.args)
+            seen[node.args[0].value] = len(node.args) - 1
+    assert seen == {name: len(protos[name]) for name in INFER_ENTRIES}
+
+
+def test_forward_only_flag_exists_and_is_on():
+    from mmft import sweep as S
+    assert S.FORWARD_ONLY is True
+
+
+def test_sweep_state_buffers_are_allocated_by_their_first_use():
+    from mmft.sweep import SweepState
+    st = object.__new__(SweepState)
+    st._bufs, st.N, st.D, st.Hd, st.h, st.HN, st.DHN, st.hid16 = {}, 5, 4, 8, torch.zeros(5, 4), None, None, False
+    assert st._bufs == {}
+    a = st.A
+    assert set(st._bufs) == {'A'} and a.shape == (5, 4) and st.A is a and not bool(a.any())
+    assert st.LSE.shape == (5, 4) and st.HS.shape == (5, 8) and set(st._bufs) == {'A', 'LSE', 'HS'}
+    assert st.HN is None                                     # a plain field: reading it allocates nothing
+    hn = st.hidden_rows()
+    assert st.HN is hn and hn.shape == (5, 8) and set(st._bufs) == {'A', 'LSE', 'HS', 'HN'}
+    with pytest.raises(AttributeError):
+        st.A = a                                             # no field to overwrite: the buffer lives in the graph's dict
+
+
+def test_design_permutations_invert_the_batch_renumbering():
+    from mmft.infer import design_permutations
+    rng = np.random.default_rng(0)
+    old_of_new = rng.permutation(11)
+    node_off = np.array([0, 4, 11])
+    perms = design_permutations(old_of_new, node_off)
+    assert [p.shape[0] for p in perms] == [4, 7]
+    for i, p in enumerate(perms):
+        assert (old_of_new[p] == node_off[i] + np.arange(p.shape[0])).all()
+    assert sorted(np.concatenate(perms).tolist()) == list(range(11))
+
+
+def test_update_puts_design_order_rows_on_their_batch_rows():
+    """Two designs merged and renumbered on the CPU: rows pushed in each design's own node order land where
+    DesignBatch itself would have put them (old_of_new), the other design's rows and the addresses stay."""
+    from mmft.infer import design_permutations, update_design
+    from mmft.synth import synth_design
+    from mmft.train import DesignBatch
+    designs = [synth_design(N=600, L=8, tile=32, seed=50 + i, end_frac=0.2) for i in range(2)]
+    b = DesignBatch(designs, 'cpu')
+    nd = b.graph.ndata
+    perms = [torch.from_numpy(p) for p in design_permutations(b.old_of_new, b.node_off)]
+    ptrs = (nd['cell_feat'].data_ptr(), nd['net_feat'].data_ptr(), b.images.data_ptr())
+    rng = np.random.default_rng(1)
+    new_cell = [rng.standard_normal(d.cell_feat.shape).astype(np.float32) for d in designs]
+    new_net = rng.standard_normal(designs[1].net_feat.shape).astype(np.float32)
+    new_img = rng.random(designs[0].image.shape).astype(np.float32)
+    update_design(b, perms[0], 0, cell_feat=new_cell[0], image=torch.from_numpy(new_img))
+    update_design(b, perms[1], 1, cell_feat=new_cell[1], net_feat=new_net)
+    assert np.array_equal(nd['cell_feat'].numpy(), np.concatenate(new_cell)[b.old_of_new])
+    assert np.array_equal(nd['net_feat'].numpy(), np.concatenate([designs[0].net_feat, new_net])[b.old_of_new])
+    assert np.array_equal(b.images[0].numpy(), new_img) and np.array_equal(b.images[1].numpy(), designs[1].image)
+    assert ptrs == (nd['cell_feat'].data_ptr(), nd['net_feat'].data_ptr(), b.images.data_ptr())
+    before = nd['cell_feat'].clone()
+    for bad in (dict(cell_feat=new_cell[0][:-1]), dict(cell_feat=new_cell[0].astype(np.float64)), dict(image=new_img[:, :-1]),
+                dict(net_feat=new_net[:, :1])):
+        with pytest.raises((TypeError, ValueError)):
+            update_design(b, perms[0], 0, **bad)
+    with pytest.raises(IndexError):
+        update_design(b, perms[0], 2, cell_feat=new_cell[0])
+    assert torch.equal(nd['cell_feat'], before)
