@@ -30,6 +30,8 @@ extern "C" {
 #define MMFT_POOL_MAX 0
 #define MMFT_POOL_AVG 1
 
+/* 201: the bias corrections of mmft_adam_step are double (they were float up to 200): a caller built against an older header
+ * passes them in the wrong registers. */
 int mmft_version(void);
 const char* mmft_last_error(void);
 /* Arithmetic of the MFMA-bound contractions (dense layers, convolutions, fused level MLPs), process-wide:
@@ -459,10 +461,12 @@ int mmft_eval_sums_by_level(const float* pred, const float* arrival, const float
                             const int* level, int n, int num_levels, double* out, int device, void* stream);
 /* one Adam step over flat buffers, same operation order as torch.optim.Adam (amsgrad=False):
  * g += wd*p; m = lerp(m, g, 1-b1); v = b2*v + (1-b2)*g*g; p -= (lr/bc1) * m / (sqrt(v)/sqrt(bc2) + eps)
- * gscale multiplies the gradient first (1/world_size after a sum all-reduce) */
+ * gscale multiplies the gradient first (1/world_size after a sum all-reduce).  The bias corrections 1 - beta^t are fp64:
+ * lr / bc1 and sqrt(bc2) are formed in fp64 and rounded to fp32 once, as torch does and as mmft_adam_step_counted does in
+ * the kernel, so the three Adam entry points take bit-identical steps from the same state. */
 int mmft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, float bias_correction1,
-                   float bias_correction2, float gscale, int device, void* stream);
+                   float beta2, float eps, float weight_decay, double bias_correction1,
+                   double bias_correction2, float gscale, int device, void* stream);
 /* same, with the step-dependent scalars read from DEVICE memory (step_scalars[0] = lr/bias_correction1,
  * step_scalars[1] = sqrt(bias_correction2)) so that the launch can be captured once in a HIP graph and
  * replayed every step */

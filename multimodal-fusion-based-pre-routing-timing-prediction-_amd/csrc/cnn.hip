@@ -471,19 +471,24 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const float* __restri
 }
 
 // ------------------------------------------------------------------ bilinear x2 up-sampling, align_corners=True
-// nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) of Up(bilinear=True) (src/Unet.py:48-51), with ATen's
-// arithmetic: scale = (in - 1) / (out - 1) (0 when out == 1), src = scale * dst, i0 = (int)src, i1 = i0 + (i0 < in - 1),
-// lambda1 = src - i0, lambda0 = 1 - lambda1.
-__device__ __forceinline__ void up2_coord(int o, int in, float scale, int& i0, int& i1, float& l0, float& l1) {
-  const float src = scale * (float)o;
-  i0 = (int)src;
+// nn.Upsample(scale_factor=2, mode='bilinear', align_corners=True) of Up(bilinear=True) (src/Unet.py:48-51): the source
+// index src = dst * (in - 1) / (out - 1), i0 = floor(src), i1 = i0 + (i0 < in - 1), lambda1 = src - i0, lambda0 = 1 - lambda1
+// of ATen's definition, but NOT ATen's fp32 evaluation of it: src is kept as the exact fraction o (in - 1) / (2 in - 1),
+// quotient and remainder in integers, ONE rounding in lambda1.  (scale * o in fp32 carries the rounding of scale and of the
+// product into lambda1 - an absolute 1.5e-5 at source row 127, 7e-6 of the output's scale at H = 128 against fp64.)  Parity
+// with fp64 is 1e-7; parity with the reference's own fp32 output is therefore the looser of the two, up to that 7e-6.
+// Cost: two integer divisions per output element forward, one per candidate backward - a layer only Up(bilinear=True) runs;
+// the U-Net of the benchmark and of every shipped configuration uses the transposed convolution.  o (in - 1) < 2^31 for in <= 32767, which the entry points require.
+__device__ __forceinline__ void up2_coord(int o, int in, int& i0, int& i1, float& l0, float& l1) {
+  const int den = 2 * in - 1, num = o * (in - 1);
+  i0 = num / den;
   i1 = i0 + (i0 < in - 1 ? 1 : 0);
-  l1 = src - (float)i0;
+  l1 = (float)(num - i0 * den) / (float)den;
   l0 = 1.0f - l1;
 }
 
 __global__ void __launch_bounds__(256) upsample2x_fwd_kernel(const float* __restrict__ x, float* __restrict__ y, int Nimg,
-                                                             int H, int W, int C, float sy, float sx) {
+                                                             int H, int W, int C) {
   const int Ho = 2 * H, Wo = 2 * W;
   long long total = (long long)Nimg * Ho * Wo * C;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -495,8 +500,8 @@ __global__ void __launch_bounds__(256) upsample2x_fwd_kernel(const float* __rest
     int n = (int)(p / Ho);
     int y0, y1, x0, x1;
     float ly0, ly1, lx0, lx1;
-    up2_coord(yo, H, sy, y0, y1, ly0, ly1);
-    up2_coord(xo, W, sx, x0, x1, lx0, lx1);
+    up2_coord(yo, H, y0, y1, ly0, ly1);
+    up2_coord(xo, W, x0, x1, lx0, lx1);
     const float* b = x + (long long)n * H * W * C + c;
     float v00 = b[((long long)y0 * W + x0) * C], v01 = b[((long long)y0 * W + x1) * C];
     float v10 = b[((long long)y1 * W + x0) * C], v11 = b[((long long)y1 * W + x1) * C];
@@ -507,7 +512,7 @@ __global__ void __launch_bounds__(256) upsample2x_fwd_kernel(const float* __rest
 // gather form of the backward (no atomics): input pixel (yy, xx) collects, over the few output rows / columns whose
 // source interval touches it, the weight the forward gave it
 __global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const float* __restrict__ gy, float* __restrict__ dx, int Nimg,
-                                                             int H, int W, int C, float sy, float sx) {
+                                                             int H, int W, int C) {
   const int Ho = 2 * H, Wo = 2 * W;
   long long total = (long long)Nimg * H * W * C;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long long)gridDim.x * blockDim.x) {
@@ -517,23 +522,23 @@ __global__ void __launch_bounds__(256) upsample2x_bwd_kernel(const float* __rest
     p /= W;
     int yy = (int)(p % H);
     int n = (int)(p / H);
-    // candidate outputs: src in (yy - 1, yy + 1)  <=>  o in ((yy - 1) / s, (yy + 1) / s); widened by one on both sides
-    int oy_lo = sy > 0.f ? (int)floorf((float)(yy - 1) / sy) - 1 : 0, oy_hi = sy > 0.f ? (int)ceilf((float)(yy + 1) / sy) + 1 : Ho - 1;
-    int ox_lo = sx > 0.f ? (int)floorf((float)(xx - 1) / sx) - 1 : 0, ox_hi = sx > 0.f ? (int)ceilf((float)(xx + 1) / sx) + 1 : Wo - 1;
-    oy_lo = oy_lo < 0 ? 0 : oy_lo; ox_lo = ox_lo < 0 ? 0 : ox_lo;
+    // candidate outputs: src = o (in - 1) / (2 in - 1) in (yy - 1, yy + 1)  <=>  o in ((yy - 1) (2 in - 1) / (in - 1),
+    // (yy + 1) (2 in - 1) / (in - 1)): floor and ceiling in integers (in == 1: every output reads the one input)
+    int oy_lo = H > 1 ? ((yy > 1 ? yy - 1 : 0) * (2 * H - 1)) / (H - 1) : 0, oy_hi = H > 1 ? ((yy + 1) * (2 * H - 1) + H - 2) / (H - 1) : Ho - 1;
+    int ox_lo = W > 1 ? ((xx > 1 ? xx - 1 : 0) * (2 * W - 1)) / (W - 1) : 0, ox_hi = W > 1 ? ((xx + 1) * (2 * W - 1) + W - 2) / (W - 1) : Wo - 1;
     oy_hi = oy_hi > Ho - 1 ? Ho - 1 : oy_hi; ox_hi = ox_hi > Wo - 1 ? Wo - 1 : ox_hi;
     float acc = 0.f;
     const float* g = gy + (long long)n * Ho * Wo * C + c;
     for (int oy = oy_lo; oy <= oy_hi; ++oy) {
       int y0, y1;
       float ly0, ly1;
-      up2_coord(oy, H, sy, y0, y1, ly0, ly1);
+      up2_coord(oy, H, y0, y1, ly0, ly1);
       float wy = (y0 == yy ? ly0 : 0.f) + (y1 == yy ? ly1 : 0.f);
       if (wy == 0.f && y0 != yy && y1 != yy) continue;
       for (int ox = ox_lo; ox <= ox_hi; ++ox) {
         int x0, x1;
         float lx0, lx1;
-        up2_coord(ox, W, sx, x0, x1, lx0, lx1);
+        up2_coord(ox, W, x0, x1, lx0, lx1);
         if (x0 != xx && x1 != xx) continue;
         float wx = (x0 == xx ? lx0 : 0.f) + (x1 == xx ? lx1 : 0.f);
         acc += wy * wx * g[((long long)oy * Wo + ox) * C];
@@ -845,23 +850,21 @@ int mmft_bn_train_bwd(const float* gy, const float* x, const float* y, const flo
   return check_launch("bn_train_bwd");
 }
 
-static inline float up2_scale(int in) { return 2 * in > 1 ? (float)(in - 1) / (float)(2 * in - 1) : 0.f; }
-
 int mmft_upsample_bilinear2x_fwd(const float* x, float* y, int Nimg, int H, int W, int C, int device, void* stream) {
-  MMFT_REQUIRE(x && y && Nimg > 0 && H > 0 && W > 0 && C > 0, "upsample_bilinear2x_fwd: bad args");
+  MMFT_REQUIRE(x && y && Nimg > 0 && H > 0 && W > 0 && C > 0 && H <= 32767 && W <= 32767, "upsample_bilinear2x_fwd: bad args (H, W <= 32767)");
   DeviceGuard dg(device);
   long long total = (long long)Nimg * 4 * H * W * C;
   MMFT_LAUNCH("upsample2x_fwd_kernel", 0.0, 4.0 * total * 1.25, upsample2x_fwd_kernel, dim3(ew_grid(total)), dim3(256),
-              (hipStream_t)stream, x, y, Nimg, H, W, C, up2_scale(H), up2_scale(W));
+              (hipStream_t)stream, x, y, Nimg, H, W, C);
   return check_launch("upsample_bilinear2x_fwd");
 }
 
 int mmft_upsample_bilinear2x_bwd(const float* gy, float* dx, int Nimg, int H, int W, int C, int device, void* stream) {
-  MMFT_REQUIRE(gy && dx && Nimg > 0 && H > 0 && W > 0 && C > 0, "upsample_bilinear2x_bwd: bad args");
+  MMFT_REQUIRE(gy && dx && Nimg > 0 && H > 0 && W > 0 && C > 0 && H <= 32767 && W <= 32767, "upsample_bilinear2x_bwd: bad args (H, W <= 32767)");
   DeviceGuard dg(device);
   long long total = (long long)Nimg * H * W * C;
   MMFT_LAUNCH("upsample2x_bwd_kernel", 0.0, 4.0 * total * 5.0, upsample2x_bwd_kernel, dim3(ew_grid(total)), dim3(256),
-              (hipStream_t)stream, gy, dx, Nimg, H, W, C, up2_scale(H), up2_scale(W));
+              (hipStream_t)stream, gy, dx, Nimg, H, W, C);
   return check_launch("upsample_bilinear2x_bwd");
 }
 

@@ -747,13 +747,16 @@ int mmft_eval_sums_by_level(const float* pred, const float* arrival, const float
 }
 
 int mmft_adam_step(float* p, const float* g, float* m, float* v, long long n, float lr, float beta1, float beta2, float eps,
-                   float weight_decay, float bias_correction1, float bias_correction2, float gscale, int device,
+                   float weight_decay, double bias_correction1, double bias_correction2, float gscale, int device,
                    void* stream) {
   MMFT_REQUIRE(p && g && m && v && n >= 0, "adam_step: bad args");
-  MMFT_REQUIRE(bias_correction1 > 0.f && bias_correction2 > 0.f, "adam_step: bias corrections must be positive");
+  MMFT_REQUIRE(bias_correction1 > 0.0 && bias_correction2 > 0.0, "adam_step: bias corrections must be positive");
   if (n == 0) return MMFT_OK;
   DeviceGuard dg(device);
-  MMFT_LAUNCH("adam_kernel", 0.0, 28.0 * n, adam_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, p, g, m, v, n, lr / bias_correction1, beta1, beta2, eps, weight_decay, sqrtf(bias_correction2), gscale, (const float*)nullptr);
+  // both step scalars are formed in fp64 and rounded once, as torch does on the host and adam_counted_kernel on the device:
+  // the three Adam entry points then take bit-identical steps
+  const float step_size = (float)((double)lr / bias_correction1), bc2_sqrt = (float)sqrt(bias_correction2);
+  MMFT_LAUNCH("adam_kernel", 0.0, 28.0 * n, adam_kernel, dim3(ew_grid(n)), dim3(256), (hipStream_t)stream, p, g, m, v, n, step_size, beta1, beta2, eps, weight_decay, bc2_sqrt, gscale, (const float*)nullptr);
   return check_launch("adam_step");
 }
 

@@ -508,3 +508,108 @@ def test_scratch_owner_scopes_workspace_to_its_owner(monkeypatch):
             lib.workspace('cpu', 8 << 20)
     assert getattr(lib._scope, 'owner', None) is None
     assert lib._workspace == before
+
+
+# Test files that call kernels one at a time against a reference of the same operation (the others drive whole models or steps).
+KERNEL_LEVEL_FILES = ('test_kernels_gpu.py', 'test_head_kernels_gpu.py', 'test_graph_kernels_gpu.py', 'test_cnn_layers_gpu.py',
+                      'test_bf16_gpu.py', 'test_unet16_gpu.py', 'test_unet_eval_gpu.py', 'test_fold_gpu.py', 'test_infer_gpu.py',
+                      'test_prep_gpu.py')
+# Entry points that launch no kernel of their own (size / capability queries, the launch profiler, process settings): the test
+# that covers each indirectly, and why that is enough.
+ABI_COVERED_INDIRECTLY = {
+    'mmft_version': ('test_host_cpu.py::test_library_exports_every_declared_symbol', 'a constant; read after loading the library'),
+    'mmft_set_math_mode': ('test_bf16_gpu.py::test_linear_fwd_dgrad', 'a process-wide switch: every lib.math_mode block sets and restores it'),
+    'mmft_prof_hint': ('test_bench_contract_gpu.py::test_bench_line_contract', 'profiler bookkeeping: bench --full reports the hinted launches'),
+    'mmft_prof_stamp': ('test_host_cpu.py::test_every_call_site_matches_the_header', 'a one-thread timestamp for tools/step_timeline.py; its call site is checked'),
+    'mmft_colsum_workspace_bytes': ('test_kernels_gpu.py::test_linear_wgrad_colsum', 'ops.colsum sizes its scratch with it; the entry point rejects a short one'),
+    'mmft_linear_wgrad_workspace_bytes': ('test_kernels_gpu.py::test_linear_wgrad_colsum', 'ops.linear_wgrad sizes its slabs with it'),
+    'mmft_linear_wgrad_bias_workspace_bytes': ('test_kernels_gpu.py::test_linear_wgrad_colsum', 'ops.linear_wgrad(with_bias) sizes its slabs with it'),
+    'mmft_mlp2_first_layer_grads_workspace_bytes': ('test_kernels_gpu.py::test_mlp2_first_layer_grads', 'the wrapper sizes its scratch with it'),
+    'mmft_conv2d_wgrad_workspace_bytes': ('test_kernels_gpu.py::test_conv3x3_forward_dgrad_wgrad', 'ops.conv2d_wgrad sizes its slabs with it'),
+    'mmft_outconv_bwd_workspace_bytes': ('test_kernels_gpu.py::test_outconv_fused_vs_torch', 'ops.outconv_bwd sizes its scratch with it'),
+    'mmft_mlp2_feat_bwd_workspace_bytes': ('test_bf16_gpu.py::test_feature_mlp_without_hidden_tensor', 'ops.mlp2_feat_bwd_bf16 sizes its scratch with it'),
+    'mmft_rows_outer_supported': ('test_bf16_gpu.py::test_rows_outer_weight_gradient', 'the shape gate in front of mmft_rows_outer_bf16'),
+    'mmft_rows_outer_workspace_bytes': ('test_bf16_gpu.py::test_rows_outer_weight_gradient', 'sizes the slabs of mmft_rows_outer_bf16'),
+    'mmft_u16_pack_desc_bytes': ('test_unet16_gpu.py::test_conv3x3_forward_exact_and_stats', 'unet16.pack_table asserts it equals its ctypes record'),
+    'mmft_u16_conv3x3_wgrad_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
+    'mmft_u16_convt_wgrad_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
+    'mmft_u16_outconv_bwd_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
+    'mmft_levelize_workspace_bytes': ('test_prep_gpu.py::test_levelize_trace_masks_vs_restatement', 'prep.levelize sizes its scratch with it'),
+    'mmft_minmax_workspace_bytes': ('test_prep_gpu.py::test_minmax_normalize_bit_exact', 'prep.minmax_normalize_ sizes its scratch with it'),
+}
+
+
+# Entry points that a kernel-level test reaches through a thin wrapper, so that the test's code never spells their name:
+# (test file, wrapper module under mmft/, wrapper function).  The ledger checks the chain: the wrapper's body holds the
+# lib.call('mmft_...') literal and the test file's code calls the wrapper.
+ABI_CALLED_THROUGH_WRAPPER = {
+    'mmft_linear_wgrad_bias': ('test_kernels_gpu.py', 'ops.py', 'linear_wgrad'),
+    'mmft_rows_outer_bf16': ('test_bf16_gpu.py', 'ops.py', 'linear_wgrad'),
+    'mmft_path_mask_count': ('test_prep_gpu.py', 'prep.py', 'rasterize_path_masks'),
+    'mmft_path_mask_fill': ('test_prep_gpu.py', 'prep.py', 'rasterize_path_masks'),
+    'mmft_minmax_normalize': ('test_prep_gpu.py', 'prep.py', 'minmax_normalize_'),
+    'mmft_u16_pack_weights': ('test_unet16_gpu.py', 'unet16.py', 'pack_run'),
+}
+
+
+def _code_only(src):
+    """Python source without comments and docstrings: what is left are names and the string literals that code uses."""
+    import ast
+    import io
+    import tokenize
+    doc = set()
+    for node in ast.walk(ast.parse(src)):
+        if isinstance(node, (ast.Module, ast.FunctionDef, ast.ClassDef)) and node.body and isinstance(node.body[0], ast.Expr) and \
+                isinstance(node.body[0].value, ast.Constant) and isinstance(node.body[0].value.value, str):
+            doc.add(node.body[0].lineno)
+    out = []
+    for tok in tokenize.generate_tokens(io.StringIO(src).readline):
+        if tok.type == tokenize.COMMENT or (tok.type == tokenize.STRING and tok.start[0] in doc):
+            continue
+        out.append(tok.string)
+    return ' '.join(out)
+
+
+def test_every_abi_entry_point_has_a_kernel_level_test():
+    """The claim "every C-ABI entry point has a kernel-level test" kept honest.  Each function declared in include/mmft.h is
+    (1) named in the CODE of a kernel-level GPU test file - comments and docstrings do not count - with or without the mmft_
+        prefix, or as the device kernel NAME_kernel that a test demands from the launch profiler's report; or
+    (2) listed in ABI_CALLED_THROUGH_WRAPPER, and the chain test code -> wrapper -> lib.call('mmft_NAME') is there; or
+    (3) listed in ABI_COVERED_INDIRECTLY (queries, profiling helpers, process settings) with an existing test and a reason.
+    No table holds a name that an earlier rule covers, or one that is not declared."""
+    import ast
+    import os
+    import re
+    here = os.path.dirname(os.path.abspath(__file__))
+    root = os.path.dirname(here)
+    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(root, 'include', 'mmft.h')).read(), flags=re.S)
+    names = re.findall(r'\b(?:int|long long|const char\*)\s+(mmft_[a-z0-9_]+)\s*\(', hdr)
+    assert len(names) == len(set(names)) >= 120 and set(names) == set(lib.header_symbols())
+    code = {}
+    for f in KERNEL_LEVEL_FILES:
+        src = open(os.path.join(here, f)).read()
+        assert 'pytest.mark.gpu' in src, f
+        code[f] = _code_only(src)
+    assert _code_only('"""mmft_a"""\nx = f("mmft_b")  # mmft_c\n').split() == ['x', '=', 'f', '(', '"mmft_b"', ')']
+
+    def in_code(n, t):
+        return re.search(r'(?<![A-Za-z0-9_])(?:mmft_)?' + n[len('mmft_'):] + r'(?:_kernel)?(?![A-Za-z0-9_])', t) is not None
+    named = {n for n in names if any(in_code(n, t) for t in code.values())}
+    pkg = os.path.join(root, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', 'mmft')
+    for n, (tf, mod, fn) in ABI_CALLED_THROUGH_WRAPPER.items():
+        assert n in names and n not in named, f'{n}: declared, and not already named in test code'
+        msrc = open(os.path.join(pkg, mod)).read()
+        body = [ast.get_source_segment(msrc, node) for node in ast.walk(ast.parse(msrc)) if isinstance(node, ast.FunctionDef) and node.name == fn]
+        assert len(body) == 1 and f"'{n}'" in _code_only(body[0]), f'{mod}:{fn} does not call {n}'
+        assert tf in KERNEL_LEVEL_FILES and re.search(r'(?<![A-Za-z0-9_])' + re.escape(fn) + r' \(', code[tf]), f'{tf} does not call {fn}'
+    covered = named | set(ABI_CALLED_THROUGH_WRAPPER)
+    missing = sorted(set(names) - covered - set(ABI_COVERED_INDIRECTLY))
+    assert not missing, f'entry points without a kernel-level test: {missing}'
+    assert not sorted(set(ABI_COVERED_INDIRECTLY) & covered), sorted(set(ABI_COVERED_INDIRECTLY) & covered)
+    assert not sorted(set(ABI_COVERED_INDIRECTLY) - set(names))
+    for n, (test_id, why) in ABI_COVERED_INDIRECTLY.items():
+        f, t = test_id.split('::')
+        assert re.search(r'^def ' + t + r'\(', open(os.path.join(here, f)).read(), re.M), (n, test_id)
+        assert len(why) > 10
+        assert re.search(r'(_workspace_bytes|_supported|_slabs|_desc_bytes)$|^mmft_(prof_\w+|version|last_error|set_math_mode)$', n), \
+            f'{n}: the table is for queries, profiling helpers and process settings only'

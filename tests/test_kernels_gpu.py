@@ -1,4 +1,9 @@
-"""Kernel-level parity: every C-ABI entry point against plain torch fp64 math on the same inputs."""
+"""Kernel-level parity of the dense layers, the fp32 convolutions, the level gathers and the fused OutConv against plain torch
+fp64 math on the same inputs.  The other entry points of include/mmft.h have kernel-level files of their own: the fusion head and
+step glue in test_head_kernels_gpu.py, segment sums / row flags / the attention branch in test_graph_kernels_gpu.py, the fp32 CNN
+layer kernels in test_cnn_layers_gpu.py (and, from before, the bf16 paths in test_bf16_gpu.py / test_unet16_gpu.py /
+test_unet_eval_gpu.py, the folded and forward-only level kernels in test_fold_gpu.py / test_infer_gpu.py, preprocessing in
+test_prep_gpu.py).  tests/test_host_cpu.py::test_every_abi_entry_point_has_a_kernel_level_test keeps that list complete."""
 import numpy as np
 import pytest
 import torch
@@ -72,7 +77,7 @@ def test_linear_wgrad_colsum(dev, rows, out, inn):
     assert torch.equal(ops.linear_wgrad(g, x), dw)
     cs = ops.colsum(g)
     assert rel_err(cs, g.double().sum(0)) < TOL
-    # weight and bias gradient from one pass over g (column sums as a by-product of the n-tile-0 workgroups)
+    # mmft_linear_wgrad_bias: weight and bias gradient from one pass over g (column sums as a by-product of the n-tile-0 workgroups)
     dw3, db3 = ops.linear_wgrad(g, x, with_bias=True)
     assert torch.equal(dw3, dw)
     assert rel_err(db3, g.double().sum(0)) < TOL
@@ -347,6 +352,10 @@ def test_outconv_fused_vs_torch(dev, pooling, N, H, W, Ci):
     out.backward(gy.to(dev))
     assert rel_err(xg.grad, xd.grad) < 1e-5
     assert rel_err(wg.grad, wd.grad) < 1e-5 and rel_err(bg.grad, bd.grad) < 1e-5
+    # the two entry points by name (mmft_outconv_fwd / mmft_outconv_bwd): what the autograd node above ran
+    assert torch.equal(ops.outconv_fwd(xg.detach(), wg.detach(), bg.detach(), mode), out.detach())
+    dx_, dw_, db_ = ops.outconv_bwd(xg.detach(), wg.detach(), bg.detach(), gy.to(dev).contiguous(), mode)
+    assert rel_err(dx_, xd.grad) < 1e-5 and rel_err(dw_.reshape(-1), wd.grad.reshape(-1)) < 1e-5 and rel_err(db_, bd.grad) < 1e-5
     # the composition the other shapes take
     x2 = xg.detach().clone().requires_grad_(True)
     out2 = C.relu(C.pool2x2(C.conv2d(x2, wg, bg, pad=0), mode))

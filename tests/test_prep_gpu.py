@@ -21,6 +21,8 @@ def csr(n, rows, cols, dev):
 
 @pytest.mark.parametrize('n,e,seed', [(50, 120, 0), (3000, 12000, 1), (20000, 50000, 2)])
 def test_levelize_trace_masks_vs_restatement(dev, n, e, seed):
+    """mmft_levelize, mmft_trace_critical_paths and the two mask passes mmft_path_mask_count + mmft_path_mask_fill (through the
+    mmft.prep wrappers, which add only the scan between the passes) against the CPU restatement, bit for bit."""
     from mmft import prep
     src, dst = random_dag(n, e, seed)
     suc, pre = PR.adjacency(n, src, dst)
@@ -90,6 +92,7 @@ def test_prep_edge_cases(dev):
 
 
 def test_minmax_normalize_bit_exact(dev):
+    """mmft_minmax_normalize (prep.minmax_normalize_) against the restated reference scaling, bit for bit, NaN columns included."""
     from mmft import prep
     torch.manual_seed(0)
     f = torch.randn(70001, 7) * 3 + 1

@@ -39,7 +39,7 @@ def conv_weight_dev(w, dev):
 
 
 def run_conv(x_nhwc_dev, rgb, w_dev, backward, N, H, W, Ci, Co, stats=True, dev=None):
-    """mmft_u16_conv3x3 with a freshly packed weight; returns (bf16 [N,H,W,Co], stats [tiles,2,Co] or None)."""
+    """mmft_u16_conv3x3 with a weight freshly packed by mmft_u16_pack_weights (unet16.pack_run); returns (bf16 [N,H,W,Co], stats [tiles,2,Co] or None)."""
     buf, table, offs, lanes = unet16.pack_table([unet16.conv_pack_entries('w', w_dev, backward=backward)], dev)
     unet16.pack_run(buf, table, 1, lanes)
     y = torch.empty((N, H, W, Co), dtype=BF, device=dev)
