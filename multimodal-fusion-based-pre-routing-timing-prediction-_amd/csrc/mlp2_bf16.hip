@@ -14,7 +14,6 @@
 //   * 8 waves per 32-row tile: wave w owns hidden columns [32w, 32w + 32) and output columns [16w, 16w + 16).
 // The reverse form (weights_kmajor in the fp32 kernel) is the same kernel fed with the transposed packs.
 #include <stdlib.h>
-#include <type_traits>
 #include "mlp_tile_bf16.h"
 #include "fold_gather.h"
 
@@ -128,28 +127,19 @@ __global__ void __launch_bounds__(512) mlp2_rows_bf16_kernel(Mlp2Bf16Args a) {
 // Rows with very many in-edges are walked serially by one thread group here: the caller uses the two-kernel form
 // (pair_fwd_gather with its whole-workgroup path + mlp2_rows_bf16) for levels that have such rows.
 // ------------------------------------------------------------------------------------------------------------------
-struct LevelFwdArgs {
-  float* h;
-  const float* pre;
-  long long ld;
-  const int *in_ptr, *in_idx, *ic_ptr, *ic_idx, *ic_drv;
-  int net_row0, n_net;
-  const int* rows;
-  int cell_row0, n_cell;
+// What the training form (KEEP = true) stores for the reverse sweep: the fan-in sums, their log-sum-exp and the hidden rows.
+// The forward-only form (KEEP = false, the *_infer entry points) keeps nothing of the cell rows, so these have no address there.
+template <bool KEEP>
+struct Kept {};
+template <>
+struct Kept<true> {
   float *A, *LSE;
-  const unsigned short *w1, *w2;
-  const float *b1, *b2;
   float* hid_out;
   long long ldhid;
-  int hid16;                   // mask / hid_out hold bf16
-  int relu;
-  const unsigned char* active;
-  int cell_tiles;
+  int hid16;                   // hid_out holds bf16
 };
 
-// Forward-only form (KEEP = false, mmft_level_fwd_bf16_infer): nothing of the cell rows is kept for a reverse sweep, so A, LSE
-// and the hidden rows have no address here
-struct LevelFwdInferArgs {
+struct LevelFwdCommon {
   float* h;
   const float* pre;
   long long ld;
@@ -161,18 +151,18 @@ struct LevelFwdInferArgs {
   const float *b1, *b2;
   int relu;
   const unsigned char* active;
-  int cell_tiles;
+  int cell_tiles;              // set by the launcher
 };
 
 template <bool KEEP>
-using LevelFwdArgsOf = typename std::conditional<KEEP, LevelFwdArgs, LevelFwdInferArgs>::type;
+struct LevelFwdArgs : LevelFwdCommon, Kept<KEEP> {};
 
 // 16 rows per tile: one gather item per thread and twice as many workgroups as the 32-row tile of mlp2_rows_bf16_kernel -
 // the gather, not the MLP, sets the duration of a level, and it wants the memory-level parallelism.
 // KEEP = false: h alone is the result - no store of A / LSE / the hidden rows and no log for LSE; every instruction that
 // decides a value of h is the one of KEEP = true (the bf16 tile of A still goes to LDS: it is the MLP's input).
 template <bool KEEP>
-__global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgsOf<KEEP> a) {
+__global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs<KEEP> a) {
   constexpr int BM = 16;
   __shared__ __attribute__((aligned(16))) unsigned short xs[BM * L2_XS];
   __shared__ __attribute__((aligned(16))) unsigned short hs[BM * L2_HS];
@@ -267,44 +257,25 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgsOf<KEEP
 //   * the net rows of level l - 1 are no longer separate workgroups (504 cell tiles + 504 net blocks on 512 workgroup
 //     slots = two rounds, the second one waiting for the first): workgroup b also writes net rows 16 b .. 16 b + 15,
 //     their loads issued ahead of the gather through `net_drv` (the single driver of every net, static).
-struct LevelSlotsArgs {
+struct LevelSlotsCommon {
   float* h;
   const float* pre;
   long long ld;
   const int* slots;      // [N][8]: hrow[4], prow[4]; hrow < 0: no edge; prow < 0: the edge's value is h[hrow] itself
   const int* net_drv;    // [N]: driver row of a net, < 0: none
   int net_row0, n_net, cell_row0, n_cell;
-  float *A, *LSE;
-  const unsigned short *w1, *w2;
-  const float *b1, *b2;
-  float* hid_out;
-  long long ldhid;
-  int hid16;                   // mask / hid_out hold bf16
-  int relu;
-  const unsigned char* active;
-  int cell_tiles;
-};
-
-// Forward-only form (KEEP = false, mmft_level_fwd_slots_infer), as LevelFwdInferArgs
-struct LevelSlotsInferArgs {
-  float* h;
-  const float* pre;
-  long long ld;
-  const int* slots;
-  const int* net_drv;
-  int net_row0, n_net, cell_row0, n_cell;
   const unsigned short *w1, *w2;
   const float *b1, *b2;
   int relu;
   const unsigned char* active;
-  int cell_tiles;
+  int cell_tiles;        // set by the launcher
 };
 
 template <bool KEEP>
-using LevelSlotsArgsOf = typename std::conditional<KEEP, LevelSlotsArgs, LevelSlotsInferArgs>::type;
+struct LevelSlotsArgs : LevelSlotsCommon, Kept<KEEP> {};
 
 template <int RB, bool KEEP>
-__global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgsOf<KEEP> a) {
+__global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs<KEEP> a) {
   // RB row blocks of 16 cell rows per workgroup: thread group g gathers rows g, g + 16, ..; with RB = 2 half as many workgroups
   // fetch the 128 KB of packed weights (64 MB of L2 traffic per launch at RB = 1)
   constexpr int BM = 16 * RB;
@@ -702,6 +673,9 @@ __global__ void __launch_bounds__(256) pack_bf16_kernel(const float* __restrict_
 
 using namespace mmft;
 
+// the alignment rule of an optional pointer (and of its row pitch, in elements of 4 bytes)
+static bool opt_aligned16(const void* p, long long ld = 0) { return !p || (aligned16(p) && ld % 4 == 0); }
+
 extern "C" int mmft_pack_bf16(const float* src, long long ld, int R, int C, void* dst, int transpose, int device,
                               void* stream) {
   MMFT_REQUIRE(src && dst && R > 0 && C > 0 && ld >= C, "pack_bf16: bad args");
@@ -723,10 +697,10 @@ extern "C" int mmft_mlp2_rows_bf16(const float* x1, long long ldx1, const int* r
   }
   MMFT_REQUIRE(n >= 0, "mlp2_rows_bf16: negative row count");
   MMFT_REQUIRE(ldx1 % 4 == 0 && ldout % 4 == 0 && aligned16(x1) && aligned16(out) && aligned16(w1_bf16) && aligned16(w2_bf16) &&
-                   (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)),
+                   opt_aligned16(b1) && opt_aligned16(b2),
                "mlp2_rows_bf16: operands must be 16-byte aligned");
-  MMFT_REQUIRE(!mask || (ldmask % 4 == 0 && aligned16(mask)), "mlp2_rows_bf16: mask alignment");
-  MMFT_REQUIRE(!hid_out || (ldhid % 4 == 0 && aligned16(hid_out)), "mlp2_rows_bf16: hid_out alignment");
+  MMFT_REQUIRE(opt_aligned16(mask, ldmask), "mlp2_rows_bf16: mask alignment");
+  MMFT_REQUIRE(opt_aligned16(hid_out, ldhid), "mlp2_rows_bf16: hid_out alignment");
   if (n == 0) return MMFT_OK;
   DeviceGuard dg(device);
   Mlp2Bf16Args a{x1, ldx1, rows, n, (const unsigned short*)w1_bf16, b1, (const unsigned short*)w2_bf16, b2, mask, ldmask,
@@ -737,33 +711,46 @@ extern "C" int mmft_mlp2_rows_bf16(const float* x1, long long ldx1, const int* r
   return check_launch("mlp2_rows_bf16");
 }
 
+// ---- the two fused forward level kernels: every host-side rule of a kernel is stated once, for its training form and its
+// forward-only form alike (KEEP as in the kernels); `a.cell_tiles` is filled in here
+static bool kept_given(const Kept<true>& k) { return k.A && k.LSE; }
+static bool kept_given(const Kept<false>&) { return true; }
+static bool kept_aligned(const Kept<true>& k) { return opt_aligned16(k.A) && opt_aligned16(k.LSE) && opt_aligned16(k.hid_out, k.ldhid); }
+static bool kept_aligned(const Kept<false>&) { return true; }
+static double level_mlp_flops(int n_cell) { return 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2); }
+
+template <bool KEEP>
+static int launch_level_fwd_bf16(LevelFwdArgs<KEEP> a, int D, long long alg_bytes, int device, void* stream) {
+  constexpr const char* fn = KEEP ? "level_fwd_bf16" : "level_fwd_bf16_infer";
+  MMFT_REQUIRE(D == L2_K1, "%s: D must be %d", fn, L2_K1);
+  MMFT_REQUIRE(a.n_net >= 0 && a.n_cell >= 0 && a.net_row0 >= 0 && a.cell_row0 >= 0, "%s: negative row count / offset", fn);
+  if (a.n_net + a.n_cell == 0) return MMFT_OK;
+  MMFT_REQUIRE(a.h && a.pre && a.in_ptr && a.ic_ptr && (a.n_cell == 0 || (kept_given(a) && a.w1 && a.w2)), "%s: null pointer", fn);
+  MMFT_REQUIRE(a.ld >= D && a.ld % 4 == 0 && aligned16(a.h) && aligned16(a.pre) && kept_aligned(a) && opt_aligned16(a.w1) &&
+                   opt_aligned16(a.w2) && opt_aligned16(a.b1) && opt_aligned16(a.b2),
+               "%s: operands must be 16-byte aligned", fn);
+  DeviceGuard dg(device);
+  constexpr int LV_BM = 16;
+  a.cell_tiles = cdiv(a.n_cell, LV_BM);
+  int net_blocks = cdiv((long long)a.n_net * 32, 512);
+  if (net_blocks > 1024) net_blocks = 1024;
+  MMFT_LAUNCH(KEEP ? "level_fwd_bf16_kernel" : "level_fwd_bf16_infer_kernel", level_mlp_flops(a.n_cell),
+              alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<KEEP>, dim3(a.cell_tiles + net_blocks), dim3(512),
+              (hipStream_t)stream, a);
+  return check_launch(fn);
+}
+
 extern "C" int mmft_level_fwd_bf16(float* h, const float* pre, long long ld, int D, const int* in_net_indptr,
                                    const int* in_net_indices, const int* in_cell_indptr, const int* in_cell_indices,
                                    int net_row0, int n_net, const int* cell_rows, int cell_row0, int n_cell, float* A,
                                    float* LSE, const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2,
                                    float* hid_out, long long ldhid, int relu, const unsigned char* active,
                                    const int* in_cell_driver, long long alg_bytes, int hid_bf16, int device, void* stream) {
-  MMFT_REQUIRE(D == L2_K1, "level_fwd_bf16: D must be %d", L2_K1);
-  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_bf16: negative row count / offset");
-  if (n_net + n_cell == 0) return MMFT_OK;
-  MMFT_REQUIRE(h && pre && in_net_indptr && in_cell_indptr && (n_cell == 0 || (A && LSE && w1_bf16 && w2_bf16)),
-               "level_fwd_bf16: null pointer");
-  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && (!A || aligned16(A)) && (!LSE || aligned16(LSE)) &&
-                   (!w1_bf16 || aligned16(w1_bf16)) && (!w2_bf16 || aligned16(w2_bf16)) && (!b1 || aligned16(b1)) &&
-                   (!b2 || aligned16(b2)) && (!hid_out || (aligned16(hid_out) && ldhid % 4 == 0)),
-               "level_fwd_bf16: operands must be 16-byte aligned");
-  DeviceGuard dg(device);
-  constexpr int LV_BM = 16;
-  const int tiles = cdiv(n_cell, LV_BM);
-  int net_blocks = cdiv((long long)n_net * 32, 512);
-  if (net_blocks > 1024) net_blocks = 1024;
-  LevelFwdArgs a{h, pre, ld, in_net_indptr, in_net_indices, in_cell_indptr, in_cell_indices, in_cell_driver, net_row0, n_net, cell_rows,
-                 cell_row0, n_cell, A, LSE, (const unsigned short*)w1_bf16, (const unsigned short*)w2_bf16, b1, b2, hid_out,
-                 ldhid, hid_bf16 ? 1 : 0, relu, active, tiles};
-  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  MMFT_LAUNCH("level_fwd_bf16_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<true>,
-              dim3(tiles + net_blocks), dim3(512), (hipStream_t)stream, a);
-  return check_launch("level_fwd_bf16");
+  return launch_level_fwd_bf16<true>({{h, pre, ld, in_net_indptr, in_net_indices, in_cell_indptr, in_cell_indices, in_cell_driver,
+                                       net_row0, n_net, cell_rows, cell_row0, n_cell, (const unsigned short*)w1_bf16,
+                                       (const unsigned short*)w2_bf16, b1, b2, relu, active, 0},
+                                      {A, LSE, hid_out, ldhid, hid_bf16 ? 1 : 0}},
+                                     D, alg_bytes, device, stream);
 }
 
 /* Forward-only form of mmft_level_fwd_bf16: the same h, nothing kept for a reverse sweep (level_fwd_bf16_kernel<false>). */
@@ -773,26 +760,11 @@ extern "C" int mmft_level_fwd_bf16_infer(float* h, const float* pre, long long l
                                          const void* w1_bf16, const float* b1, const void* w2_bf16, const float* b2, int relu,
                                          const unsigned char* active, const int* in_cell_driver, long long alg_bytes, int device,
                                          void* stream) {
-  MMFT_REQUIRE(D == L2_K1, "level_fwd_bf16_infer: D must be %d", L2_K1);
-  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_bf16_infer: negative row count / offset");
-  if (n_net + n_cell == 0) return MMFT_OK;
-  MMFT_REQUIRE(h && pre && in_net_indptr && in_cell_indptr && (n_cell == 0 || (w1_bf16 && w2_bf16)),
-               "level_fwd_bf16_infer: null pointer");
-  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && (!w1_bf16 || aligned16(w1_bf16)) &&
-                   (!w2_bf16 || aligned16(w2_bf16)) && (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)),
-               "level_fwd_bf16_infer: operands must be 16-byte aligned");
-  DeviceGuard dg(device);
-  constexpr int LV_BM = 16;
-  const int tiles = cdiv(n_cell, LV_BM);
-  int net_blocks = cdiv((long long)n_net * 32, 512);
-  if (net_blocks > 1024) net_blocks = 1024;
-  LevelFwdInferArgs a{h, pre, ld, in_net_indptr, in_net_indices, in_cell_indptr, in_cell_indices, in_cell_driver, net_row0, n_net,
-                      cell_rows, cell_row0, n_cell, (const unsigned short*)w1_bf16, (const unsigned short*)w2_bf16, b1, b2, relu,
-                      active, tiles};
-  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  MMFT_LAUNCH("level_fwd_bf16_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, level_fwd_bf16_kernel<false>,
-              dim3(tiles + net_blocks), dim3(512), (hipStream_t)stream, a);
-  return check_launch("level_fwd_bf16_infer");
+  return launch_level_fwd_bf16<false>({{h, pre, ld, in_net_indptr, in_net_indices, in_cell_indptr, in_cell_indices, in_cell_driver,
+                                        net_row0, n_net, cell_rows, cell_row0, n_cell, (const unsigned short*)w1_bf16,
+                                        (const unsigned short*)w2_bf16, b1, b2, relu, active, 0},
+                                       {}},
+                                      D, alg_bytes, device, stream);
 }
 
 // Row blocks per workgroup of the slot-form level kernels (both the training and the forward-only form choose here).
@@ -806,32 +778,35 @@ static int level_slots_rb(int n_net, int n_cell) {
   return rb_env ? rb_env : (rows_max >= 32 * 192 ? 2 : 1);
 }
 
+template <bool KEEP>
+static int launch_level_fwd_slots(LevelSlotsArgs<KEEP> a, int D, long long alg_bytes, int device, void* stream) {
+  constexpr const char* fn = KEEP ? "level_fwd_slots" : "level_fwd_slots_infer";
+  MMFT_REQUIRE(D == L2_K1, "%s: D must be %d", fn, L2_K1);
+  MMFT_REQUIRE(a.n_net >= 0 && a.n_cell >= 0 && a.net_row0 >= 0 && a.cell_row0 >= 0, "%s: negative row count / offset", fn);
+  if (a.n_net + a.n_cell == 0) return MMFT_OK;
+  MMFT_REQUIRE(a.h && a.pre && a.slots && a.net_drv && (a.n_cell == 0 || (kept_given(a) && a.w1 && a.w2)), "%s: null pointer", fn);
+  MMFT_REQUIRE(a.ld >= D && a.ld % 4 == 0 && aligned16(a.h) && aligned16(a.pre) && aligned16(a.slots) && kept_aligned(a) &&
+                   opt_aligned16(a.w1) && opt_aligned16(a.w2) && opt_aligned16(a.b1) && opt_aligned16(a.b2),
+               "%s: operands must be 16-byte aligned", fn);
+  DeviceGuard dg(device);
+  // workgroup b takes cell rows and net rows [bm b, bm b + bm): the longer of the two levels sets the grid
+  const bool rb2 = level_slots_rb(a.n_net, a.n_cell) == 2;
+  const int bm = rb2 ? 32 : 16, net_tiles = cdiv(a.n_net, bm);
+  a.cell_tiles = cdiv(a.n_cell, bm);
+  MMFT_LAUNCH(KEEP ? "level_fwd_slots_kernel" : "level_fwd_slots_infer_kernel", level_mlp_flops(a.n_cell),
+              alg_bytes > 0 ? (double)alg_bytes : 0.0, (rb2 ? level_fwd_slots_kernel<2, KEEP> : level_fwd_slots_kernel<1, KEEP>),
+              dim3(a.cell_tiles > net_tiles ? a.cell_tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
+  return check_launch(fn);
+}
+
 extern "C" int mmft_level_fwd_slots(float* h, const float* pre, long long ld, int D, const int* slots, const int* net_driver,
                                     int net_row0, int n_net, int cell_row0, int n_cell, float* A, float* LSE, const void* w1_bf16,
                                     const float* b1, const void* w2_bf16, const float* b2, float* hid_out, long long ldhid, int relu,
                                     const unsigned char* active, long long alg_bytes, int hid_bf16, int device, void* stream) {
-  MMFT_REQUIRE(D == L2_K1, "level_fwd_slots: D must be %d", L2_K1);
-  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_slots: negative row count / offset");
-  if (n_net + n_cell == 0) return MMFT_OK;
-  MMFT_REQUIRE(h && pre && slots && net_driver && (n_cell == 0 || (A && LSE && w1_bf16 && w2_bf16)), "level_fwd_slots: null pointer");
-  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && aligned16(slots) && (!A || aligned16(A)) &&
-                   (!LSE || aligned16(LSE)) && (!w1_bf16 || aligned16(w1_bf16)) && (!w2_bf16 || aligned16(w2_bf16)) &&
-                   (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)) && (!hid_out || (aligned16(hid_out) && ldhid % 4 == 0)),
-               "level_fwd_slots: operands must be 16-byte aligned");
-  DeviceGuard dg(device);
-  const int rb = level_slots_rb(n_net, n_cell);
-  const int bm = rb == 2 ? 32 : 16;
-  const int tiles = cdiv(n_cell, bm), net_tiles = cdiv(n_net, bm);
-  LevelSlotsArgs a{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, A, LSE, (const unsigned short*)w1_bf16,
-                   (const unsigned short*)w2_bf16, b1, b2, hid_out, ldhid, hid_bf16 ? 1 : 0, relu, active, tiles};
-  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  if (rb == 2)
-    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<2, true>),
-                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
-  else
-    MMFT_LAUNCH("level_fwd_slots_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<1, true>),
-                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
-  return check_launch("level_fwd_slots");
+  return launch_level_fwd_slots<true>({{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, (const unsigned short*)w1_bf16,
+                                        (const unsigned short*)w2_bf16, b1, b2, relu, active, 0},
+                                       {A, LSE, hid_out, ldhid, hid_bf16 ? 1 : 0}},
+                                      D, alg_bytes, device, stream);
 }
 
 /* Forward-only form of mmft_level_fwd_slots: the same h, nothing kept for a reverse sweep (level_fwd_slots_kernel<RB, false>). */
@@ -839,27 +814,10 @@ extern "C" int mmft_level_fwd_slots_infer(float* h, const float* pre, long long 
                                           int net_row0, int n_net, int cell_row0, int n_cell, const void* w1_bf16, const float* b1,
                                           const void* w2_bf16, const float* b2, int relu, const unsigned char* active,
                                           long long alg_bytes, int device, void* stream) {
-  MMFT_REQUIRE(D == L2_K1, "level_fwd_slots_infer: D must be %d", L2_K1);
-  MMFT_REQUIRE(n_net >= 0 && n_cell >= 0 && net_row0 >= 0 && cell_row0 >= 0, "level_fwd_slots_infer: negative row count / offset");
-  if (n_net + n_cell == 0) return MMFT_OK;
-  MMFT_REQUIRE(h && pre && slots && net_driver && (n_cell == 0 || (w1_bf16 && w2_bf16)), "level_fwd_slots_infer: null pointer");
-  MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(h) && aligned16(pre) && aligned16(slots) && (!w1_bf16 || aligned16(w1_bf16)) &&
-                   (!w2_bf16 || aligned16(w2_bf16)) && (!b1 || aligned16(b1)) && (!b2 || aligned16(b2)),
-               "level_fwd_slots_infer: operands must be 16-byte aligned");
-  DeviceGuard dg(device);
-  const int rb = level_slots_rb(n_net, n_cell);
-  const int bm = rb == 2 ? 32 : 16;
-  const int tiles = cdiv(n_cell, bm), net_tiles = cdiv(n_net, bm);
-  LevelSlotsInferArgs a{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, (const unsigned short*)w1_bf16,
-                        (const unsigned short*)w2_bf16, b1, b2, relu, active, tiles};
-  const double fl = 2.0 * n_cell * ((double)L2_K1 * L2_HD + (double)L2_HD * L2_D2);
-  if (rb == 2)
-    MMFT_LAUNCH("level_fwd_slots_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<2, false>),
-                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
-  else
-    MMFT_LAUNCH("level_fwd_slots_infer_kernel", fl, alg_bytes > 0 ? (double)alg_bytes : 0.0, (level_fwd_slots_kernel<1, false>),
-                dim3(tiles > net_tiles ? tiles : net_tiles), dim3(512), (hipStream_t)stream, a);
-  return check_launch("level_fwd_slots_infer");
+  return launch_level_fwd_slots<false>({{h, pre, ld, slots, net_driver, net_row0, n_net, cell_row0, n_cell, (const unsigned short*)w1_bf16,
+                                         (const unsigned short*)w2_bf16, b1, b2, relu, active, 0},
+                                        {}},
+                                       D, alg_bytes, device, stream);
 }
 
 /* Reverse sweep of one (cell level l, net level l + 1) pair, see level_bwd_pair_kernel: tiles int32[ntiles][8] (first driver id,
@@ -879,9 +837,8 @@ extern "C" int mmft_level_bwd_pair(float* G, const float* h, const float* A, con
                "level_bwd_pair: null pointer");
   MMFT_REQUIRE(!has_mlp || (w1_bf16 && w2_bf16 && mask), "level_bwd_pair: the MLP part needs both weight packs and the saved hidden rows");
   MMFT_REQUIRE(ld >= D && ld % 4 == 0 && aligned16(G) && aligned16(h) && aligned16(A) && aligned16(LSE) && aligned16(DA) &&
-                   aligned16(cslots) && aligned16(tiles) && aligned16(scratch) && (!w1_bf16 || aligned16(w1_bf16)) &&
-                   (!w2_bf16 || aligned16(w2_bf16)) && (!mask || (aligned16(mask) && ldmask % 4 == 0)) &&
-                   (!hid_out || (aligned16(hid_out) && ldhid % 4 == 0)),
+                   aligned16(cslots) && aligned16(tiles) && aligned16(scratch) && opt_aligned16(w1_bf16) &&
+                   opt_aligned16(w2_bf16) && opt_aligned16(mask, ldmask) && opt_aligned16(hid_out, ldhid),
                "level_bwd_pair: operands must be 16-byte aligned");
   DeviceGuard dg(device);
   LevelBwdPairArgs a{G, h, A, LSE, DA, ld, own_mask, tiles, out_net_indptr, sink_shift, cslots, out_cell_indptr, out_cell_indices,

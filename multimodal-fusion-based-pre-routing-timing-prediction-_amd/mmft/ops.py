@@ -3,6 +3,8 @@
 Every function checks on the host that operand shapes match what the kernels and their grids assume
 before launching, and raises instead of falling back when the inputs are not device fp32 tensors.
 """
+import os
+
 import torch
 from . import lib
 
@@ -11,10 +13,9 @@ ACT_NONE, ACT_RELU, ACT_LEAKY = 0, 1, 2
 POOL_MAX, POOL_AVG = 0, 1
 # rows with more edges than this get a whole workgroup in the level kernels (graph.hip): a cell row's in-edges (forward
 # gather) / a node's out-edges (reverse pull) are a serial chain of dependent loads in one thread group otherwise
-import os as _os
-# rows with more in- / out-edges than this get a whole workgroup (MMFT_HEAVY_IN / MMFT_HEAVY_OUT override, read at import)
-PAIR_HEAVY_IN = int(_os.environ.get('MMFT_HEAVY_IN', '16'))
-PAIR_HEAVY_OUT = int(_os.environ.get('MMFT_HEAVY_OUT', '16'))
+# (MMFT_HEAVY_IN / MMFT_HEAVY_OUT override, read at import)
+PAIR_HEAVY_IN = int(os.environ.get('MMFT_HEAVY_IN', '16'))
+PAIR_HEAVY_OUT = int(os.environ.get('MMFT_HEAVY_OUT', '16'))
 
 
 def _chk(t, name, dtype=torch.float32):
@@ -51,28 +52,20 @@ def _same_hid_dtype(*ts):
     return int(bool(d) and d.pop() == torch.bfloat16)
 
 
-def _launch(name, args):
-    """lib.call, returning the argument list with tensors replaced by their addresses: a caller whose tensors are persistent
-    (the sweep's buffers and static tables) keeps the list and repeats the launch with `relaunch`, skipping this wrapper's
-    checks - the per-level kernels of the drop-in loop are issued eagerly, 63 times per step, and the checks cost more
-    host time than the launch."""
-    lib.call(name, *args)
-    return [a.data_ptr() if torch.is_tensor(a) else a for a in args]
-
-
-class _Recorded:
-    """`_launch` spelled `recorded.call('mmft_x', a, b, ...)`: the form whose argument count the static check of the call sites
-    (tests/test_host_cpu.py) compares with the header."""
+class recorded:
+    """`recorded.call('mmft_x', a, b, ...)` is lib.call, returning the argument list with tensors replaced by their addresses:
+    a caller whose tensors are persistent (the sweep's buffers and static tables) keeps the list and repeats the launch with
+    `relaunch`, skipping the wrapper's checks - the per-level kernels of the drop-in loop are issued eagerly, 63 times per
+    step, and the checks cost more host time than the launch.  Spelled like lib.call, so the static check of the call sites
+    (tests/test_host_cpu.py) compares its argument count with the header."""
     @staticmethod
     def call(name, *args):
-        return _launch(name, list(args))
-
-
-recorded = _Recorded
+        lib.call(name, *args)
+        return [a.data_ptr() if torch.is_tensor(a) else a for a in args]
 
 
 def relaunch(name, raw, dev, stream):
-    """Repeat a launch recorded by `_launch` on the given stream (the last two arguments of every entry point)."""
+    """Repeat a launch recorded by `recorded.call` on the given stream (the last two arguments of every entry point)."""
     lib.call(name, *raw[:-2], dev, stream)
 
 
@@ -93,6 +86,36 @@ def _idx(t, name, n=None):
     if n is not None and t.numel() != n:
         raise ValueError(f'{name}: expected {n} entries, got {t.numel()}')
     return t
+
+
+def _bf16_mat(fn, t, nm, shape):
+    if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
+        raise ValueError(f'{fn}: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+
+
+def _packed_w(fn, w1p, w2p):
+    """The two pre-packed bf16 weights of a 128 -> 256 -> 128 level MLP (pack_bf16; the reverse form's transposed packs have
+    the same shapes)."""
+    _bf16_mat(fn, w1p, 'w1p', (256, 128)); _bf16_mat(fn, w2p, 'w2p', (128, 256))
+
+
+def _like_h(fn, h, pairs, D=None):
+    """h and every (tensor, name) of `pairs` are fp32 row tensors of one shape and row pitch; D: the width the kernel is
+    built for.  Returns N."""
+    for t, nm in ((h, 'h'),) + tuple(pairs):
+        _rows2d(t, nm)
+        if t.shape != h.shape or t.stride(0) != h.stride(0):
+            raise ValueError(f'{fn}: {nm} must have the layout of h')
+    if D is not None and h.shape[1] != D:
+        raise ValueError(f'{fn}: D = {D} only')
+    return h.shape[0]
+
+
+def _own_flags(fn, own, N):
+    if own is not None:
+        _chk(own, 'own', torch.uint8)
+        if own.numel() != N:
+            raise ValueError(f'{fn}: one own-gradient flag per node expected')
 
 
 def act_code(slope_or_none):
@@ -275,8 +298,8 @@ def pack_bf16(w, transpose=False, out=None):
     shape = (C, R) if transpose else (R, C)
     if out is None:
         out = torch.empty(shape, dtype=torch.bfloat16, device=w.device)
-    elif not (out.is_cuda and out.dtype == torch.bfloat16 and tuple(out.shape) == shape and out.is_contiguous()):
-        raise ValueError(f'pack_bf16: out must be a contiguous bf16 CUDA tensor of shape {shape}')
+    else:
+        _bf16_mat('pack_bf16', out, 'out', shape)
     dev, st = lib.stream_args(w)
     lib.call('mmft_pack_bf16', w, w.stride(0), R, C, out, int(transpose), dev, st)
     return out
@@ -285,9 +308,7 @@ def pack_bf16(w, transpose=False, out=None):
 def mlp2_rows_bf16(x1, rows, w1p, b1, w2p, b2, out, mask=None, hid_out=None, add_act=False, relu_out=False, active=None):
     """Fused Linear-ReLU-Linear over gathered rows with pre-packed bf16 weights (mmft_mlp2_rows_bf16)."""
     _rows2d(x1, 'x1'); _rows2d(out, 'out'); _idx(rows, 'rows')
-    for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'mlp2_rows_bf16: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+    _packed_w('mlp2_rows_bf16', w1p, w2p)
     if x1.shape[1] != 128 or out.shape[1] != 128 or out.shape[0] != x1.shape[0]:
         raise ValueError('mlp2_rows_bf16: 128 -> 256 -> 128 over node-indexed buffers')
     for t, nm in ((mask, 'mask'), (hid_out, 'hid_out')):
@@ -303,59 +324,27 @@ def mlp2_rows_bf16(x1, rows, w1p, b1, w2p, b2, out, mask=None, hid_out=None, add
     return out
 
 
-def _level_fwd_bf16_operands(fn, h, pre, kept, in_net, in_cell, net_range, cell_rows, w1p, w2p):
-    """Checks shared by level_fwd_bf16 and its forward-only twin; `kept` = the (tensor, name) pairs with the layout of h."""
-    for t, nm in ((h, 'h'), (pre, 'pre')) + tuple(kept):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'{fn}: {nm} must have the layout of h')
-    N = h.shape[0]
-    if h.shape[1] != 128:
-        raise ValueError(f'{fn}: D = 128 only')
+def _level_fwd_operands(fn, h, pre, kept, w1p, w2p):
+    """What the four fused forward level wrappers check alike; kept = (A, LSE, hid_out), or None in the forward-only form.
+    Returns N."""
+    N = _like_h(fn, h, ((pre, 'pre'),) + (((kept[0], 'A'), (kept[1], 'LSE')) if kept else ()), D=128)
+    _packed_w(fn, w1p, w2p)
+    if kept:
+        _hid2d(kept[2], 'hid_out')
+        if kept[2].shape != (N, 256):
+            raise ValueError(f'{fn}: hid_out must be [N, 256]')
+    return N
+
+
+def _level_csr_rows(N, in_net, in_cell, net_range, cell_rows):
+    """Index form of a level pair: the two in-edge CSRs, the net rows as a range and the cell rows as any row spec."""
     _csr(in_net[0], in_net[1], N, 'in_net'); _csr(in_cell[0], in_cell[1], N, 'in_cell')
     _, nrow0, nn = _rowspec(net_range if net_range is not None else (0, 0), N, 'net_range')
-    ct, crow0, nc = _rowspec(cell_rows, N, 'cell_rows')
-    for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'{fn}: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
-    return N, nrow0, nn, ct, crow0, nc
+    return (nrow0, nn) + _rowspec(cell_rows, N, 'cell_rows')
 
 
-def level_fwd_bf16(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
-                   alg_bytes=0, in_cell_driver=None):
-    """Fused forward level kernel of the bf16 mode (mmft_level_fwd_bf16): folded gather + fc_cell_neigh in one launch."""
-    N, nrow0, nn, ct, crow0, nc = _level_fwd_bf16_operands('level_fwd_bf16', h, pre, ((A, 'A'), (LSE, 'LSE')), in_net, in_cell,
-                                                           net_range, cell_rows, w1p, w2p)
-    _hid2d(hid_out, 'hid_out')
-    if hid_out.shape != (N, 256):
-        raise ValueError('level_fwd_bf16: hid_out must be [N, 256]')
-    dev, st = lib.stream_args(h)
-    lib.call('mmft_level_fwd_bf16', h, pre, h.stride(0), 128, in_net[0], in_net[1], in_cell[0], in_cell[1], nrow0, nn, ct, crow0,
-             nc, A, LSE, w1p, b1, w2p, b2, hid_out, hid_out.stride(0), int(relu), _active(active, N),
-             _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), _same_hid_dtype(hid_out), dev, st)
-
-
-def level_fwd_bf16_infer(h, pre, in_net, in_cell, net_range, cell_rows, w1p, b1, w2p, b2, relu=True, active=None, alg_bytes=0,
-                         in_cell_driver=None):
-    """Forward-only twin of level_fwd_bf16 (mmft_level_fwd_bf16_infer): the same h, nothing kept for a reverse sweep.  Returns
-    the recorded launch (relaunch)."""
-    N, nrow0, nn, ct, crow0, nc = _level_fwd_bf16_operands('level_fwd_bf16_infer', h, pre, (), in_net, in_cell, net_range, cell_rows,
-                                                           w1p, w2p)
-    dev, st = lib.stream_args(h)
-    return recorded.call('mmft_level_fwd_bf16_infer', h, pre, h.stride(0), 128, in_net[0], in_net[1], in_cell[0], in_cell[1], nrow0,
-                         nn, ct, crow0, nc, w1p, b1, w2p, b2, int(relu), _active(active, N),
-                         _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), dev, st)
-
-
-def _level_fwd_slots_operands(fn, h, pre, kept, slots, net_driver, net_range, cell_range, w1p, w2p):
-    """Checks shared by level_fwd_slots and its forward-only twin."""
-    for t, nm in ((h, 'h'), (pre, 'pre')) + tuple(kept):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'{fn}: {nm} must have the layout of h')
-    N = h.shape[0]
-    if h.shape[1] != 128:
-        raise ValueError(f'{fn}: D = 128 only')
+def _level_slot_rows(fn, N, slots, net_driver, net_range, cell_range):
+    """Slot form of a level pair: the static tables of PinGraph.level_slots and two row ranges."""
     for t, nm, shape in ((slots, 'slots', (N, 8)), (net_driver, 'net_driver', (N,))):
         if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.int32 and tuple(t.shape) == shape and t.is_contiguous()):
             raise ValueError(f'{fn}: {nm} must be a contiguous int32 CUDA tensor of shape {shape}')
@@ -363,47 +352,57 @@ def _level_fwd_slots_operands(fn, h, pre, kept, slots, net_driver, net_range, ce
     crow0, nc = cell_range
     if min(nrow0, nn, crow0, nc) < 0 or nrow0 + nn > N or crow0 + nc > N:
         raise ValueError(f'{fn}: row range outside the graph')
-    for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
-        if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-            raise ValueError(f'{fn}: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
-    return N, nrow0, nn, crow0, nc
+    return nrow0, nn, crow0, nc
+
+
+def level_fwd_bf16(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
+                   alg_bytes=0, in_cell_driver=None):
+    """Fused forward level kernel of the bf16 mode (mmft_level_fwd_bf16): folded gather + fc_cell_neigh in one launch.
+    Returns the recorded launch (relaunch), as the three wrappers below do."""
+    N = _level_fwd_operands('level_fwd_bf16', h, pre, (A, LSE, hid_out), w1p, w2p)
+    nrow0, nn, ct, crow0, nc = _level_csr_rows(N, in_net, in_cell, net_range, cell_rows)
+    dev, st = lib.stream_args(h)
+    return recorded.call('mmft_level_fwd_bf16', h, pre, h.stride(0), 128, in_net[0], in_net[1], in_cell[0], in_cell[1], nrow0, nn,
+                         ct, crow0, nc, A, LSE, w1p, b1, w2p, b2, hid_out, hid_out.stride(0), int(relu), _active(active, N),
+                         _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), _same_hid_dtype(hid_out), dev, st)
+
+
+def level_fwd_bf16_infer(h, pre, in_net, in_cell, net_range, cell_rows, w1p, b1, w2p, b2, relu=True, active=None, alg_bytes=0,
+                         in_cell_driver=None):
+    """Forward-only twin of level_fwd_bf16 (mmft_level_fwd_bf16_infer): the same h, nothing kept for a reverse sweep."""
+    N = _level_fwd_operands('level_fwd_bf16_infer', h, pre, None, w1p, w2p)
+    nrow0, nn, ct, crow0, nc = _level_csr_rows(N, in_net, in_cell, net_range, cell_rows)
+    dev, st = lib.stream_args(h)
+    return recorded.call('mmft_level_fwd_bf16_infer', h, pre, h.stride(0), 128, in_net[0], in_net[1], in_cell[0], in_cell[1], nrow0,
+                         nn, ct, crow0, nc, w1p, b1, w2p, b2, int(relu), _active(active, N),
+                         _edge_drivers(in_cell_driver, in_cell[1]), int(alg_bytes), dev, st)
 
 
 def level_fwd_slots(h, pre, slots, net_driver, net_range, cell_range, A, LSE, w1p, b1, w2p, b2, hid_out, relu=True, active=None,
                     alg_bytes=0):
     """Slot-table form of level_fwd_bf16 (mmft_level_fwd_slots): contiguous net / cell row ranges, fan-in <= 4."""
-    N, nrow0, nn, crow0, nc = _level_fwd_slots_operands('level_fwd_slots', h, pre, ((A, 'A'), (LSE, 'LSE')), slots, net_driver,
-                                                        net_range, cell_range, w1p, w2p)
-    _hid2d(hid_out, 'hid_out')
-    if hid_out.shape != (N, 256):
-        raise ValueError('level_fwd_slots: hid_out must be [N, 256]')
+    N = _level_fwd_operands('level_fwd_slots', h, pre, (A, LSE, hid_out), w1p, w2p)
+    nrow0, nn, crow0, nc = _level_slot_rows('level_fwd_slots', N, slots, net_driver, net_range, cell_range)
     dev, st = lib.stream_args(h)
-    return _launch('mmft_level_fwd_slots', [h, pre, h.stride(0), 128, slots, net_driver, nrow0, nn, crow0, nc, A, LSE, w1p, b1, w2p, b2,
-                                            hid_out, hid_out.stride(0), int(relu), _active(active, N), int(alg_bytes),
-                                            _same_hid_dtype(hid_out), dev, st])
+    return recorded.call('mmft_level_fwd_slots', h, pre, h.stride(0), 128, slots, net_driver, nrow0, nn, crow0, nc, A, LSE, w1p, b1,
+                         w2p, b2, hid_out, hid_out.stride(0), int(relu), _active(active, N), int(alg_bytes),
+                         _same_hid_dtype(hid_out), dev, st)
 
 
 def level_fwd_slots_infer(h, pre, slots, net_driver, net_range, cell_range, w1p, b1, w2p, b2, relu=True, active=None, alg_bytes=0):
     """Forward-only twin of level_fwd_slots (mmft_level_fwd_slots_infer): the same h, nothing kept for a reverse sweep."""
-    N, nrow0, nn, crow0, nc = _level_fwd_slots_operands('level_fwd_slots_infer', h, pre, (), slots, net_driver, net_range, cell_range,
-                                                        w1p, w2p)
+    N = _level_fwd_operands('level_fwd_slots_infer', h, pre, None, w1p, w2p)
+    nrow0, nn, crow0, nc = _level_slot_rows('level_fwd_slots_infer', N, slots, net_driver, net_range, cell_range)
     dev, st = lib.stream_args(h)
     return recorded.call('mmft_level_fwd_slots_infer', h, pre, h.stride(0), 128, slots, net_driver, nrow0, nn, crow0, nc, w1p, b1, w2p,
                          b2, int(relu), _active(active, N), int(alg_bytes), dev, st)
 
 
 def level_bwd_pair(G, h, A, LSE, DA, own, tiles, ntiles, out_net_indptr, sink_shift, cslots, out_cell, scratch, counters, w1p, w2p,
-                   HN, DHN, relu=True,
-                   has_mlp=True, alg_bytes=0):
+                   HN, DHN, relu=True, has_mlp=True, alg_bytes=0):
     """Reverse sweep of one (cell level, net level above it) pair in one launch (mmft_level_bwd_pair); the tables come from
     PinGraph.level_bwd_pairs, which checks the layout the kernel assumes."""
-    for t, nm in ((G, 'G'), (h, 'h'), (A, 'A'), (LSE, 'LSE'), (DA, 'DA')):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'level_bwd_pair: {nm} must have the layout of h')
-    N = h.shape[0]
-    if h.shape[1] != 128:
-        raise ValueError('level_bwd_pair: D = 128 only')
+    N = _like_h('level_bwd_pair', h, ((G, 'G'), (A, 'A'), (LSE, 'LSE'), (DA, 'DA')), D=128)
     if not (torch.is_tensor(tiles) and tiles.is_cuda and tiles.dtype == torch.int32 and tiles.dim() == 2 and tiles.shape[1] == 8
             and tiles.is_contiguous() and tiles.shape[0] == ntiles):
         raise ValueError('level_bwd_pair: tiles must be a contiguous int32 CUDA tensor [ntiles, 8]')
@@ -418,14 +417,9 @@ def level_bwd_pair(G, h, A, LSE, DA, own, tiles, ntiles, out_net_indptr, sink_sh
     if out_net_indptr.numel() != N + 1:
         raise ValueError('level_bwd_pair: out_net_indptr must have N + 1 entries')
     _csr(out_cell[0], out_cell[1], N, 'out_cell')
-    if own is not None:
-        _chk(own, 'own', torch.uint8)
-        if own.numel() != N:
-            raise ValueError('level_bwd_pair: one own-gradient flag per node expected')
+    _own_flags('level_bwd_pair', own, N)
     if has_mlp:
-        for t, nm, shape in ((w1p, 'w1p', (256, 128)), (w2p, 'w2p', (128, 256))):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.bfloat16 and tuple(t.shape) == shape and t.is_contiguous()):
-                raise ValueError(f'level_bwd_pair: {nm} must be a contiguous bf16 CUDA tensor of shape {shape}')
+        _packed_w('level_bwd_pair', w1p, w2p)             # W2g^T, W1g^T
         for t, nm in ((HN, 'HN'), (DHN, 'DHN')):
             if t is None and nm == 'DHN':
                 continue
@@ -433,12 +427,12 @@ def level_bwd_pair(G, h, A, LSE, DA, own, tiles, ntiles, out_net_indptr, sink_sh
             if tuple(t.shape) != (N, 256):
                 raise ValueError(f'level_bwd_pair: {nm} must be [N, 256]')
     dev, st = lib.stream_args(h)
-    return _launch('mmft_level_bwd_pair', [G, h, A, LSE, DA, h.stride(0), 128, N, own, tiles, int(ntiles), out_net_indptr, int(sink_shift),
-                                           cslots, out_cell[0], out_cell[1], scratch, counters, int(relu), int(bool(has_mlp)),
-                                           w1p if has_mlp else None, w2p if has_mlp else None, HN if has_mlp else None,
-                                           HN.stride(0) if has_mlp else 0, DHN if has_mlp else None,
-                                           DHN.stride(0) if (has_mlp and DHN is not None) else 0, int(alg_bytes),
-                                           _same_hid_dtype(HN, DHN) if has_mlp else 0, dev, st])
+    return recorded.call('mmft_level_bwd_pair', G, h, A, LSE, DA, h.stride(0), 128, N, own, tiles, int(ntiles), out_net_indptr,
+                         int(sink_shift), cslots, out_cell[0], out_cell[1], scratch, counters, int(relu), int(bool(has_mlp)),
+                         w1p if has_mlp else None, w2p if has_mlp else None, HN if has_mlp else None,
+                         HN.stride(0) if has_mlp else 0, DHN if has_mlp else None,
+                         DHN.stride(0) if (has_mlp and DHN is not None) else 0, int(alg_bytes),
+                         _same_hid_dtype(HN, DHN) if has_mlp else 0, dev, st)
 
 
 def mlp2_feat_fusable(fin, HD, D2):
@@ -643,20 +637,13 @@ def target_rows_end(idx, flags):
 
 def level_bwd_pull(G, h, rows, out_net, out_net_w, out_cell, A, LSE, DA, relu=True, alg_bytes=0, own=None, heavy=None,
                    heavy_thresh=PAIR_HEAVY_OUT, active=None):
-    for t, nm in ((G, 'G'), (h, 'h'), (A, 'A'), (LSE, 'LSE'), (DA, 'DA')):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'level_bwd_pull: {nm} must have the layout of h')
-    N = h.shape[0]
+    N = _like_h('level_bwd_pull', h, ((G, 'G'), (A, 'A'), (LSE, 'LSE'), (DA, 'DA')))
     _csr(out_net[0], out_net[1], N, 'out_net'); _csr(out_cell[0], out_cell[1], N, 'out_cell')
     _chk(out_net_w, 'out_net_w')
     if out_net_w.numel() != out_net[1].numel() or not out_net_w.is_contiguous():
         raise ValueError('level_bwd_pull: one weight per out-net edge expected')
     rt, row0, n = _rowspec(rows, N, 'rows')
-    if own is not None:
-        _chk(own, 'own', torch.uint8)
-        if own.numel() != N:
-            raise ValueError('level_bwd_pull: one own-gradient flag per node expected')
+    _own_flags('level_bwd_pull', own, N)
     dev, st = lib.stream_args(h)
     if heavy is not None:
         _idx(heavy, 'heavy')
@@ -666,16 +653,11 @@ def level_bwd_pull(G, h, rows, out_net, out_net_w, out_cell, A, LSE, DA, relu=Tr
     return G
 
 
-
-
 def pair_fwd_gather(h, pre, in_net, in_cell, net_range, cell_rows, A, LSE, relu=True, heavy=None, heavy_thresh=PAIR_HEAVY_IN,
                     alg_bytes=0, active=None, in_cell_driver=None):
     """Folded forward gather of one (net level, cell level) pair: see mmft_pair_fwd_gather in include/mmft.h.
     net_range = (row0, n); cell_rows = int32 tensor | (row0, n) | None (no cell level)."""
-    _rows2d(h, 'h'); _rows2d(pre, 'pre')
-    N = h.shape[0]
-    if pre.shape != h.shape or pre.stride(0) != h.stride(0):
-        raise ValueError('pair_fwd_gather: pre must have the layout of h')
+    N = _like_h('pair_fwd_gather', h, ((pre, 'pre'),))
     _csr(in_net[0], in_net[1], N, 'in_net'); _csr(in_cell[0], in_cell[1], N, 'in_cell')
     _, nrow0, nn = _rowspec(net_range if net_range is not None else (0, 0), N, 'net_range')
     if cell_rows is None:
@@ -716,11 +698,7 @@ def seg_attn_fwd(h, key, c12, in_csr, rows, A, alpha):
 
 
 def level_bwd_pull_attn(G, h, rows, out_net, out_net_w, out_cell, o2i, alpha, DA, relu=True, own=None):
-    for t, nm in ((G, 'G'), (h, 'h'), (DA, 'DA')):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'level_bwd_pull_attn: {nm} must have the layout of h')
-    N = h.shape[0]
+    N = _like_h('level_bwd_pull_attn', h, ((G, 'G'), (DA, 'DA')))
     _csr(out_net[0], out_net[1], N, 'out_net'); _csr(out_cell[0], out_cell[1], N, 'out_cell')
     _idx(o2i, 'o2i', out_cell[1].numel()); _chk(alpha, 'alpha'); _chk(out_net_w, 'out_net_w')
     if alpha.numel() != out_cell[1].numel() or out_net_w.numel() != out_net[1].numel():
@@ -735,11 +713,7 @@ def level_bwd_pull_attn(G, h, rows, out_net, out_net_w, out_cell, o2i, alpha, DA
 
 
 def seg_attn_bwd_scores(DA, h, A, alpha, key, c12, in_csr, rows, dcp):
-    for t, nm in ((DA, 'DA'), (h, 'h'), (A, 'A')):
-        _rows2d(t, nm)
-        if t.shape != h.shape or t.stride(0) != h.stride(0):
-            raise ValueError(f'seg_attn_bwd_scores: {nm} must have the layout of h')
-    N = h.shape[0]
+    N = _like_h('seg_attn_bwd_scores', h, ((DA, 'DA'), (A, 'A')))
     _csr(in_csr[0], in_csr[1], N, 'in_csr'); _chk(dcp, 'dcp')
     if tuple(dcp.shape) != (N, 2) or not dcp.is_contiguous():
         raise ValueError('seg_attn_bwd_scores: dcp must be a contiguous [N, 2] tensor')

@@ -562,6 +562,18 @@ def _pinned(st, i, build):
     return build(st.level_lists) if rec is None else rec.keep[i]
 
 
+def _recorded(prep, key, name, dev, stream, build):
+    """The launch of entry point `name` that the sweep record holds under `key` (prep = its `calls`), issued again on `stream`;
+    the first time build() - the checked ops wrapper - issues it and what it returns is kept.  prep None: no record, build()."""
+    rec = prep.get(key) if prep is not None else None
+    if rec is not None:
+        ops.relaunch(name, rec, dev, stream)
+    elif prep is not None:
+        prep[key] = build()
+    else:
+        build()
+
+
 class SweepFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, state, level_rows, tix, c12, anchor, *params):
@@ -670,42 +682,25 @@ class SweepFn(torch.autograd.Function):
                 # hidden row kept for the reverse sweep (4 Hd or 2 Hd)
                 kept_bytes = level_rows[level_id].numel() * (8 * st.D + (2 if st.hid16 else 4) * st.Hd) if (meta_c and has_cell) else 0
                 level_bytes = (meta_n['bytes_mean'] if meta_n else 0) + (meta_c['bytes_softmax'] if meta_c else 0) + kept_bytes
-                if fused and slot_tabs is not None and fold[level_id]['range'] is not None and slot_tabs[2][level_id] <= 4 and \
-                        (fold[net_l]['range'] is not None or not fold[net_l]['n']):
-                    # ... with the static slot table instead of the per-edge index chain, net rows inside the cell workgroups
-                    if fwd_only:
-                        # (a key of its own: a training step after this sweep must not re-issue a launch that leaves A / LSE stale;
-                        #  bytes: A and LSE - which happen to weigh what h read + written does - and the hidden row are not moved)
-                        rec = prep.get(('fi', level_id)) if prep is not None else None
-                        if rec is not None:
-                            ops.relaunch('mmft_level_fwd_slots_infer', rec, dev_, stream_)
-                            continue
-                        rec = ops.level_fwd_slots_infer(st.h, st.PRE, slot_tabs[0], slot_tabs[1], fold[net_l]['range'] or (0, 0),
-                                                        fold[level_id]['range'], st.wpack[0], b1g, st.wpack[1], b2g, relu=st.relu,
-                                                        active=st.active, alg_bytes=level_bytes - kept_bytes)
-                        if prep is not None:
-                            prep[('fi', level_id)] = rec
-                        continue
-                    rec = prep.get(('f', level_id)) if prep is not None else None
-                    if rec is not None:
-                        ops.relaunch('mmft_level_fwd_slots', rec, dev_, stream_)
-                        continue
-                    rec = ops.level_fwd_slots(st.h, st.PRE, slot_tabs[0], slot_tabs[1], fold[net_l]['range'] or (0, 0), fold[level_id]['range'],
-                                              st.A, st.LSE, st.wpack[0], b1g, st.wpack[1], b2g, st.HN, relu=st.relu, active=st.active,
-                                              alg_bytes=level_bytes)
-                    if prep is not None:
-                        prep[('f', level_id)] = rec
-                    continue
-                if fused and fwd_only:
-                    ops.level_fwd_bf16_infer(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.wpack[0], b1g,
-                                             st.wpack[1], b2g, relu=st.relu, active=st.active, in_cell_driver=drv,
-                                             alg_bytes=level_bytes - kept_bytes)
-                    continue
                 if fused:
-                    # bf16 mode: gather + fc_cell_neigh of the pair in ONE launch
-                    ops.level_fwd_bf16(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow, st.A, st.LSE,
-                                       st.wpack[0], b1g, st.wpack[1], b2g, st.HN, relu=st.relu, active=st.active, in_cell_driver=drv,
-                                       alg_bytes=level_bytes)
+                    # bf16 mode: gather + fc_cell_neigh of the pair in ONE launch, its form picked here.  Slot form: the static slot
+                    # table instead of the per-edge index chain, net rows inside the cell workgroups; only its launches are recorded.
+                    # Forward-only form: a key of its own (a training step after this sweep must not re-issue a launch that leaves
+                    # A / LSE stale); bytes: A and LSE - which happen to weigh what h read + written does - and the hidden row are
+                    # not moved
+                    slot = slot_tabs is not None and fold[level_id]['range'] is not None and slot_tabs[2][level_id] <= 4 and \
+                        (fold[net_l]['range'] is not None or not fold[net_l]['n'])
+                    fn = (ops.level_fwd_slots_infer if slot else ops.level_fwd_bf16_infer) if fwd_only else \
+                        (ops.level_fwd_slots if slot else ops.level_fwd_bf16)
+
+                    def build():
+                        net_range = fold[net_l]['range'] or (0, 0)
+                        tabs = (slot_tabs[0], slot_tabs[1], net_range, fold[level_id]['range']) if slot else (in_net, in_cell, net_range, crow)
+                        kept, hid = ((), ()) if fwd_only else ((st.A, st.LSE), (st.HN,))
+                        opts = {} if slot else {'in_cell_driver': drv}
+                        return fn(st.h, st.PRE, *tabs, *kept, st.wpack[0], b1g, st.wpack[1], b2g, *hid, relu=st.relu, active=st.active,
+                                  alg_bytes=level_bytes - (kept_bytes if fwd_only else 0), **opts)
+                    _recorded(prep if slot else None, ('fi' if fwd_only else 'f', level_id), 'mmft_' + fn.__name__, dev_, stream_, build)
                     continue
                 # (forward-only: A is the transient between the two launches, LSE is not written, the hidden rows are not stored)
                 ops.pair_fwd_gather(st.h, st.PRE, in_net, in_cell, fold[net_l]['range'] or (0, 0), crow,
@@ -793,15 +788,9 @@ class SweepFn(torch.autograd.Function):
                     mn = st.level_meta[cell_l + 1] if (st.level_meta and cell_l + 1 < len(st.level_meta)) else None
                     nb = (mc['bytes_pull'] if mc else 0) + (mn['bytes_pull'] if mn else 0) + \
                         (pr['n_cell'] * (8 * st.D + (4 if st.hid16 else 8) * st.Hd) if cell_l > 0 else 0)
-                    rec = prep.get(('b', cell_l)) if prep is not None else None
-                    if rec is not None:
-                        ops.relaunch('mmft_level_bwd_pair', rec, dev_b, stream_b)
-                        continue
-                    rec = ops.level_bwd_pair(st.G, st.h, st.A, st.LSE, st.DA, own, pr['tiles'], pr['ntiles'], out_net[0], pr['sink_shift'],
-                                             cslots, out_cell, pscratch, pcounters, st.wpack[2], st.wpack[3], st.HN, st.DHN, relu=st.relu,
-                                             has_mlp=cell_l > 0, alg_bytes=nb)
-                    if prep is not None:
-                        prep[('b', cell_l)] = rec
+                    _recorded(prep, ('b', cell_l), 'mmft_level_bwd_pair', dev_b, stream_b, lambda: ops.level_bwd_pair(
+                        st.G, st.h, st.A, st.LSE, st.DA, own, pr['tiles'], pr['ntiles'], out_net[0], pr['sink_shift'], cslots, out_cell,
+                        pscratch, pcounters, st.wpack[2], st.wpack[3], st.HN, st.DHN, relu=st.relu, has_mlp=cell_l > 0, alg_bytes=nb))
                     continue
             if not rows.numel():
                 continue
