@@ -1,9 +1,9 @@
 // bf16-storage element-wise / reduction kernels of the layout U-Net (bf16 math mode): train-mode BatchNorm + ReLU
 // (src/Unet.py:17-18,20-21) split as  statistics (conv epilogue, unet16_conv.hip) -> finalize -> apply (+ 2x2 pooling of
 // src/Unet.py:33-36 in the same pass, + the skip half of the concatenation of src/Unet.py:67 written in place),
-// its backward (partial sums -> finalize -> apply), the pooling backward fused with the skip-connection gradient add, and
-// OutConv (src/Unet.py:71-82).  All tensors bf16 NHWC in HBM (half the bytes of the fp32 kernels of cnn.hip), statistics
-// fp32, combined in fp64 in a fixed order (bitwise reproducible).
+// its backward (partial sums -> finalize -> apply) and the pooling backward fused with the skip-connection gradient add.
+// All tensors bf16 NHWC in HBM (half the bytes of the fp32 kernels of cnn.hip), statistics fp32, combined in fp64 in a
+// fixed order (bitwise reproducible).  (OutConv on bf16 activations: outconv.hip.)
 #include "unet16.h"
 
 namespace mmft {
@@ -340,134 +340,6 @@ __global__ void __launch_bounds__(256) u16_pool_bwd_kernel(U16PoolBwdArgs p) {
   }
 }
 
-// ---------------------------------------------------------------------------------------------- OutConv (bf16 activations)
-// outconv.hip with bf16 loads / stores: out = relu(pool2x2(b + sum_c w[c] x[c])) fp32; backward recomputes the pixel
-// values from x, writes dx (bf16) and per-workgroup slabs of dw / db.
-constexpr int OC16_CI = 16;
-
-struct U16OutConvArgs {
-  const u16* x;        // [N][H][W][16]
-  const float* w;      // [16]
-  const float* bias;   // [1] or null
-  const float* gout;   // [N][H/2][W/2]
-  float* out;          // [N][H/2][W/2]
-  u16* dx;             // [N][H][W][16]
-  float* slabs;        // [gridDim.x][17]
-  int N, H, W, mode;
-  long long items;     // N * (H / 2) * (W / 32)
-};
-
-__device__ __forceinline__ void oc16_window(const U16OutConvArgs& a, long long item, int lane, float xv[OC16_CI], float& pooled,
-                                            int& arg, int& me, long long& pix, long long& opix) {
-  const int wx = a.W / 32;
-  const int xb = (int)(item % wx);
-  const long long rp = item / wx;
-  const int y2 = (int)(rp % (a.H / 2));
-  const long long n = rp / (a.H / 2);
-  const int rowbit = lane >> 5, xx = xb * 32 + (lane & 31);
-  pix = (n * a.H + 2 * y2 + rowbit) * a.W + xx;
-  opix = rp * (a.W / 2) + (xx >> 1);
-  const u16* p = a.x + pix * OC16_CI;
-  unpack8(*reinterpret_cast<const u32x4*>(p), xv);
-  unpack8(*reinterpret_cast<const u32x4*>(p + 8), xv + 8);
-  float v = a.bias ? a.bias[0] : 0.f;
-#pragma unroll
-  for (int c = 0; c < OC16_CI; ++c) v = __fmaf_rn(xv[c], a.w[c], v);
-  me = rowbit * 2 + (xx & 1);
-  const float vx = __shfl_xor(v, 1, 64), vy = __shfl_xor(v, 32, 64), vd = __shfl_xor(v, 33, 64);
-  float qv[4];
-  qv[0] = me == 0 ? v : me == 1 ? vx : me == 2 ? vy : vd;
-  qv[1] = me == 1 ? v : me == 0 ? vx : me == 3 ? vy : vd;
-  qv[2] = me == 2 ? v : me == 3 ? vx : me == 0 ? vy : vd;
-  qv[3] = me == 3 ? v : me == 2 ? vx : me == 1 ? vy : vd;
-  if (a.mode == MMFT_POOL_MAX) {
-    float m = qv[0];
-    arg = 0;
-#pragma unroll
-    for (int j = 1; j < 4; ++j)
-      if (qv[j] > m || qv[j] != qv[j]) {
-        m = qv[j];
-        arg = j;
-      }
-    pooled = m;
-  } else {
-    pooled = (qv[0] + qv[1] + qv[2] + qv[3]) * 0.25f;
-    arg = -1;
-  }
-}
-
-__global__ void __launch_bounds__(256) u16_outconv_fwd_kernel(U16OutConvArgs a) {
-  const int lane = threadIdx.x & 63;
-  for (long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6); item < a.items; item += (long long)gridDim.x * 4) {
-    float xv[OC16_CI], pooled;
-    int arg, me;
-    long long pix, opix;
-    oc16_window(a, item, lane, xv, pooled, arg, me, pix, opix);
-    if (me == 0) a.out[opix] = pooled > 0.f ? pooled : 0.f;
-  }
-}
-
-__global__ void __launch_bounds__(256) u16_outconv_bwd_kernel(U16OutConvArgs a) {
-  __shared__ float red[4][OC16_CI + 1];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float acc[OC16_CI + 1];
-#pragma unroll
-  for (int c = 0; c <= OC16_CI; ++c) acc[c] = 0.f;
-  for (long long item = (long long)blockIdx.x * 4 + wave; item < a.items; item += (long long)gridDim.x * 4) {
-    float xv[OC16_CI], pooled;
-    int arg, me;
-    long long pix, opix;
-    oc16_window(a, item, lane, xv, pooled, arg, me, pix, opix);
-    float g = a.gout[opix];
-    if (!(pooled > 0.f)) g = 0.f;
-    g = a.mode == MMFT_POOL_MAX ? (me == arg ? g : 0.f) : g * 0.25f;
-    float d[OC16_CI];
-#pragma unroll
-    for (int c = 0; c < OC16_CI; ++c) {
-      d[c] = a.w[c] * g;
-      acc[c] = __fmaf_rn(g, xv[c], acc[c]);
-    }
-    acc[OC16_CI] += g;
-    u16* dst = a.dx + pix * OC16_CI;
-    *reinterpret_cast<u32x4*>(dst) = pack8(d);
-    *reinterpret_cast<u32x4*>(dst + 8) = pack8(d + 8);
-  }
-#pragma unroll
-  for (int c = 0; c <= OC16_CI; ++c) {
-    float v = acc[c];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    if (lane == 0) red[wave][c] = v;
-  }
-  __syncthreads();
-  if (threadIdx.x <= OC16_CI)
-    a.slabs[(long long)blockIdx.x * (OC16_CI + 1) + threadIdx.x] =
-        ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
-}
-
-__global__ void __launch_bounds__(512) u16_outconv_reduce_kernel(const float* __restrict__ slabs, int nslab, float* __restrict__ dw,
-                                                                 float* __restrict__ db, int accumulate) {
-  __shared__ float part[8][64];
-  const int e = threadIdx.x & 63, p = threadIdx.x >> 6;
-  float s = 0.f;
-  if (e <= OC16_CI)
-    for (int b = p; b < nslab; b += 8) s += slabs[(long long)b * (OC16_CI + 1) + e];
-  part[p][e] = s;
-  __syncthreads();
-  if (p == 0 && e <= OC16_CI) {
-    float t = 0.f;
-    for (int k = 0; k < 8; ++k) t += part[k][e];
-    float* dst = e < OC16_CI ? dw + e : db;
-    if (dst) *dst = accumulate ? *dst + t : t;
-  }
-}
-
-static inline int u16_oc_grid(long long items) {
-  long long g = (items + 3) / 4;
-  if (g > 1024) g = 1024;
-  return (int)(g < 1 ? 1 : g);
-}
-
 static inline int u16_bwd_blocks(long long rows) {         // row blocks per image of the backward partial sums
   long long b = (rows + 511) / 512;
   if (b > 256) b = 256;
@@ -555,45 +427,6 @@ int mmft_u16_pool_bwd(const void* a, int lda, const void* gskip, int ldg, const 
   MMFT_LAUNCH("u16_pool_bwd_kernel", 0.0, 2.0 * N * H * W * C * (gskip ? 3.25 : 2.25), u16_pool_bwd_kernel, dim3(ew_grid(items)), dim3(256),
               (hipStream_t)stream, p);
   return check_launch("u16_pool_bwd");
-}
-
-int mmft_u16_outconv_fwd(const void* x, const float* w, const float* bias, float* out, int N, int H, int W, int mode, int device,
-                         void* stream) {
-  MMFT_REQUIRE(x && w && out && N > 0 && H % 2 == 0 && W % 32 == 0 && (mode == MMFT_POOL_MAX || mode == MMFT_POOL_AVG) && aligned16(x),
-               "u16_outconv_fwd: needs 16 input channels, even H, W %% 32 == 0");
-  DeviceGuard dg(device);
-  const long long items = (long long)N * (H / 2) * (W / 32);
-  U16OutConvArgs a{reinterpret_cast<const u16*>(x), w, bias, nullptr, out, nullptr, nullptr, N, H, W, mode, items};
-  MMFT_LAUNCH("u16_outconv_fwd_kernel", 2.0 * N * H * W * 16, 2.0 * N * H * W * 16 + 1.0 * N * H * W, u16_outconv_fwd_kernel,
-              dim3(u16_oc_grid(items)), dim3(256), (hipStream_t)stream, a);
-  return check_launch("u16_outconv_fwd");
-}
-
-long long mmft_u16_outconv_bwd_workspace_bytes(int N, int H, int W) {
-  return (long long)u16_oc_grid((long long)N * (H / 2) * (W / 32)) * 17 * 4;
-}
-
-/* slabs of 17 floats: [dw[16] | db] */
-int mmft_u16_outconv_bwd_slabs(int N, int H, int W) { return u16_oc_grid((long long)N * (H / 2) * (W / 32)); }
-
-int mmft_u16_outconv_bwd(const void* x, const float* w, const float* bias, const float* gout, void* dx, float* dw, float* db,
-                         int accumulate, int N, int H, int W, int mode, float* workspace, long long workspace_bytes, int device,
-                         void* stream) {
-  MMFT_REQUIRE(x && w && gout && dx && N > 0 && H % 2 == 0 && W % 32 == 0 && (mode == MMFT_POOL_MAX || mode == MMFT_POOL_AVG) &&
-                   aligned16(x) && aligned16(dx),
-               "u16_outconv_bwd: needs 16 input channels, even H, W %% 32 == 0");
-  MMFT_REQUIRE(workspace && workspace_bytes >= mmft_u16_outconv_bwd_workspace_bytes(N, H, W), "u16_outconv_bwd: workspace too small");
-  DeviceGuard dg(device);
-  hipStream_t st = (hipStream_t)stream;
-  const long long items = (long long)N * (H / 2) * (W / 32);
-  const int grid = u16_oc_grid(items);
-  U16OutConvArgs a{reinterpret_cast<const u16*>(x), w, bias, gout, nullptr, reinterpret_cast<u16*>(dx), workspace, N, H, W, mode, items};
-  MMFT_LAUNCH("u16_outconv_bwd_kernel", 4.0 * N * H * W * 16, 4.0 * N * H * W * 16 + 1.0 * N * H * W, u16_outconv_bwd_kernel, dim3(grid),
-              dim3(256), st, a);
-  int rc = check_launch("u16_outconv_bwd");
-  if (rc || !dw) return rc;          // dw == NULL: the slabs stay in `workspace` for mmft_slab_reduce_batch
-  hipLaunchKernelGGL(u16_outconv_reduce_kernel, dim3(1), dim3(512), 0, st, workspace, grid, dw, db, accumulate ? 1 : 0);
-  return check_launch("u16_outconv_reduce");
 }
 
 }  // extern "C"

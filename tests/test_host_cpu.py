@@ -526,14 +526,12 @@ ABI_COVERED_INDIRECTLY = {
     'mmft_linear_wgrad_bias_workspace_bytes': ('test_kernels_gpu.py::test_linear_wgrad_colsum', 'ops.linear_wgrad(with_bias) sizes its slabs with it'),
     'mmft_mlp2_first_layer_grads_workspace_bytes': ('test_kernels_gpu.py::test_mlp2_first_layer_grads', 'the wrapper sizes its scratch with it'),
     'mmft_conv2d_wgrad_workspace_bytes': ('test_kernels_gpu.py::test_conv3x3_forward_dgrad_wgrad', 'ops.conv2d_wgrad sizes its slabs with it'),
-    'mmft_outconv_bwd_workspace_bytes': ('test_kernels_gpu.py::test_outconv_fused_vs_torch', 'ops.outconv_bwd sizes its scratch with it'),
     'mmft_mlp2_feat_bwd_workspace_bytes': ('test_bf16_gpu.py::test_feature_mlp_without_hidden_tensor', 'ops.mlp2_feat_bwd_bf16 sizes its scratch with it'),
     'mmft_rows_outer_supported': ('test_bf16_gpu.py::test_rows_outer_weight_gradient', 'the shape gate in front of mmft_rows_outer_bf16'),
     'mmft_rows_outer_workspace_bytes': ('test_bf16_gpu.py::test_rows_outer_weight_gradient', 'sizes the slabs of mmft_rows_outer_bf16'),
     'mmft_u16_pack_desc_bytes': ('test_unet16_gpu.py::test_conv3x3_forward_exact_and_stats', 'unet16.pack_table asserts it equals its ctypes record'),
     'mmft_u16_conv3x3_wgrad_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
     'mmft_u16_convt_wgrad_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
-    'mmft_u16_outconv_bwd_slabs': ('test_unet16_gpu.py::test_batched_reduce_equals_per_layer_reduce', 'the slab count of the deferred reduction'),
     'mmft_levelize_workspace_bytes': ('test_prep_gpu.py::test_levelize_trace_masks_vs_restatement', 'prep.levelize sizes its scratch with it'),
     'mmft_minmax_workspace_bytes': ('test_prep_gpu.py::test_minmax_normalize_bit_exact', 'prep.minmax_normalize_ sizes its scratch with it'),
 }

@@ -283,6 +283,63 @@ def test_outconv_bf16_input(dev, pool):
     assert rel_err(dw, wa.grad.reshape(16)) < 1e-5 and rel_err(db, ba.grad) < 1e-5
 
 
+def _outconv_twin_inputs(N, H, W):
+    """bf16-representable x with eight 2x2 windows whose four pixels hold the same channel vector (an exact tie of the
+    window's four values), fp32 w / gout, a clearly positive bias; returns the tied windows as (n, y2, x2) rows."""
+    g = torch.Generator().manual_seed(21)
+    x = torch.randn((N, H, W, 16), generator=g).to(BF)
+    w, b = torch.randn(16, generator=g), 1.0 + 0.1 * torch.randn(1, generator=g)
+    gout = torch.randn((N, H // 2, W // 2), generator=g)
+    wins = torch.randperm(N * (H // 2) * (W // 2), generator=g)[:8]
+    ties = torch.stack([wins // ((H // 2) * (W // 2)), (wins // (W // 2)) % (H // 2), wins % (W // 2)], 1)
+    for n, y2, x2 in ties.tolist():
+        x[n, 2 * y2:2 * y2 + 2, 2 * x2:2 * x2 + 2, :] = x[n, 2 * y2, 2 * x2, :].clone()
+    return x, w, b, gout, ties
+
+
+# (1, 2, 32): one item - one wave works, three contribute zeros to the slab; (2, 6, 64): 12 items, a grid of 3, a slab
+# count that is no multiple of the reduction's 8; (1, 258, 1024): 4128 items > 4 x 1024 - the grid-stride loop's second pass
+@pytest.mark.parametrize('N,H,W', [(1, 2, 32), (2, 6, 64), (1, 258, 1024)])
+@pytest.mark.parametrize('pool', ['max', 'avg'])
+def test_outconv_bf16_form_is_the_fp32_form(dev, pool, N, H, W):
+    """The two storage forms of OutConv are one kernel template (csrc/outconv.hip): on an x that bf16 represents,
+    mmft_u16_outconv_* and mmft_outconv_* give the same out, dw, db (stored and accumulated) bit for bit and the same dx
+    after its one rounding to bf16, a tie within a window goes to its first pixel, and the slab rules agree."""
+    x16, w, b, gout, ties = _outconv_twin_inputs(N, H, W)
+    mode = ops.POOL_MAX if pool == 'max' else ops.POOL_AVG
+    x16, w, b, gout = x16.to(dev), w.to(dev), b.to(dev), gout.to(dev)
+    x32 = x16.float()
+    d, s = lib.stream_args(x16)
+    nbytes = lib.query('mmft_u16_outconv_bwd_workspace_bytes', N, H, W)
+    assert lib.query('mmft_u16_outconv_bwd_slabs', N, H, W) * 17 * 4 == nbytes == lib.query('mmft_outconv_bwd_workspace_bytes', N, H, W, 16)
+    ws = lib.workspace(dev, nbytes)
+
+    out32, out16 = torch.empty((N, H // 2, W // 2), device=dev), torch.empty((N, H // 2, W // 2), device=dev)
+    lib.call('mmft_outconv_fwd', x32, w, b, out32, N, H, W, 16, mode, d, s)
+    lib.call('mmft_u16_outconv_fwd', x16, w, b, out16, N, H, W, mode, d, s)
+    assert torch.equal(out16, out32)
+
+    fill = torch.Generator().manual_seed(22)
+    dw0, db0 = torch.randn(16, generator=fill).to(dev), torch.randn(1, generator=fill).to(dev)
+    dx32, dx16 = torch.empty((N, H, W, 16), device=dev), torch.empty((N, H, W, 16), dtype=BF, device=dev)
+    for accumulate in (0, 1):
+        dw32, db32, dw16, db16 = dw0.clone(), db0.clone(), dw0.clone(), db0.clone()
+        lib.call('mmft_outconv_bwd', x32, w, b, gout, dx32, dw32, db32, accumulate, N, H, W, 16, mode, ws, ws.numel() * 4, d, s)
+        lib.call('mmft_u16_outconv_bwd', x16, w, b, gout, dx16, dw16, db16, accumulate, N, H, W, mode, ws, ws.numel() * 4, d, s)
+        assert torch.equal(dw16, dw32) and torch.equal(db16, db32), accumulate
+        assert not torch.equal(dw32, dw0) and not torch.equal(db32, db0)
+    assert torch.equal(dx16, dx32.to(BF))
+
+    if pool == 'max':
+        routed = 0
+        for n, y2, x2 in ties.tolist():
+            if float(out32[n, y2, x2]) > 0:
+                win = dx32[n, 2 * y2:2 * y2 + 2, 2 * x2:2 * x2 + 2, :].reshape(4, 16)
+                assert bool((win[0] != 0).any()) and bool((win[1:] == 0).all()), (n, y2, x2)
+                routed += 1
+        assert routed > 0, 'no tied window with a positive pooled value: the first-maximum rule was not exercised'
+
+
 def _cos(a, b):
     a, b = a.detach().double().cpu().reshape(-1), b.detach().double().cpu().reshape(-1)
     return float((a @ b) / (a.norm() * b.norm() + 1e-300))
