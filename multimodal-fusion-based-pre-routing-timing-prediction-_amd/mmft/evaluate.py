@@ -81,15 +81,29 @@ def level_metrics_from_sums(rows):
 
 
 @torch.no_grad()
-def validate(train_step, path_ids_per_design=None, per_level=False, frozen_stats=False):
+def validate(train_step, path_ids_per_design=None, per_level=False, frozen_stats=False, per_design=False):
     """Forward over all (or the given) paths of the designs held by `train_step` (a mmft.train.TrainStep) and
     return the metric dict; per_level=True adds 'levels': R2 / MAPE of every topological level (src/test.py:211-216).
     One device->host copy.  frozen_stats=False (default) is the reference's behaviour: the modules stay in train mode
     (SURVEY D5).  frozen_stats=True: the CNN runs in eval mode for this call (running statistics, no buffer written) and is
-    returned to the mode it was in."""
+    returned to the mode it was in.
+
+    per_design=True adds 'designs': one metric dict per design of the batch - what the reference reports per case and
+    averages over the cases (src/train.py:280-290, src/test.py:283-313) - from the SAME forward.  Task 'reg': one more
+    mmft_eval_sums_by_level launch keyed by each row's design index (with per_level a second one keyed by design and
+    level, for each design's 'levels'); the sums ride in the one device->host copy.  Task 'cls' has no keyed sums kernel:
+    the pooled call is followed by one call per design with the other designs' path lists empty - correct, but B more
+    forwards (and, unless frozen_stats, B more updates of the BatchNorm running statistics)."""
     b = train_step.batch
     if path_ids_per_design is None:
         path_ids_per_design = [np.arange(d.num_paths) for d in b.designs]
+    if per_design and getattr(train_step, 'task', 'reg') == 'cls':
+        m = validate(train_step, path_ids_per_design, per_level=per_level, frozen_stats=frozen_stats)
+        empty = np.zeros(0, dtype=np.int64)
+        m['designs'] = [validate(train_step, [ids if j == i else empty for j, ids in enumerate(path_ids_per_design)],
+                                 per_level=per_level, frozen_stats=frozen_stats) if len(path_ids_per_design[i]) else dict(n=0)
+                        for i in range(b.B)]
+        return m
     sel = b.select(path_ids_per_design)
     with frozen_statistics(train_step.cnn, frozen_stats):
         hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
@@ -108,12 +122,41 @@ def validate(train_step, path_ids_per_design=None, per_level=False, frozen_stats
         f1 = 2 * recall * precision / (recall + precision) if (precision or recall) else 0.0
         return dict(n=int(n), loss=lsum / n, r2=0.0, acc=(tp + tn) / n, recall=recall, precision=precision, f1=f1,
                     tp=int(tp), fp=int(fp), tn=int(tn), fn=int(fn))
+    if per_design:
+        return _validate_per_design(b, sel, hats, arrival, required, label, per_level)
     if not per_level:
         return metrics_from_sums(eval_sums(hats, arrival, required, label).cpu().tolist())
     both = torch.cat([eval_sums(hats, arrival, required, label).reshape(1, 10),
                       eval_sums_by_level(hats, arrival, required, label, sel[5].contiguous(), b.L)], 0).cpu().tolist()
     m = metrics_from_sums(both[0])
     m['levels'] = level_metrics_from_sums(both[1:])
+    return m
+
+
+def _validate_per_design(b, sel, hats, arrival, required, label, per_level):
+    """The 'reg' tail of validate(per_design=True): pooled sums [1], per-level sums [L] (per_level), per-design sums [B],
+    per-design-and-level sums [B * L] (per_level) - one concatenation, one device->host copy."""
+    B, L = b.B, b.L
+    # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
+    design = torch.div(sel[2], b.P, rounding_mode='floor').to(torch.int32).contiguous()
+    parts = [eval_sums(hats, arrival, required, label).reshape(1, 10)]
+    if per_level:
+        parts.append(eval_sums_by_level(hats, arrival, required, label, sel[5].contiguous(), L))
+    parts.append(eval_sums_by_level(hats, arrival, required, label, design, B))
+    if per_level:
+        parts.append(eval_sums_by_level(hats, arrival, required, label, (design * L + sel[5]).contiguous(), B * L))
+    rows = torch.cat(parts, 0).cpu().tolist()
+    m = metrics_from_sums(rows[0])
+    pos = 1
+    if per_level:
+        m['levels'] = level_metrics_from_sums(rows[pos:pos + L])
+        pos += L
+    m['designs'] = [metrics_from_sums(r) if r[0] > 0 else dict(n=0) for r in rows[pos:pos + B]]
+    pos += B
+    if per_level:
+        for i, dm in enumerate(m['designs']):
+            if dm['n']:
+                dm['levels'] = level_metrics_from_sums(rows[pos + i * L:pos + (i + 1) * L])
     return m
 
 

@@ -565,6 +565,57 @@ class FlatAdam:
     def device_step_count(self):
         return int(self.state[0, 0].item())
 
+    def _layout(self):
+        return dict(n=int(self.n), offsets=[int(o) for o in self.offsets], sizes=[int(p.numel()) for p in self.params],
+                    buckets=[(str(name), int(lo), int(hi)) for name, lo, hi in self.bucket_ranges])
+
+    def state_dict_hyper(self):
+        return dict(lr=float(self.lr), betas=(float(self.betas[0]), float(self.betas[1])), eps=float(self.eps),
+                    weight_decay=float(self.wd))
+
+    def state_dict(self):
+        """Host copies of the moments, the per-bucket device counters and the step count, the hyperparameters and the
+        layout of the flat buffer (offsets / sizes / bucket ranges: what a load checks itself against).  The parameters
+        are not in it: they travel in the modules' own state_dict()."""
+        return dict(m=self.m.detach().cpu().clone(), v=self.v.detach().cpu().clone(), state=self.state.detach().cpu().clone(),
+                    step_count=int(self.step_count), hyper=self.state_dict_hyper(), layout=self._layout())
+
+    def check_layout(self, sd):
+        """Raise ValueError, saying why, unless `sd` was saved from an optimizer with this one's parameter layout."""
+        mine, theirs = self._layout(), sd['layout']
+        sizes, offsets = [int(s) for s in theirs['sizes']], [int(o) for o in theirs['offsets']]
+        if len(sizes) != len(mine['sizes']):
+            raise ValueError(f"FlatAdam.load_state_dict: saved from {len(sizes)} parameters, this optimizer holds "
+                             f"{len(mine['sizes'])}")
+        for i, (a, b) in enumerate(zip(sizes, mine['sizes'])):
+            if a != b:
+                raise ValueError(f'FlatAdam.load_state_dict: parameter {i} was saved with {a} elements, here it has {b}')
+        if offsets != mine['offsets'] or int(theirs['n']) != mine['n']:
+            raise ValueError('FlatAdam.load_state_dict: same parameter sizes, but the saved flat buffer places them at other '
+                             f"offsets ({int(theirs['n'])} elements in all, here {mine['n']})")
+        if [tuple(b) for b in theirs['buckets']] != mine['buckets']:
+            raise ValueError(f"FlatAdam.load_state_dict: saved with the buckets {[tuple(b) for b in theirs['buckets']]}, "
+                             f"this optimizer has {mine['buckets']}")
+        for name, dst in (('m', self.m), ('v', self.v), ('state', self.state)):
+            src = sd[name]
+            if tuple(src.shape) != tuple(dst.shape) or src.dtype != dst.dtype:
+                raise ValueError(f'FlatAdam.load_state_dict: {name} is {tuple(src.shape)} {src.dtype}, '
+                                 f'expected {tuple(dst.shape)} {dst.dtype}')
+
+    def load_state_dict(self, sd):
+        """Restore state_dict() IN PLACE: m, v and the counters keep their device addresses (captured graphs have baked
+        them in; the hyperparameters a graph was captured with are baked in too and do not follow a load).  A state saved
+        from another parameter layout is refused.  Parameters are loaded through the modules' own load_state_dict();
+        whoever does that calls gradsink.params_changed() afterwards, as this method does."""
+        self.check_layout(sd)
+        for name, dst in (('m', self.m), ('v', self.v), ('state', self.state)):
+            dst.copy_(sd[name])
+        self.step_count = int(sd['step_count'])
+        h = sd['hyper']
+        self.lr, self.betas, self.eps, self.wd = float(h['lr']), (float(h['betas'][0]), float(h['betas'][1])), float(h['eps']), \
+            float(h['weight_decay'])
+        gradsink.params_changed()
+
 
 def _dense(t):
     """non-overlapping and dense (any permutation of a contiguous block)."""

@@ -190,12 +190,26 @@ class DesignBatch:
 class TrainStep:
     def __init__(self, pmodel, cnn, designs, device, lr=1e-3, weight_decay=0.0, fused_optimizer=True, world_size=1,
                  mode='sweep', overlap=True, with_optimizer=True, task='reg', cone=False, dense_path_map=False,
-                 keep_grads=True):
+                 keep_grads=True, optimizer=None):
         """mode='dropin': per-level model() calls exactly as src/train.py:490-511;
         mode='sweep': PathModel.forward_sweep, same arithmetic with level-invariant work hoisted.
         task='reg': MSE on the arrival time (nlabels = 1); task='cls': CrossEntropy on ndata['label'] with a
-        nlabels-wide head (src/train.py:32,513-522; src/options.py:32,49)."""
+        nlabels-wide head (src/train.py:32,513-522; src/options.py:32,49).
+        optimizer: a FlatAdam over exactly trainable_parameters(pmodel, cnn) that this step uses instead of building one -
+        the one Adam state of the reference (src/train.py:431-435) shared by several steps over different designs
+        (mmft.epochs.EpochTrainer); lr, weight_decay and keep_grads are then the optimizer's own."""
         assert mode in ('dropin', 'sweep') and task in ('reg', 'cls')
+        if optimizer is not None:
+            if not with_optimizer or not fused_optimizer:
+                raise ValueError('TrainStep: optimizer= is the fused FlatAdam of a training step '
+                                 '(not with with_optimizer=False or fused_optimizer=False)')
+            if world_size > 1:
+                raise ValueError('TrainStep: a shared optimizer under data parallelism (world_size > 1) is not supported')
+            if not isinstance(optimizer, FlatAdam):
+                raise ValueError(f'TrainStep: optimizer= expects a FlatAdam, got {type(optimizer).__name__}')
+            want = trainable_parameters(pmodel, cnn)
+            if len(optimizer.params) != len(want) or {id(p) for p in optimizer.params} != {id(p) for p in want}:
+                raise ValueError('TrainStep: the optimizer does not hold exactly trainable_parameters(pmodel, cnn)')
         self.mode, self.task = mode, task
         # dense_path_map (drop-in mode): the reference's literal per-level map, th.index_select(path_masks, 0, paths).to_dense()
         # * feat_map (src/train.py:500-501: sparse COO masks with int64 values, promoted by the multiply), instead of the
@@ -220,6 +234,8 @@ class TrainStep:
         self.reducer = None
         if not with_optimizer:                  # evaluation-only harness (mmft.evaluate.validate): shares the modules
             self.optim = None
+        elif optimizer is not None:             # shared: the parameters already live in its flat buffer
+            self.optim = optimizer
         elif fused_optimizer:
             if world_size > 1:
                 # data parallel: one flat range per gradient bucket, reduced as soon as its gradients exist
