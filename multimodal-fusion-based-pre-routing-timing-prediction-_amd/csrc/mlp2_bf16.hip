@@ -439,8 +439,9 @@ __global__ void __launch_bounds__(512) level_fwd_slots_kernel(LevelSlotsArgs<KEE
 // driver-side fold 5x slower than two pulls), no float atomics, and for such tiles the same additions in the same order as
 // level_bwd_pull: bitwise equal (tested).  The finished driver rows go to LDS as bf16 and through the MFMA phases of the level
 // MLP (one or two 16-row blocks).
-// HEAVY drivers (more sinks than a tile's target: drivers of high-fanout nets) would leave their workgroup walking hundreds
-// of sinks while the rest of the card has finished; their sink run is cut into PARTS (16 sinks), one workgroup each.  A part
+// HEAVY drivers (more sinks than a tile of whole drivers may hold, PinGraph.BWD_PAIR_TILE_SINKS = 32: drivers of high-fanout
+// nets) would leave their workgroup walking hundreds of sinks while the rest of the card has finished; the host cuts their sink
+// run into PARTS of PinGraph.BWD_PAIR_PART = 32 sinks (the last one may hold fewer), one workgroup each.  A part
 // finishes its sinks, writes the partial sum of their rows (in edge order) to scratch and bumps a per-driver counter; the
 // workgroup that arrives last adds the partial sums IN PART ORDER (whichever workgroup that is: the result does not depend on
 // the arrival order), finishes the driver's row and runs the MLP phases for it.  Nobody waits for anybody.
@@ -503,7 +504,8 @@ __global__ void __launch_bounds__(512) level_bwd_pair_kernel(LevelBwdPairArgs a)
       for (int j = 0; j < 4; ++j) acc[d][j] = mine_v ? acc[d][j] : 0.f;
     }
   }
-  // ---- the tile's sinks, 32 at a time (a tile of whole drivers holds at most 32, a part of a heavy driver 16)
+  // ---- the tile's sinks, 32 at a time (as the host tiles them, a tile of whole drivers and a part of a heavy driver hold at
+  // most 32: one round; a longer run takes several)
   for (int c0 = e0; c0 < e1; c0 += SC) {
     const int cend = c0 + SC < e1 ? c0 + SC : e1;
     int e = c0 + gr;

@@ -431,7 +431,7 @@ class PinGraph:
                 fan = np.diff(optr[row0:row0 + n + 1])
                 ok = (e1 - e0 == n_net) and (n_net == 0 or bool((oidx[e0:e1] == np.arange(rn[0], rn[0] + n_net)).all()))
                 if ok:
-                    # greedy tiling: close a tile at 16 drivers, or when the next driver would push it past the sink target
+                    # greedy tiling: close a tile at BWD_PAIR_TILE_DRIVERS drivers, or when the next driver would push it past the sink budget
                     tiles, start, sinks, srow, cnt = [], 0, 0, 0, 0
                     fl = fan.tolist()
                     pos = optr[row0:row0 + n + 1].tolist()                # CSR position of every driver's first sink

@@ -296,7 +296,7 @@ def test_paired_reverse_level_kernel_equals_three_kernel_form(dev, fanout_skew, 
     and fc_cell_neigh's backward) against the three-launch form (mmft_level_bwd_pull twice, mmft_mlp2_rows_bf16 reversed).
     parts=False: every driver whole inside one tile - the same additions in the same order as the pulls (run without their
     workgroup-per-heavy-row path): bitwise equal G, DA, hidden gradients and parameter gradients.  parts=True (the shipped
-    setting): drivers with more than 48 sinks are cut into parts of 32 whose partial sums are added in part order by whichever
+    setting): drivers with more than PinGraph.BWD_PAIR_TILE_SINKS = 32 sinks are cut into parts of BWD_PAIR_PART = 32 whose partial sums are added in part order by whichever
     workgroup arrives last - another summation order for those rows (1e-5), and two runs must agree bit for bit.  With
     fanout_skew some pins have more than four cell consumers (the CSR tail of the slot table)."""
     from mmft import sweep as S
