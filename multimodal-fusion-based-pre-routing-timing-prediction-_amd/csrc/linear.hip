@@ -319,7 +319,7 @@ using namespace mmft;
 
 extern "C" {
 
-int mmft_version(void) { return 201; }      // 201: mmft_adam_step takes its bias corrections as double
+int mmft_version(void) { return 202; }      // 202: the extension header include/mmft_report.h (mmft_timing_report)
 
 int mmft_set_math_mode(int mode) {
   MMFT_REQUIRE(mode == MMFT_MATH_F32 || mode == MMFT_MATH_BF16, "set_math_mode: unknown mode %d", mode);

@@ -160,6 +160,46 @@ def _validate_per_design(b, sel, hats, arrival, required, label, per_level):
     return m
 
 
+@torch.no_grad()
+def timing_report(train_step, path_ids_per_design=None, k=32, hist=None, frozen_stats=False):
+    """What a timing engine prints, for the model and for the truth: one forward as validate() runs it, then the report
+    kernel (mmft.report) twice over the same rows - on the predictions and on the true arrival times - and ONE device->host
+    copy.  Per design a dict with
+      predicted, actual   the two reports (mmft.report.decode: n, n_nan, violations, wns, wns_row, tns, worst, hist, ...;
+                          rows are rows of the forward's output, endpoints the batch's node ids)
+      wns_error, tns_error   predicted - actual (None for a design without a valid row)
+      topk_overlap        |worst-k rows predicted & worst-k rows actual| / min(k, valid rows) (None without a valid row)
+    Regression task only."""
+    from . import report as R
+    if getattr(train_step, 'task', 'reg') != 'reg':
+        raise ValueError('timing_report: the regression task only')
+    b = train_step.batch
+    if path_ids_per_design is None:
+        path_ids_per_design = [np.arange(d.num_paths) for d in b.designs]
+    if not sum(len(p) for p in path_ids_per_design):
+        raise ValueError('timing_report: no path selected')
+    sel = b.select(path_ids_per_design)
+    with frozen_statistics(train_step.cnn, frozen_stats):
+        hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
+    idx, T = ends_d.long(), ends_d.numel()
+    arrival = b.arrival[idx].reshape(T).contiguous()
+    required = b.required[idx].reshape(T).contiguous()
+    # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
+    design = np.zeros(T, dtype=np.int64) if b.B == 1 else sel[2].cpu().numpy().astype(np.int64) // b.P
+    ptr, rows = (torch.from_numpy(a).to(hats.device) for a in R.group_rows(design, b.B))
+    bufs = R.ReportBuffers(b.B, k, hist, hats.device, reports=2)
+    R.timing_report(hats.contiguous(), required, ptr, rows, k, hist, out=bufs.tensors(0))
+    R.timing_report(arrival, required, ptr, rows, k, hist, out=bufs.tensors(1))
+    predicted, actual = (R.decode(*h, endpoints=np.asarray(sel[4])) for h in bufs.host())
+    out = []
+    for p, a in zip(predicted, actual):
+        m = min(int(k), p['n'], a['n'])
+        both = len({r for r, _ in p['worst']} & {r for r, _ in a['worst']})
+        out.append(dict(predicted=p, actual=a, wns_error=p['wns'] - a['wns'] if m else None,
+                        tns_error=p['tns'] - a['tns'] if m else None, topk_overlap=both / m if m else None))
+    return out
+
+
 def validate_designs(pmodel, cnn, designs, device, per_level=True, mode='sweep', frozen_stats=False):
     """The per-design loop of validate() / test() (src/train.py:137-291, src/test.py:124-318): every design is evaluated
     on its own as ONE batch over all of its paths (modules stay in train mode, SURVEY D5, unless frozen_stats=True puts

@@ -66,11 +66,15 @@ class Predictor:
                           fp32 mode, a U-Net that does not take its fused eval path.  Same results either way
     overlap               the netlist sweep on a side stream under the U-Net (as TrainStep)
     cone                  the sweep skips nodes outside the endpoints' fan-in cone (few endpoints of a large design)
+    report                None, or dict(k=32, hist=(lo, hi, nbins) or None): every predict() also launches the timing report
+                          kernel (mmft.report) on the predictions and the endpoints' required times, as the last launch of
+                          the call - inside the replayed graph in bf16 mode; report() decodes the last call's buffers.
+                          Regression task only.  predict() returns what it returns without it
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
-                 cone=False):
+                 cone=False, report=None):
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
@@ -92,7 +96,29 @@ class Predictor:
         self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
         self._tensors = [t for root in (pmodel, cnn) if root is not None for t in list(root.parameters()) + list(root.buffers())]
         self._replay = self._sig = self._out = None
+        self._report = self._make_report(report) if report is not None else None
 
+    def _make_report(self, spec):
+        """Everything the report launch needs that the static selection decides: the endpoints' required times, the rows of
+        each design, the output buffers and the scratch - static addresses, kept alive with the replay."""
+        from . import report as R
+        unknown = set(spec) - {'k', 'hist'}
+        if unknown:
+            raise ValueError(f'Predictor: report= takes k and hist, got {sorted(unknown)}')
+        nlabels = self.pmodel.mlp_fuse.layers[-1].out_features
+        if nlabels != 1:
+            raise ValueError(f'Predictor: report= needs the regression head (nlabels = 1), the model has {nlabels} labels')
+        b, dev = self.batch, self.device
+        k, hist = int(spec.get('k', 32)), spec.get('hist')
+        T = self._sel[0].numel()
+        required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
+        # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
+        design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
+        ptr, rows = R.group_rows(design, b.B)
+        bufs = R.ReportBuffers(b.B, k, hist, dev)
+        scratch = torch.empty((R.workspace_bytes(T, b.B, k, hist) + 7) // 8, dtype=torch.int64, device=dev)
+        return dict(k=k, hist=hist, required=required, design_ptr=torch.from_numpy(ptr).to(dev), design_rows=torch.from_numpy(rows).to(dev),
+                    bufs=bufs, scratch=scratch, ready=False)
     @contextlib.contextmanager
     def _modes_kept(self):
         """Module modes and the U-Net's statistics-per-image switch (set for the call, as TrainStep sets it for good: with it
@@ -141,7 +167,14 @@ class Predictor:
             cur.wait_stream(self.side)
             h_gnn.record_stream(cur)
         h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
-        return pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+        pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+        if self._report is not None:
+            from . import report as R
+            r = self._report
+            R.timing_report(pred.contiguous(), r['required'], r['design_ptr'], r['design_rows'], r['k'], r['hist'],
+                            out=r['bufs'].tensors(), workspace=r['scratch'])
+            r['ready'] = True
+        return pred
 
     @torch.no_grad()
     def predict(self):
@@ -158,11 +191,22 @@ class Predictor:
             sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
             if self._replay is None or sig != self._sig:
                 self._sig = sig
-                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors))
+                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report))
             out = self._replay.run(self._launches)
             if out is not None:                                  # an eager or the capturing call
                 self._out = out
             return self._out, self.endpoints
+
+    def report(self):
+        """The timing report of the LAST predict(): one dict per design (mmft.report.decode: n, n_nan, violations, wns,
+        wns_row, tns, worst, hist, wns_endpoint, worst_endpoints; rows are rows of `pred`, endpoints in the caller's
+        numbering).  One small device->host copy."""
+        from . import report as R
+        if self._report is None:
+            raise RuntimeError('Predictor.report(): no report was requested (report=dict(k=..., hist=...))')
+        if not self._report['ready']:
+            raise RuntimeError('Predictor.report(): predict() has not run yet')
+        return R.decode(*self._report['bufs'].host()[0], endpoints=self.endpoints)
 
     def update(self, i, cell_feat=None, net_feat=None, image=None):
         """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the

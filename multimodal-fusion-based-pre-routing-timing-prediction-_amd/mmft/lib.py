@@ -1,4 +1,5 @@
-"""ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h).
+"""ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
+include/mmft_report.h, called through `ext`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -14,13 +15,14 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('MMFT_LIB') or os.path.join(PKG_DIR, 'lib', 'libmmft_hip.so')      # MMFT_LIB: another build of the same library (A/B runs)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft.h')
+EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report.h')      # extensions: not the reference's path
 
 _lib = None
 
 
-def header_decls():
-    """{name: (restype, [argtypes])} parsed from include/mmft.h - the header is the single source of truth."""
-    with open(HEADER_PATH) as f:
+def _parse_header(path):
+    """{name: (restype, [argtypes])} of every function a header declares."""
+    with open(path) as f:
         text = f.read()
     text = re.sub(r'/\*.*?\*/', '', text, flags=re.S)
     decls = {}
@@ -43,10 +45,20 @@ def header_decls():
                 elif prm.startswith('double'):
                     args.append(ctypes.c_double)
                 else:
-                    raise RuntimeError(f'mmft.h: cannot parse parameter "{prm}" of {name}')
+                    raise RuntimeError(f'{os.path.basename(path)}: cannot parse parameter "{prm}" of {name}')
         res = {'int': ctypes.c_int, 'long long': ctypes.c_longlong, 'const char*': ctypes.c_char_p}[ret]
         decls[name] = (res, args)
     return decls
+
+
+def header_decls():
+    """{name: (restype, [argtypes])} parsed from include/mmft.h - the header is the single source of truth."""
+    return _parse_header(HEADER_PATH)
+
+
+def ext_decls():
+    """The same for include/mmft_report.h, the entry points beyond the reference's hot path (called through `ext`)."""
+    return _parse_header(EXT_HEADER_PATH)
 
 
 def header_symbols():
@@ -106,6 +118,30 @@ def query(name, *args):
     if fn is None:
         fn = _FN[name] = getattr(load(), name)
     return int(fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args]))
+
+
+_EXT = {}
+
+
+def ext(name, *args):
+    """Call an entry point of include/mmft_report.h; restype and argtypes are bound from that header on first use.  An `int`
+    entry point raises like `call`; a `long long` query returns its value and raises when that is negative."""
+    fn = _EXT.get(name)
+    if fn is None:
+        decls = ext_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {EXT_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _EXT[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if fn.restype is ctypes.c_int:
+        if rc != 0:
+            raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+        return None
+    if rc < 0:
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
 
 
 _workspace = {}

@@ -1,6 +1,6 @@
 """Inference time and memory in bf16 math mode: predictions for all (or --paths) endpoints of resident designs.
 
-    python tools/bench_predict.py [--config B E] [--paths 0] [--reps 30] [--rounds 7] [--out FILE]
+    python tools/bench_predict.py [--config B E] [--paths 0] [--reps 30] [--rounds 7] [--report K] [--out FILE]
 
 Rows, per config (B: 8 designs x 65 536 nodes, 64 levels, 256^2 tiles; E: one design, 1 048 576 nodes, 128 levels, 512^2 tile,
 Zipf fan-in):
@@ -11,6 +11,10 @@ Zipf fan-in):
   trainstep_fwd_only  the same call with the flag on
   predictor_eager   mmft.infer.Predictor(graphed=False).predict()
   predictor_graph   Predictor().predict() replaying its captured graph
+  predictor_graph_report   (--report K) Predictor(report=dict(k=K, hist=(-1, 1, 32))): the replayed graph ends in the timing
+                    report kernel, and the call ends in report() - one small device->host copy, decoded
+  predictor_graph_host_report   (--report K) the plain replayed predict(), then the same numbers on the host: pred.cpu() and
+                    mmft.report.reference_report (numpy) - what a caller without the kernel does
   sweep_keep        the netlist sweep alone under no_grad, mmft.sweep.FORWARD_ONLY = False (the training forward)
   sweep_fwd_only    ... FORWARD_ONLY = True
 Timing: device events around `reps` back-to-back calls, after a warm-up of every row; the rows alternate inside each round, so
@@ -47,7 +51,7 @@ except ImportError:                                               # an older che
 CONFIGS = {'B': dict(designs=8, N=65536, L=64, tile=256, fanin='regular'),
            'E': dict(designs=1, N=1048576, L=128, tile=512, fanin='irregular')}
 LEVEL_KERNELS = ('level_fwd_slots_kernel', 'level_fwd_slots_infer_kernel', 'level_fwd_bf16_kernel', 'level_fwd_bf16_infer_kernel',
-                 'pair_fwd_gather_kernel', 'mlp2_rows_bf16_kernel<fwd>')
+                 'pair_fwd_gather_kernel', 'mlp2_rows_bf16_kernel<fwd>', 'timing_report_kernel')
 
 
 def timed(fn, reps):
@@ -120,6 +124,28 @@ def run_config(name, cfg, a, emit, dev):
             pg = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
             rows['predictor_eager'], graphs['predictor_eager'] = (lambda: pe.predict()[0]), pe.batch.graph
             rows['predictor_graph'], graphs['predictor_graph'] = (lambda: pg.predict()[0]), pg.batch.graph
+        if Predictor is not None and a.report:
+            from mmft import report as R
+            hist = (-1.0, 1.0, 32)
+            pr = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, report=dict(k=a.report, hist=hist))
+            ph = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+            host = dict(required=pr._report['required'].cpu().numpy(), ptr=pr._report['design_ptr'].cpu().numpy(),
+                        rows=pr._report['design_rows'].cpu().numpy())
+            last = {}
+
+            def graph_report():
+                y = pr.predict()[0]
+                last['device'] = pr.report()
+                return y
+
+            def graph_host_report():
+                y = ph.predict()[0]
+                last['host'] = R.decode(*R.reference_report(y.cpu().numpy(), host['required'], host['ptr'], host['rows'], a.report, hist),
+                                        endpoints=ph.endpoints)
+                return y
+            rows['predictor_graph_report'], graphs['predictor_graph_report'] = graph_report, pr.batch.graph
+            rows['predictor_graph_host_report'], graphs['predictor_graph_host_report'] = graph_host_report, ph.batch.graph
+
         def sweep_row(flag):
             sb = DesignBatch(designs, dev)                 # a graph of its own: the buffers a sweep allocated stay with its graph
             sb.graph.ndata['h'] = torch.zeros((sb.N, 128), dtype=torch.float32, device=dev)
@@ -163,6 +189,12 @@ def run_config(name, cfg, a, emit, dev):
                                         torch.equal(outs['sweep_fwd_only'][1], outs['sweep_keep'][1]))
         emit(config=name, row='outputs', bitwise_equal=eq, pred_absmax=float(outs['baseline'][0].abs().max()))
         assert all(eq.values()), eq
+        if 'predictor_graph_report' in rows:                # the two reports say the same (TNS: another order of fp64 additions)
+            same = all({**d, 'tns': 0} == {**h, 'tns': 0} and abs(d['tns'] - h['tns']) <= 1e-9 * max(1.0, abs(h['tns']))
+                       for d, h in zip(last['device'], last['host']))
+            emit(config=name, row='reports', equal=same, k=a.report, wns=[d['wns'] for d in last['device']],
+                 tns=[d['tns'] for d in last['device']], violations=[d['violations'] for d in last['device']])
+            assert same
         # launches, in a pass of its own
         for nm in [n for n in names if n != 'predictor_graph']:
             prof = profile(rows[nm])
@@ -180,6 +212,7 @@ def main():
     ap.add_argument('--paths', type=int, default=0, help='paths per design (0: all)')
     ap.add_argument('--reps', type=int, default=30)
     ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--report', type=int, default=0, help='k of the timing report rows (0: none)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
