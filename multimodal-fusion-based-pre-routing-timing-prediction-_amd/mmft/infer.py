@@ -70,11 +70,16 @@ class Predictor:
                           kernel (mmft.report) on the predictions and the endpoints' required times, as the last launch of
                           the call - inside the replayed graph in bf16 mode; report() decodes the last call's buffers.
                           Regression task only.  predict() returns what it returns without it
+    placement             True: the path masks follow the pins.  Every design carries placement data
+                          (placement.attach_placement: path nodes, pin coordinates, masks rasterised from them); the masked
+                          projection is computed from those tables (placement.placed_fc) instead of the static masks, and
+                          update(i, pin_x=..., pin_y=...) moves design i's pins in place - inside the replayed graph too.
+                          Predictions are bitwise those of placement=False until a pin moves.  Needs pmodel.fcn and a CNN
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
-                 cone=False, report=None):
+                 cone=False, report=None, placement=False):
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
@@ -97,6 +102,30 @@ class Predictor:
         self._tensors = [t for root in (pmodel, cnn) if root is not None for t in list(root.parameters()) + list(root.buffers())]
         self._replay = self._sig = self._out = None
         self._report = self._make_report(report) if report is not None else None
+        self._placed = self._make_placed(designs) if placement else None
+
+    def _make_placed(self, designs):
+        """The batch's placement tables; refuses designs without placement data and designs whose stored masks are not the
+        masks of their pins (turning the mode on then changes no prediction until a pin moves)."""
+        from . import placement as PL
+        if self.pmodel.fcn is None or self.cnn is None:
+            raise ValueError('Predictor: placement=True needs the masked projection (pmodel.fcn and a CNN)')
+        for i, d in enumerate(designs):
+            if not PL.has_placement(d):
+                raise ValueError(f'Predictor: placement=True, but design {i} carries no placement data '
+                                 f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
+        b = self.batch
+        if not b.masks.run_block or b.P > PL.MAX_CELLS:
+            raise ValueError(f'Predictor: placement=True needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; it has {b.P}')
+        placed = PL.PlacedPaths(designs, b.node_off, self.device)
+        ip, cols = (t.cpu().numpy().astype(np.int64) for t in placed.csr())
+        for i in range(b.B):
+            q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
+            if not (np.array_equal(ip[q0:q1 + 1], b.masks.host_indptr[q0:q1 + 1]) and
+                    np.array_equal(cols[ip[q0]:ip[q1]], b.masks.host_cols[ip[q0]:ip[q1]])):
+                raise ValueError(f'Predictor: the stored masks of design {i} are not the masks of its pins '
+                                 '(placement.attach_placement rebuilds them)')
+        return placed
 
     def _make_report(self, spec):
         """Everything the report launch needs that the static selection decides: the endpoints' required times, the rows of
@@ -166,7 +195,11 @@ class Predictor:
             # joined BEFORE the masked projection, as TrainStep.forward does
             cur.wait_stream(self.side)
             h_gnn.record_stream(cur)
-        h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
+        if self._placed is not None:
+            from .placement import placed_fc
+            h_cnn = placed_fc(self._placed, paths_d, foff_d if b.B > 1 else None, feat, pm_.fcn.weight, pm_.fcn.bias, b.masks)
+        else:
+            h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
         pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
         if self._report is not None:
             from . import report as R
@@ -191,7 +224,7 @@ class Predictor:
             sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
             if self._replay is None or sig != self._sig:
                 self._sig = sig
-                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report))
+                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed))
             out = self._replay.run(self._launches)
             if out is not None:                                  # an eager or the capturing call
                 self._out = out
@@ -208,8 +241,34 @@ class Predictor:
             raise RuntimeError('Predictor.report(): predict() has not run yet')
         return R.decode(*self._report['bufs'].host()[0], endpoints=self.endpoints)
 
-    def update(self, i, cell_feat=None, net_feat=None, image=None):
+    def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None):
         """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the
         design's image shape) for design i; numpy arrays or tensors.  Copied into the resident buffers on the current stream:
-        the next predict() sees them, eager or replayed."""
-        update_design(self.batch, self._perm[i] if 0 <= i < len(self._perm) else None, i, cell_feat, net_feat, image)
+        the next predict() sees them, eager or replayed.  pin_x / pin_y (placement=True only; both or neither): new map-cell
+        coordinates of the design's pins, int32 / int64 [N_i]; any value is allowed, boxes are clamped to the map.  All
+        arguments of a call are validated before any is written."""
+        if not 0 <= i < self.batch.B:
+            raise IndexError(f'update: design {i} of {self.batch.B}')
+        pins = None
+        if pin_x is not None or pin_y is not None:
+            if self._placed is None:
+                raise ValueError('update: pin_x / pin_y need a Predictor built with placement=True')
+            if pin_x is None or pin_y is None:
+                raise ValueError('update: pin_x and pin_y go together')
+            pins = self._placed.check_pins(i, pin_x, pin_y)
+        update_design(self.batch, self._perm[i], i, cell_feat, net_feat, image)
+        if pins is not None:
+            self._placed.set_pins(i, *pins)
+
+    def masks(self, i):
+        """Host (indptr, cols) int64 of design i's current path masks: rasterised from the pins as they are now with
+        placement=True (synchronises), the design's stored masks otherwise."""
+        b = self.batch
+        if not 0 <= i < b.B:
+            raise IndexError(f'masks: design {i} of {b.B}')
+        q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
+        if self._placed is not None:
+            ip, cols = (t.cpu().numpy().astype(np.int64) for t in self._placed.csr())
+        else:
+            ip, cols = b.masks.host_indptr, b.masks.host_cols
+        return ip[q0:q1 + 1] - ip[q0], cols[ip[q0]:ip[q1]].copy()

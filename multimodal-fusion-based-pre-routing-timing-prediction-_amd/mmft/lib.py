@@ -1,5 +1,5 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
-include/mmft_report.h, called through `ext`).
+include/mmft_report.h, called through `ext`, and in include/mmft_place.h, called through `place`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -16,6 +16,7 @@ PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('MMFT_LIB') or os.path.join(PKG_DIR, 'lib', 'libmmft_hip.so')      # MMFT_LIB: another build of the same library (A/B runs)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft.h')
 EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report.h')      # extensions: not the reference's path
+PLACE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_place.h')     # masks that follow a placement
 
 _lib = None
 
@@ -59,6 +60,11 @@ def header_decls():
 def ext_decls():
     """The same for include/mmft_report.h, the entry points beyond the reference's hot path (called through `ext`)."""
     return _parse_header(EXT_HEADER_PATH)
+
+
+def place_decls():
+    """The same for include/mmft_place.h (called through `place`)."""
+    return _parse_header(PLACE_HEADER_PATH)
 
 
 def header_symbols():
@@ -140,6 +146,26 @@ def ext(name, *args):
             raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
         return None
     if rc < 0:
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_PLACE = {}
+
+
+def place(name, *args):
+    """Call an `int mmft_*(...)` entry point of include/mmft_place.h, bound from that header on first use; raises like `call`
+    and returns the code (0), as `ext` returns a query's value."""
+    fn = _PLACE.get(name)
+    if fn is None:
+        decls = place_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {PLACE_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _PLACE[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
     return int(rc)
 

@@ -1,0 +1,224 @@
+"""Path masks that follow a moving placement (include/mmft_place.h).
+
+A path mask is the union of the drive -> sink bounding boxes along a path, in map cells
+(src/verilog_parser_asap7.py:1302-1369): a pure function of the path's nodes and the pins' coordinates.  A design may carry
+that placement data - `path_nodes` [num_paths, maxlen] (-1 padded, the layout prep.trace_critical_paths emits), `path_lens`
+[num_paths], `pin_x` / `pin_y` [N] map-cell coordinates - next to its rasterised `mask_indptr` / `mask_cols`:
+
+    rasterize_host / runs_host   the mask rule and its run form in numpy (host side: attach_placement, tests, tools)
+    attach_placement             validates the four arrays, sets them on a design and rebuilds its masks from them
+    PlacedPaths                  the device tables of a batch of such designs; set_pins() moves a design's pins in place
+    placed_fc                    the masked projection computed from those tables by mmft_placed_fc_fwd: bitwise what
+                                 fusion.masked_fc gives on masks rasterised from the same pins, with nothing to rebuild
+"""
+import numpy as np
+import torch
+
+from . import fusion, lib
+
+FIELDS = ('path_nodes', 'path_lens', 'pin_x', 'pin_y')
+MAX_CELLS = 65536          # the kernel's LDS bitmap (mmft_place.h)
+
+
+def has_placement(design):
+    return all(getattr(design, k, None) is not None for k in FIELDS)
+
+
+def _bitmaps(path_nodes, path_lens, pin_x, pin_y, map_x, map_y):
+    """Per path the bool [map_x, map_y] union of its boxes: the mask rule of include/mmft_place.h."""
+    nodes, lens = np.asarray(path_nodes), np.asarray(path_lens)
+    px, py = np.asarray(pin_x).astype(np.int64), np.asarray(pin_y).astype(np.int64)
+    if nodes.ndim != 2 or lens.shape != (nodes.shape[0],) or px.shape != py.shape or px.ndim != 1:
+        raise ValueError('path_nodes [num_paths, maxlen], path_lens [num_paths] and pin_x / pin_y [N] expected')
+    maxlen = nodes.shape[1]
+    for q in range(nodes.shape[0]):
+        bm = np.zeros((map_x, map_y), dtype=bool)
+        n = min(int(lens[q]), maxlen)
+        for j in range(n - 1):
+            a, b = int(nodes[q, j]), int(nodes[q, j + 1])
+            x1, x2 = max(min(px[a], px[b]), 0), min(max(px[a], px[b]), map_x - 1)
+            y1, y2 = max(min(py[a], py[b]), 0), min(max(py[a], py[b]), map_y - 1)
+            if x1 <= x2 and y1 <= y2:
+                bm[x1:x2 + 1, y1:y2 + 1] = True
+        yield bm
+
+
+def rasterize_host(path_nodes, path_lens, pin_x, pin_y, map_x, map_y):
+    """(indptr int64 [num_paths + 1], cols int64 [nnz], ascending per row) of the path masks; column = x * map_y + y."""
+    indptr, cols = [0], []
+    for bm in _bitmaps(path_nodes, path_lens, pin_x, pin_y, int(map_x), int(map_y)):
+        c = np.flatnonzero(bm.reshape(-1))
+        cols.append(c)
+        indptr.append(indptr[-1] + c.shape[0])
+    return np.asarray(indptr, dtype=np.int64), (np.concatenate(cols) if cols else np.zeros(0)).astype(np.int64)
+
+
+def runs_host(path_nodes, path_lens, pin_x, pin_y, map_x, map_y):
+    """(run_ptr [num_paths + 1], run_start [R], run_len [R]) int64 with S = fusion.RUN_BLOCK: per path the groups of
+    consecutive ones of each S-bit block of its bitmap, ascending - the runs the kernel numbers, and those
+    fusion._runs_from_csr derives from the CSR."""
+    S, P = fusion.RUN_BLOCK, int(map_x) * int(map_y)
+    if not S or P % S:
+        raise ValueError(f'runs_host: the map holds {P} cells, no multiple of the prefix block of {S}')
+    ptr, starts, lens = [0], [], []
+    for bm in _bitmaps(path_nodes, path_lens, pin_x, pin_y, int(map_x), int(map_y)):
+        v = bm.reshape(P // S, S)
+        prev = np.zeros_like(v); prev[:, 1:] = v[:, :-1]          # v << 1: the cell below, inside the block
+        nxt = np.zeros_like(v); nxt[:, :-1] = v[:, 1:]
+        s, e = np.flatnonzero((v & ~prev).reshape(-1)), np.flatnonzero((v & ~nxt).reshape(-1))
+        starts.append(s)
+        lens.append(e - s + 1)
+        ptr.append(ptr[-1] + s.shape[0])
+    cat = lambda xs: (np.concatenate(xs) if xs else np.zeros(0)).astype(np.int64)
+    return np.asarray(ptr, dtype=np.int64), cat(starts), cat(lens)
+
+
+def _int_array(x, name, ndim):
+    a = np.asarray(x)
+    if a.dtype.kind not in 'iu' or a.ndim != ndim:
+        raise ValueError(f'attach_placement: {name} must be an integer array with {ndim} dimension(s), got {a.dtype} {a.shape}')
+    a = a.astype(np.int64)
+    if a.size and (a.max() >= 2 ** 31 or a.min() < -2 ** 31):
+        raise ValueError(f'attach_placement: {name} does not fit 32-bit integers')
+    return a
+
+
+def attach_placement(design, path_nodes, path_lens, pin_x, pin_y):
+    """Give `design` its placement data and rebuild `mask_indptr` / `mask_cols` from it (rasterize_host), so that the
+    design is self-consistent.  path_nodes holds the design's own node ids, in [0, N) for j < min(len, maxlen) and -1
+    elsewhere; a length above maxlen marks a truncated row (prep.trace_critical_paths) and is clipped.  Coordinates may
+    be any 32-bit int: boxes are clamped to the map.  Nothing is set unless everything is valid.  Returns the design."""
+    nodes, lens = _int_array(path_nodes, 'path_nodes', 2), _int_array(path_lens, 'path_lens', 1)
+    px, py = _int_array(pin_x, 'pin_x', 1), _int_array(pin_y, 'pin_y', 1)
+    num_paths, N = int(design.num_paths), int(design.N)
+    if nodes.shape[0] != num_paths or nodes.shape[1] < 1 or lens.shape != (num_paths,):
+        raise ValueError(f'attach_placement: the design has {num_paths} paths, path_nodes is {nodes.shape} and path_lens {lens.shape}')
+    if px.shape != (N,) or py.shape != (N,):
+        raise ValueError(f'attach_placement: the design has {N} nodes, pin_x is {px.shape} and pin_y {py.shape}')
+    if lens.size and lens.min() < 0:
+        raise ValueError('attach_placement: negative path length')
+    live = np.arange(nodes.shape[1])[None, :] < np.minimum(lens, nodes.shape[1])[:, None]
+    if (live & ((nodes < 0) | (nodes >= N))).any():
+        raise ValueError(f'attach_placement: a path node id outside [0, {N})')
+    if (~live & (nodes != -1)).any():
+        raise ValueError('attach_placement: entries beyond a path\'s length must be -1')
+    m = int(design.map_size)
+    indptr, cols = rasterize_host(nodes, lens, px, py, m, m)
+    design.path_nodes, design.path_lens, design.pin_x, design.pin_y = nodes, lens, px, py
+    design.mask_indptr, design.mask_cols = indptr, cols
+    return design
+
+
+def _pins(x, name, n):
+    """Tensor (host or device) of one design's coordinates, or an error; nothing is copied to a device here.  The tables
+    hold 32-bit coordinates, as attach_placement requires: int64 values are range-checked (a device tensor is read back for
+    that, which synchronises - pass int32 to avoid it)."""
+    t = torch.from_numpy(x) if isinstance(x, np.ndarray) else x
+    if not torch.is_tensor(t):
+        raise TypeError(f'{name} must be a numpy array or a tensor')
+    if t.dtype not in (torch.int32, torch.int64):
+        raise TypeError(f'{name} must be int32 or int64, got {t.dtype}')
+    if tuple(t.shape) != (n,):
+        raise ValueError(f'{name} has shape {tuple(t.shape)}, the design has {n} pins')
+    if t.dtype == torch.int64 and n and (int(t.max()) >= 2 ** 31 or int(t.min()) < -2 ** 31):
+        raise ValueError(f'{name} does not fit 32-bit integers')
+    return t
+
+
+class PlacedPaths:
+    """Device tables of a batch of designs that carry placement data, at static addresses.
+
+    nodes [total paths, maxlen] int32   path nodes, shifted by the design's offset in `node_off` (the caller's numbering:
+                                        the location tables are their own and do not follow DesignBatch's renumbering),
+                                        -1 padded to the largest maxlen of the designs
+    lens [total paths], loc_x / loc_y [total nodes] int32
+    Rows follow the designs' paths one after another, as PathMasks.batch numbers them."""
+
+    def __init__(self, designs, node_off, device):
+        missing = [i for i, d in enumerate(designs) if not has_placement(d)]
+        if missing:
+            raise ValueError(f'PlacedPaths: design {missing[0]} carries no placement data (placement.attach_placement)')
+        self.node_off = np.asarray(node_off, dtype=np.int64)
+        if self.node_off.shape != (len(designs) + 1,) or any(int(self.node_off[i + 1] - self.node_off[i]) != int(d.N) for i, d in enumerate(designs)):
+            raise ValueError('PlacedPaths: node_off must hold the designs\' node offsets')
+        sizes = {int(d.map_size) for d in designs}
+        if len(sizes) != 1:
+            raise ValueError(f'PlacedPaths: one map size expected, got {sorted(sizes)}')
+        self.map_x = self.map_y = sizes.pop()
+        self.P = self.map_x * self.map_y
+        self.B = len(designs)
+        self.maxlen = max(int(np.asarray(d.path_nodes).shape[1]) for d in designs)
+        self.path_off = np.concatenate([[0], np.cumsum([d.num_paths for d in designs])]).astype(np.int64)
+        nodes = np.full((int(self.path_off[-1]), self.maxlen), -1, dtype=np.int64)
+        lens = np.zeros(int(self.path_off[-1]), dtype=np.int64)
+        for i, d in enumerate(designs):
+            pn, pl = np.asarray(d.path_nodes, dtype=np.int64), np.asarray(d.path_lens, dtype=np.int64)
+            if pn.ndim != 2 or pn.shape[0] != d.num_paths or pl.shape != (d.num_paths,) or \
+                    np.asarray(d.pin_x).shape != (d.N,) or np.asarray(d.pin_y).shape != (d.N,):
+                raise ValueError(f'PlacedPaths: design {i}: placement data does not fit the design')
+            # a length above the design's own maxlen marks a truncated row: clipped HERE, to the design's row width - the
+            # device clips to the batch's common maxlen only, and would read the -1 padding of a narrower design as nodes
+            pl = np.minimum(pl, pn.shape[1])
+            live = np.arange(pn.shape[1])[None, :] < pl[:, None]
+            if (pl < 0).any() or (live & ((pn < 0) | (pn >= d.N))).any():
+                raise ValueError(f'PlacedPaths: design {i}: a path node id outside [0, {d.N}) inside its row\'s length')
+            nodes[self.path_off[i]:self.path_off[i + 1], :pn.shape[1]] = np.where(live, pn + self.node_off[i], -1)
+            lens[self.path_off[i]:self.path_off[i + 1]] = pl
+        self.device = torch.device(device)
+        i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64).astype(np.int32)).to(self.device)
+        self.nodes = i32(nodes)
+        self.lens = i32(lens)
+        self.loc_x = i32(np.concatenate([np.asarray(d.pin_x) for d in designs]))
+        self.loc_y = i32(np.concatenate([np.asarray(d.pin_y) for d in designs]))
+
+    def check_pins(self, i, pin_x, pin_y):
+        """(x, y) as validated tensors for set_pins; raises without writing anything."""
+        if not 0 <= i < self.B:
+            raise IndexError(f'design {i} of {self.B}')
+        n = int(self.node_off[i + 1] - self.node_off[i])
+        return _pins(pin_x, 'pin_x', n), _pins(pin_y, 'pin_y', n)
+
+    def set_pins(self, i, pin_x, pin_y):
+        """New map-cell coordinates of design i's pins (int32 / int64 [N_i], numpy or tensor), copied into the design's
+        slice of loc_x / loc_y on the current stream: addresses stay.  Validated before anything is written."""
+        x, y = self.check_pins(i, pin_x, pin_y)
+        a, b = int(self.node_off[i]), int(self.node_off[i + 1])
+        self.loc_x[a:b].copy_(x.to(torch.int32), non_blocking=True)
+        self.loc_y[a:b].copy_(y.to(torch.int32), non_blocking=True)
+
+    def csr(self):
+        """(indptr int32 [paths + 1], cols int32 [nnz]) on the device: the masks of the pins as they are now, rasterised by
+        prep.rasterize_path_masks (inspection, saving; synchronises)."""
+        from . import prep
+        return prep.rasterize_path_masks(self.nodes, self.lens, self.loc_x, self.loc_y, self.map_x, self.map_y)
+
+
+def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None):
+    """fcn(mask rows * feat_map) with the mask of every batch row taken from `placed`'s current pins.
+
+    paths int32 [T] (rows of placed.nodes), f_off int32 [T] or None (one design), feat_map [B, P], w [Dout, P], b [Dout] or
+    None; `masks` is the batch's PathMasks and only says how the prefix table is laid out (B, P, run_block): the table comes
+    from fusion.masked_fc_prefix - same cache, same launches as fusion.masked_fc.  stats: optional int32 [T, 2], filled with
+    (cells, runs) of each row's mask.  Forward only."""
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (feat_map, w, b)):
+        raise RuntimeError('placed_fc is forward only: call it under torch.no_grad() (moving masks have no backward)')
+    if masks.P != placed.P or masks.B != placed.B:
+        raise ValueError(f'placed_fc: masks are {masks.B} x {masks.P}, the placement tables {placed.B} x {placed.P}')
+    if w.dim() != 2 or w.shape[1] != masks.P or w.shape[0] % 4:
+        raise ValueError(f'placed_fc: fcn weight {tuple(w.shape)} does not fit {masks.P} map cells / a multiple of 4 outputs')
+    if placed.P > MAX_CELLS:
+        raise ValueError(f'placed_fc: maps above {MAX_CELLS} cells are not supported')
+    if paths.dtype != torch.int32 or not paths.is_contiguous() or paths.device != placed.nodes.device or \
+            (f_off is not None and (f_off.dtype != torch.int32 or not f_off.is_contiguous() or f_off.numel() != paths.numel())):
+        raise ValueError('placed_fc: paths / f_off must be contiguous int32 tensors of one length on the tables\' device')
+    GP = fusion.masked_fc_prefix(feat_map, w, masks)
+    if GP is None:
+        raise ValueError('placed_fc: the masks have no run form (the map must hold a multiple of fusion.RUN_BLOCK cells, '
+                         'fusion.USE_RUNS on, contiguous feat_map and weight)')
+    T, Dout = paths.numel(), w.shape[0]
+    if stats is not None and (stats.dtype != torch.int32 or tuple(stats.shape) != (T, 2) or not stats.is_contiguous()):
+        raise ValueError('placed_fc: stats must be a contiguous int32 [T, 2] tensor')
+    out = torch.empty((T, Dout), dtype=torch.float32, device=GP.device)
+    lib.place('mmft_placed_fc_fwd', placed.nodes, placed.lens, placed.maxlen, placed.loc_x, placed.loc_y, placed.map_x,
+              placed.map_y, paths, f_off, T, GP, b, out, Dout, Dout, masks.run_block, stats, *lib.stream_args(GP))
+    return out

@@ -13,19 +13,22 @@ from .synth import SynthDesign
 
 _FIELDS = ('net_src', 'net_dst', 'cell_src', 'cell_dst', 'cell_feat', 'net_feat', 'path2level', 'path2endpoint',
            'arrival_time', 'required_time', 'label', 'is_end', 'mask_indptr', 'mask_cols', 'critical_paths', 'image')
+# optional: the placement data of mmft.placement (path nodes and pin coordinates); written and restored when present
+_PLACEMENT_FIELDS = ('path_nodes', 'path_lens', 'pin_x', 'pin_y')
 
 
 def save_design(path, d):
     """Write a design (SynthDesign or anything with the same attributes) to `path` (.npz)."""
     lvl_ptr = np.concatenate([[0], np.cumsum([len(x) for x in d.levels])]).astype(np.int64)
     tgt_ptr = np.concatenate([[0], np.cumsum([len(x) for x in d.level_targets])]).astype(np.int64)
+    placement = {k: np.asarray(getattr(d, k)) for k in _PLACEMENT_FIELDS} if all(getattr(d, k, None) is not None for k in _PLACEMENT_FIELDS) else {}
     np.savez_compressed(
         path, version=np.int64(1), N=np.int64(d.N), L=np.int64(d.L), map_size=np.int64(d.map_size), tile=np.int64(d.tile),
         level_ptr=lvl_ptr, level_nodes=np.concatenate([np.asarray(x, dtype=np.int64) for x in d.levels]),
         target_ptr=tgt_ptr,
         level_targets=np.concatenate([np.asarray(x, dtype=np.int64) for x in d.level_targets] + [np.zeros(0, np.int64)]),
         level_paths=np.concatenate([np.asarray(x, dtype=np.int64) for x in d.level_paths] + [np.zeros(0, np.int64)]),
-        **{k: np.asarray(getattr(d, k)) for k in _FIELDS})
+        **{k: np.asarray(getattr(d, k)) for k in _FIELDS}, **placement)
 
 
 def load_design(path):
@@ -40,6 +43,9 @@ def load_design(path):
     d.level_paths = [z['level_paths'][tp[i]:tp[i + 1]] for i in range(d.L)]
     for k in _FIELDS:
         setattr(d, k, z[k])
+    if all(k in z.files for k in _PLACEMENT_FIELDS):
+        for k in _PLACEMENT_FIELDS:
+            setattr(d, k, z[k])
     return d
 
 

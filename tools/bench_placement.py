@@ -1,0 +1,166 @@
+"""What it costs to follow moving pins, in bf16 math mode at config B shapes (8 designs x 65 536 nodes, 128 x 128 map).
+
+    python tools/bench_placement.py [--designs 8] [--paths 1350] [--reps 20] [--rounds 7] [--rebuilds 3] [--out FILE]
+    python tools/bench_placement.py --trace        (the launches alone, for a kernel trace of its own)
+
+The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
+  rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
+                    (placement.rasterize_host in numpy / prep.rasterize_path_masks on the device), then a new Predictor
+                    (PathMasks tables, DesignBatch) and its first two predict() calls (eager, capture).  Host clock around
+                    work that ends in a device synchronise; `rebuilds` repetitions
+  update_predict    Predictor(placement=True): update(i, pin_x, pin_y) for every design, then a replayed predict()
+  predict_placed / predict_static   a replayed predict() with placement=True / False on unmoved pins
+The last three are timed with device events around `reps` back-to-back calls and alternate inside each of `rounds` rounds;
+per row the median and min .. max over the rounds.  The predictions of update_predict must equal, bitwise, those of the
+Predictor rebuilt on the moved pins; predict_placed must equal predict_static.  One JSON line per row.
+
+--trace runs eager predict() calls of both Predictors and PlacedPaths.csr() (the two path_mask_kernel launches), nothing
+else: run it under a kernel tracer to read placed_fc_fwd_kernel next to masked_fc_fwd_runs_kernel and path_mask_kernel.
+Needs a GPU."""
+import argparse
+import copy
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd')
+for p in (ROOT, PKG, os.path.join(ROOT, 'tests')):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from mmft import lib, prep                                         # noqa: E402
+from mmft import placement as PL                                   # noqa: E402
+from mmft.infer import Predictor                                   # noqa: E402
+from mmft.synth import config_design                               # noqa: E402
+from mmft.train import build_models                                # noqa: E402
+from place_cases import placed, move                               # noqa: E402
+
+
+def timed(fn, reps):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(reps):
+        fn()
+    e1.record()
+    e1.synchronize()
+    return e0.elapsed_time(e1) / reps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--designs', type=int, default=8)
+    ap.add_argument('--paths', type=int, default=1350, help='endpoints per design (0: all)')
+    ap.add_argument('--reps', type=int, default=20)
+    ap.add_argument('--rounds', type=int, default=7)
+    ap.add_argument('--rebuilds', type=int, default=3)
+    ap.add_argument('--trace', action='store_true')
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs a GPU'
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def emit(**row):
+        lines.append(json.dumps(row))
+        print(lines[-1], flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+
+    designs = [placed(config_design('B', i), seed=100 + i) for i in range(a.designs)]
+    rng = np.random.default_rng(6)
+    ids = [np.sort(rng.permutation(d.num_paths)[:a.paths]) if a.paths else np.arange(d.num_paths) for d in designs]
+    pins = [[(d.pin_x, d.pin_y) for d in designs], [move(d, seed=200 + i, frac=0.25) for i, d in enumerate(designs)]]
+    m = designs[0].map_size
+    pmodel, cnn = build_models(map_size=m, device=dev, seed=9294)
+    with torch.no_grad():
+        cnn.outc.conv[0].bias.fill_(2.0)        # a feature map that is not all zero behind the last ReLU: the masks matter to the outputs compared
+    with lib.math_mode('bf16'), torch.no_grad():
+        static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+        moving = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True)
+        if a.trace:
+            eager = [Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False, placement=pl) for pl in (False, True)]
+            for _ in range(5):
+                for q in eager:
+                    q.predict()
+                moving._placed.csr()
+            torch.cuda.synchronize()
+            return
+        for _ in range(3):
+            ys, ym = static.predict()[0].clone(), moving.predict()[0].clone()
+        assert torch.equal(ys, ym)
+        cells = np.concatenate([np.diff(d.mask_indptr) for d in designs])
+        runs = np.diff(PL.runs_host(designs[0].path_nodes, designs[0].path_lens, designs[0].pin_x, designs[0].pin_y, m, m)[0])
+        emit(row='shapes', designs=a.designs, map=m, rows=int(sum(len(i) for i in ids)), paths=int(cells.shape[0]), maxlen=int(designs[0].path_nodes.shape[1]),
+             cells_per_path_mean=float(cells.mean()), cells_per_path_max=int(cells.max()), runs_per_path_mean_design0=float(runs.mean()))
+
+        # (a) follow a move by rebuilding
+        def rebuild(how):
+            t0 = time.perf_counter()
+            new = []
+            for d, (x, y) in zip(designs, pins[1]):
+                e = copy.copy(d)
+                e.pin_x, e.pin_y = x, y
+                if how == 'host':
+                    e.mask_indptr, e.mask_cols = PL.rasterize_host(d.path_nodes, d.path_lens, x, y, m, m)
+                else:
+                    i32 = lambda v: torch.from_numpy(np.asarray(v).astype(np.int32)).to(dev)
+                    ip, cols = prep.rasterize_path_masks(i32(d.path_nodes), i32(d.path_lens), i32(x), i32(y), m, m)
+                    e.mask_indptr, e.mask_cols = ip.cpu().numpy().astype(np.int64), cols.cpu().numpy().astype(np.int64)
+                new.append(e)
+            t1 = time.perf_counter()
+            q = Predictor(pmodel, cnn, new, dev, path_ids_per_design=ids)
+            t2 = time.perf_counter()
+            q.predict()
+            y = q.predict()[0].clone()
+            torch.cuda.synchronize()
+            return y, (t1 - t0, t2 - t1, time.perf_counter() - t2)
+        rebuilt = None
+        for how in ('host', 'device'):
+            parts = []
+            for _ in range(a.rebuilds):
+                rebuilt, p3 = rebuild(how)
+                parts.append(p3)
+            tot = [sum(p) for p in parts]
+            emit(row='rebuild_' + how, repetitions=a.rebuilds, s_median=statistics.median(tot), s_min=min(tot), s_max=max(tot),
+                 s_rasterise_median=statistics.median(p[0] for p in parts), s_predictor_median=statistics.median(p[1] for p in parts),
+                 s_two_predicts_median=statistics.median(p[2] for p in parts))
+
+        # (b), (c)
+        flip = [0]
+
+        def update_predict():
+            flip[0] ^= 1
+            for i, (x, y) in enumerate(dev_pins[flip[0]]):
+                moving.update(i, pin_x=x, pin_y=y)
+            return moving.predict()[0]
+        dev_pins = [[(torch.from_numpy(x.astype(np.int32)).to(dev), torch.from_numpy(y.astype(np.int32)).to(dev)) for x, y in ps] for ps in pins]
+        flip[0] = 0
+        followed = update_predict().clone()                              # pins[1]
+        emit(row='outputs', update_equals_rebuild=bool(torch.equal(followed, rebuilt)), placed_equals_static=bool(torch.equal(ys, ym)),
+             moved_differs=bool(not torch.equal(followed, ys)))
+        assert torch.equal(followed, rebuilt)
+        unmoved = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True)
+        for _ in range(3):
+            unmoved.predict()
+        rows = {'update_predict': update_predict, 'predict_placed': lambda: unmoved.predict()[0], 'predict_static': lambda: static.predict()[0]}
+        for fn in rows.values():
+            timed(fn, a.reps)
+        ms = {nm: [] for nm in rows}
+        for _ in range(a.rounds):
+            for nm, fn in rows.items():
+                ms[nm].append(timed(fn, a.reps))
+        for nm in rows:
+            emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=statistics.median(ms[nm]), ms_min=min(ms[nm]), ms_max=max(ms[nm]))
+        assert torch.equal(unmoved.predict()[0], static.predict()[0])
+
+
+if __name__ == '__main__':
+    main()
