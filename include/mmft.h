@@ -148,7 +148,8 @@ int mmft_level_fwd_bf16(float* h, const float* pre, long long ld, int D, const i
  * contiguous row ranges): slots[v] = int[8] = the rows of h to read for v's four in-edges (< 0: no edge) and the rows of
  * `pre` to add (< 0: the edge's value is the h row itself; >= 0: relu(h[hrow] + pre[prow]), the net of level l - 1
  * recomputed from its single driver); net_driver[u] = the driver row of net u.  Workgroup b gathers + transforms cell rows
- * 16 b .. and writes net rows 16 b .. of level l - 1 (src/model.py:88-116,138-146). */
+ * bm b .. bm b + bm - 1 and writes net rows bm b .. of level l - 1, bm = 16, or 32 from 6144 rows in either level on
+ * (src/model.py:88-116,138-146). */
 int mmft_level_fwd_slots(float* h, const float* pre, long long ld, int D, const int* slots, const int* net_driver, int net_row0,
                          int n_net, int cell_row0, int n_cell, float* A, float* LSE, const void* w1_bf16, const float* b1,
                          const void* w2_bf16, const float* b2, float* hid_out, long long ldhid, int relu,

@@ -11,7 +11,12 @@
 //   * `ic_drv` (optional, one int per cell in-edge, built on the host next to the CSR): the single driver of the net
 //     behind the edge, so that the chain is ic_ptr -> (ic_idx, ic_drv) -> rows;
 //   * FOUR edges are requested together, their index loads first, then their row loads, and the softmax recurrence
-//     consumes them in edge order (same arithmetic, same order: bitwise equal to the serial form).
+//     consumes them in edge order (same arithmetic, same order).  The serial form (no `ic_drv`) is NOT bitwise this one:
+//     max, sum and LSE come out equal, the weighted sum differs in its last bits on rows of two and more edges (<= 5e-7
+//     absolute on values near 2; `acc * scale + p * x` may be contracted around either product, and the compiler chooses
+//     per instantiation).  Both sit at 1e-7 of the fp64 value (tests/test_level_fwd_gpu.py judges each on its own); the
+//     forms that must agree bit for bit - the slot form (its own copy of this recurrence), the fused kernel and the two
+//     kernels as the sweep calls them - are all given `ic_drv`.
 #pragma once
 #include "common.h"
 

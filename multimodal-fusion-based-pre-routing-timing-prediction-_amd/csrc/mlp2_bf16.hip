@@ -255,8 +255,9 @@ __global__ void __launch_bounds__(512) level_fwd_bf16_kernel(LevelFwdArgs<KEEP> 
 //   * the read-modify-write operand h[v] of the second epilogue is requested at kernel entry, next to the first layer's
 //     weight fragments, instead of behind the second MFMA phase;
 //   * the net rows of level l - 1 are no longer separate workgroups (504 cell tiles + 504 net blocks on 512 workgroup
-//     slots = two rounds, the second one waiting for the first): workgroup b also writes net rows 16 b .. 16 b + 15,
-//     their loads issued ahead of the gather through `net_drv` (the single driver of every net, static).
+//     slots = two rounds, the second one waiting for the first): workgroup b also writes net rows BM b .. BM b + BM - 1
+//     (BM = 16 RB: 16, or 32 from 6144 rows in either level on, see level_slots_rb), their loads issued ahead of the gather
+//     through `net_drv` (the single driver of every net, static).
 struct LevelSlotsCommon {
   float* h;
   const float* pre;

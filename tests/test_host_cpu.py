@@ -513,7 +513,7 @@ def test_scratch_owner_scopes_workspace_to_its_owner(monkeypatch):
 # Test files that call kernels one at a time against a reference of the same operation (the others drive whole models or steps).
 KERNEL_LEVEL_FILES = ('test_kernels_gpu.py', 'test_head_kernels_gpu.py', 'test_graph_kernels_gpu.py', 'test_cnn_layers_gpu.py',
                       'test_bf16_gpu.py', 'test_unet16_gpu.py', 'test_unet_eval_gpu.py', 'test_fold_gpu.py', 'test_infer_gpu.py',
-                      'test_prep_gpu.py', 'test_level_bwd_gpu.py')
+                      'test_prep_gpu.py', 'test_level_bwd_gpu.py', 'test_level_fwd_gpu.py')
 # Entry points that launch no kernel of their own (size / capability queries, the launch profiler, process settings): the test
 # that covers each indirectly, and why that is enough.
 ABI_COVERED_INDIRECTLY = {
