@@ -5,7 +5,7 @@
 // times per step (second forward GEMM, weight gradient of layer 2, fused first-layer gradients): 4 x 111 us forward,
 // 2 x (120 + 103) us backward, all of it HBM time.  fin is 36 / 2: recomputing H costs 1-5 % of the MLP's flops, so
 //   * forward  (mmft_mlp2_feat_fwd_bf16): one kernel per MLP reads X, keeps the 64 x 256 hidden tile in LDS as bf16 and
-//     writes only the output rows;
+//     writes only the output rows; its MASKED instantiation (mmft_mlp2_feat_fwd_bf16_masked) does so for flagged rows only;
 //   * backward (mmft_mlp2_feat_bwd_bf16): one kernel per MLP reads G (gradient of the output rows) and X, recomputes
 //     H = relu(X W1^T + b1) with the forward's instruction sequence (bitwise the forward's H, so the ReLU mask agrees),
 //     forms dH = (G W2) * (H > 0) in registers and accumulates all four gradients
@@ -17,6 +17,7 @@
 #include <stdlib.h>
 #include "mlp_tile_bf16.h"
 #include "tr_read.h"
+#include "../../include/mmft_incr.h"
 
 namespace mmft {
 
@@ -45,15 +46,38 @@ struct FeatFwdArgs {
   float* out;
   long long ldout;
   int relu_out;
+  const unsigned char* active;   // MASKED only: one flag per node
 };
 
-template <int KS>   // K steps of 32 for the first layer (fin <= 32 KS)
+// MASKED (mmft_mlp2_feat_fwd_bf16_masked, include/mmft_incr.h): only rows whose flag is set are stored.  Every wave reads the
+// 64 flags of a tile itself and takes the ballot: the same 64 bits in all eight waves (nobody writes the flags while the kernel
+// runs), so the choice of the tiles that run is uniform over the workgroup and every barrier below is reached by all of it.
+// A tile without a flag costs that one load.  The tiles that run are computed exactly as by MASKED = false - rows are
+// independent in both GEMMs - and only the store is predicated.
+template <int KS, bool MASKED>   // K steps of 32 for the first layer (fin <= 32 KS)
 __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
   constexpr int BM = 64, RT = BM / 16, XS = KS * 32 + 8, HS = L2_HD + 8;
   __shared__ __attribute__((aligned(16))) unsigned short xs[BM * XS];
   __shared__ __attribute__((aligned(16))) unsigned short hs[BM * HS];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int r16 = lane & 15, q = lane >> 4;
+  const int ntiles = (a.n + BM - 1) / BM;
+  // the first tile at or after t (in this workgroup's stride) that runs, and its rows' flags
+  auto next_tile = [&](int t, unsigned long long& flags) -> int {
+    if constexpr (MASKED) {
+      for (; t < ntiles; t += (int)gridDim.x) {
+        const int m = t * BM + lane;
+        flags = __ballot(m < a.n && a.active[a.row0 + m] != 0);
+        if (flags) break;
+      }
+    }
+    return t;
+  };
+  unsigned long long flags = ~0ull;
+  int tile = next_tile(blockIdx.x, flags);
+  if constexpr (MASKED) {
+    if (tile >= ntiles) return;      // nothing to do here: not worth the weights
+  }
   bf16x8 w1f[2][KS], w2f[8];
 #pragma unroll
   for (int j = 0; j < 2; ++j)
@@ -67,7 +91,7 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
 #pragma unroll
   for (int j = 0; j < 2; ++j) b1v[j] = *reinterpret_cast<const f32x4*>(a.b1 + wave * 32 + j * 16 + q * 4);
   // The weights (164 KB of fp32) are fetched ONCE per workgroup: the grid is a few workgroups per CU and each walks
-  // tiles of 64 rows; the X elements of tile t + 1 are requested before tile t is multiplied.
+  // tiles of 64 rows; the X elements of the next tile that runs are requested before this one is multiplied.
   constexpr int NXE = BM * KS * 32 / 512;
   float xr[NXE];
   auto request = [&](int tile) {
@@ -78,9 +102,8 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
       xr[k] = (m < a.n && kk < a.fin) ? a.x[(long long)(a.row0 + m) * a.ldx + kk] : 0.f;
     }
   };
-  const int ntiles = (a.n + BM - 1) / BM;
-  if ((int)blockIdx.x < ntiles) request(blockIdx.x);
-  for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+  if (tile < ntiles) request(tile);
+  while (tile < ntiles) {
     const int m0 = tile * BM;
 #pragma unroll
     for (int k = 0; k < NXE; ++k) {
@@ -88,7 +111,9 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
       xs[(e / (KS * 32)) * XS + e % (KS * 32)] = mf_bf16(xr[k]);
     }
     __syncthreads();
-    if (tile + (int)gridDim.x < ntiles) request(tile + gridDim.x);
+    unsigned long long nflags = ~0ull;
+    const int nxt = next_tile(tile + (int)gridDim.x, nflags);
+    if (nxt < ntiles) request(nxt);
     f32x4 acc1[RT][2];
     tile_layer1<KS, RT>(acc1, w1f, xs, XS, r16, q);
 #pragma unroll
@@ -103,12 +128,17 @@ __global__ void __launch_bounds__(512) mlp2_feat_fwd_kernel(FeatFwdArgs a) {
     for (int i = 0; i < RT; ++i) {
       const int m = m0 + i * 16 + r16;
       if (m >= a.n) continue;
+      if constexpr (MASKED) {
+        if (!((flags >> (i * 16 + r16)) & 1)) continue;
+      }
       f32x4 v = acc2[i] + b2v;
       if (a.relu_out) v = relu4(v);
       *reinterpret_cast<f32x4*>(a.out + (long long)(a.row0 + m) * a.ldout + nn2) = v;
     }
     // the next deposit overwrites xs (last read before the barrier above) and the next epilogue hs (last read here)
     __syncthreads();
+    tile = nxt;
+    flags = nflags;
   }
 }
 
@@ -318,24 +348,44 @@ static inline int feat_bwd_grid(int n) {
 
 using namespace mmft;
 
-extern "C" int mmft_mlp2_feat_fwd_bf16(const float* x, long long ldx, int row0, int n, int fin, const float* w1, const float* b1,
-                                       const float* w2, const float* b2, float* out, long long ldout, int relu_out, int device,
-                                       void* stream) {
-  MMFT_REQUIRE(x && w1 && b1 && w2 && b2 && out, "mlp2_feat_fwd_bf16: null pointer");
-  MMFT_REQUIRE(n >= 0 && row0 >= 0 && fin >= 1 && fin <= 64 && ldx >= fin, "mlp2_feat_fwd_bf16: bad sizes (fin <= 64)");
+static int feat_fwd_launch(const char* what, const float* x, long long ldx, int row0, int n, int fin, const float* w1,
+                           const float* b1, const float* w2, const float* b2, float* out, long long ldout, int relu_out,
+                           const unsigned char* active, int device, void* stream) {
+  MMFT_REQUIRE(x && w1 && b1 && w2 && b2 && out, "%s: null pointer", what);
+  MMFT_REQUIRE(n >= 0 && row0 >= 0 && fin >= 1 && fin <= 64 && ldx >= fin, "%s: bad sizes (fin <= 64)", what);
   MMFT_REQUIRE(ldout % 4 == 0 && aligned16(out) && aligned16(w2) && aligned16(b1) && aligned16(b2),
-               "mlp2_feat_fwd_bf16: out / w2 / biases must be 16-byte aligned");
+               "%s: out / w2 / biases must be 16-byte aligned", what);
   if (n == 0) return MMFT_OK;
   DeviceGuard dg(device);
-  FeatFwdArgs a{x, ldx, row0, n, fin, w1, b1, w2, b2, out, ldout, relu_out};
+  FeatFwdArgs a{x, ldx, row0, n, fin, w1, b1, w2, b2, out, ldout, relu_out, active};
   const double fl = 2.0 * n * ((double)fin * L2_HD + (double)L2_HD * L2_D2), by = 4.0 * n * ((double)fin + L2_D2);
   int grid = cdiv(n, 64);
   if (grid > 768) grid = 768;                      // three workgroups per CU (43 KB of LDS each)
-  if (fin <= 32)
-    MMFT_LAUNCH("mlp2_feat_fwd_kernel", fl, by, mlp2_feat_fwd_kernel<1>, dim3(grid), dim3(512), (hipStream_t)stream, a);
+  // (flops / bytes of the masked form: the upper bound, every flag set - the flags live on the device)
+  if (active) {
+    if (fin <= 32)
+      MMFT_LAUNCH("mlp2_feat_fwd_masked_kernel", fl, by, (mlp2_feat_fwd_kernel<1, true>), dim3(grid), dim3(512), (hipStream_t)stream, a);
+    else
+      MMFT_LAUNCH("mlp2_feat_fwd_masked_kernel", fl, by, (mlp2_feat_fwd_kernel<2, true>), dim3(grid), dim3(512), (hipStream_t)stream, a);
+  } else if (fin <= 32)
+    MMFT_LAUNCH("mlp2_feat_fwd_kernel", fl, by, (mlp2_feat_fwd_kernel<1, false>), dim3(grid), dim3(512), (hipStream_t)stream, a);
   else
-    MMFT_LAUNCH("mlp2_feat_fwd_kernel", fl, by, mlp2_feat_fwd_kernel<2>, dim3(grid), dim3(512), (hipStream_t)stream, a);
-  return check_launch("mlp2_feat_fwd_bf16");
+    MMFT_LAUNCH("mlp2_feat_fwd_kernel", fl, by, (mlp2_feat_fwd_kernel<2, false>), dim3(grid), dim3(512), (hipStream_t)stream, a);
+  return check_launch(what);
+}
+
+extern "C" int mmft_mlp2_feat_fwd_bf16(const float* x, long long ldx, int row0, int n, int fin, const float* w1, const float* b1,
+                                       const float* w2, const float* b2, float* out, long long ldout, int relu_out, int device,
+                                       void* stream) {
+  return feat_fwd_launch("mlp2_feat_fwd_bf16", x, ldx, row0, n, fin, w1, b1, w2, b2, out, ldout, relu_out, nullptr, device, stream);
+}
+
+extern "C" int mmft_mlp2_feat_fwd_bf16_masked(const float* x, long long ldx, int row0, int n, int fin, const float* w1,
+                                              const float* b1, const float* w2, const float* b2, float* out, long long ldout,
+                                              int relu_out, const unsigned char* active, int device, void* stream) {
+  MMFT_REQUIRE(active, "mlp2_feat_fwd_bf16_masked: null pointer (active)");
+  return feat_fwd_launch("mlp2_feat_fwd_bf16_masked", x, ldx, row0, n, fin, w1, b1, w2, b2, out, ldout, relu_out, active, device,
+                         stream);
 }
 
 extern "C" long long mmft_mlp2_feat_bwd_workspace_bytes(int n, int fin) {

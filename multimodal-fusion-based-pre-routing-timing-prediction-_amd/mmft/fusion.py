@@ -559,8 +559,10 @@ class FlatAdam:
         self.step_count -= 1
 
     def note_replay(self):
-        """Host mirror of the device counter after a graph replay that contains the Adam launch."""
+        """Host mirror of the device counter after a graph replay that contains the Adam launch (and of the parameters'
+        epoch: the replay rewrote them as step_bucket does, behind Tensor._version)."""
         self.step_count += 1
+        gradsink.params_changed()
 
     def device_step_count(self):
         return int(self.state[0, 0].item())

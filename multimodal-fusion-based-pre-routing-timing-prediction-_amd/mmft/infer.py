@@ -11,7 +11,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import lib
+from . import gradsink, lib, ops
 from .evaluate import frozen_statistics
 from .fusion import MaskedPathMap
 from .train import DesignBatch
@@ -37,20 +37,55 @@ def _as_rows(x, name, shape, device):
     return t.to(device, non_blocking=True)
 
 
-def update_design(batch, perm, i, cell_feat=None, net_feat=None, image=None):
+def check_rows(rows, n_nodes, lengths=()):
+    """update(rows=): the node ids of a sparse feature update as a host int64 array, or an exception - TypeError unless
+    `rows` is a 1-D int64 numpy array or tensor, IndexError for an id outside [0, n_nodes), ValueError for a repeated id (the
+    rows of one call are written concurrently) and for a feature array in `lengths` (name -> its number of rows) that does
+    not hold one row per id.  Host only: no device is touched."""
+    r = rows.detach().cpu().numpy() if torch.is_tensor(rows) else rows
+    if not isinstance(r, np.ndarray) or r.dtype != np.int64:
+        raise TypeError(f'update: rows must be an int64 numpy array or tensor, got {getattr(r, "dtype", type(rows).__name__)}')
+    if r.ndim != 1:
+        raise ValueError(f'update: rows must be 1-D, got shape {r.shape}')
+    if r.size and (int(r.min()) < 0 or int(r.max()) >= n_nodes):
+        raise IndexError(f'update: rows outside the design\'s {n_nodes} nodes')
+    if np.unique(r).size != r.size:
+        raise ValueError('update: rows must be distinct')
+    for name, n in dict(lengths).items():
+        if n != r.size:
+            raise ValueError(f'update: {name} has {n} rows for {r.size} node ids in rows')
+    return np.ascontiguousarray(r)
+
+
+def update_design(batch, perm, i, cell_feat=None, net_feat=None, image=None, rows=None, seed=None, perm32=None):
     """Copy new features (rows in design i's own node order) / a new layout image of design i into the batch's static
     buffers, in place: addresses stay, the copies are ordered on the current stream.  perm = design_permutations(...)[i] as
-    an int64 tensor on the batch's device.  Everything is validated before anything is written."""
+    an int64 tensor on the batch's device.  rows (int64 node ids of design i, distinct): the feature arrays hold those rows
+    only.  seed (uint8 per row of the batch): the features go through ops.update_rows_diff, which also flags the rows that
+    changed bitwise (perm32: perm as int32, what that kernel indexes by, if the caller keeps one).  Everything is validated
+    before anything is written."""
     if not 0 <= i < batch.B:
         raise IndexError(f'update: design {i} of {batch.B}')
     nd, n = batch.graph.ndata, int(batch.node_off[i + 1] - batch.node_off[i])
+    feats = [(name, x) for name, x in (('cell_feat', cell_feat), ('net_feat', net_feat)) if x is not None]
+    if rows is not None:
+        if not feats:
+            raise ValueError('update: rows= names feature rows, but neither cell_feat nor net_feat is given')
+        rows = check_rows(rows, n, {name: x.shape[0] for name, x in feats if hasattr(x, 'shape') and len(x.shape) == 2})
+        n = rows.size
     todo = []
-    for name, x in (('cell_feat', cell_feat), ('net_feat', net_feat)):
-        if x is not None:
-            todo.append((nd[name], _as_rows(x, name, (n, nd[name].shape[1]), nd[name].device)))
+    for name, x in feats:
+        todo.append((nd[name], _as_rows(x, name, (n, nd[name].shape[1]), nd[name].device)))
     img = _as_rows(image, 'image', batch.images.shape[1:], batch.images.device) if image is not None else None
-    for dst, rows in todo:
-        dst.index_copy_(0, perm, rows)
+    if todo:
+        if seed is not None:                                 # the diff kernel takes int32 rows
+            perm = perm32 if perm32 is not None else perm.to(torch.int32)
+        where = perm if rows is None else perm[torch.from_numpy(rows).to(perm.device)]
+    for dst, new in todo:
+        if seed is not None:
+            ops.update_rows_diff(dst, new.contiguous(), seed, idx=where)
+        else:
+            dst.index_copy_(0, where, new)
     if img is not None:
         batch.images[i].copy_(img)
 
@@ -75,11 +110,27 @@ class Predictor:
                           projection is computed from those tables (placement.placed_fc) instead of the static masks, and
                           update(i, pin_x=..., pin_y=...) moves design i's pins in place - inside the replayed graph too.
                           Predictions are bitwise those of placement=False until a pin moves.  Needs pmodel.fcn and a CNN
+    incremental           True: h is kept from predict() to predict() and the netlist sweep runs only over the rows an update
+                          can have changed.  update() writes features through a kernel that flags the rows that really changed
+                          (`seed`); predict() turns them into `dirty`, their transitive fan-out (L - 1 small launches), runs the
+                          feature MLPs and the level kernels over flagged rows only and clears the seeds - inside the replayed
+                          graph too, which is the same graph for one edited cell and for a full sweep (all seeds set).  h, and
+                          with it every prediction, stays bitwise what a full sweep gives.  The sweep is a FULL one on the
+                          first predict(), after invalidate(), when the math mode, a module mode or the address of a parameter
+                          or buffer changed, and when a parameter or buffer was written in place: the sum of their autograd
+                          version counters moved, or gradsink.param_epoch() did - the project's own optimizer (FlatAdam, under
+                          TrainStep / GraphedTrainStep / EpochTrainer) writes through raw pointers and bumps that instead.  A
+                          write neither sees - `p.data.mul_()` (.data has a version counter of its own), a kernel of the
+                          caller's on .data_ptr() - needs invalidate().  Not under an outer stream capture: the decision
+                          is the host's, a caller's graph would bake it in, so predict() refuses there.  Where the sweep does not take the path on which every launch honours the row flags
+                          (fp32 mode, the attention branch, an unfolded schedule: sweep.incremental_supported) predict() runs
+                          the ordinary full sweep and `incremental_active` is False.  The U-Net, the masked projection and
+                          the head run in full on every call
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
-                 cone=False, report=None, placement=False):
+                 cone=False, report=None, placement=False, incremental=False):
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
@@ -97,10 +148,20 @@ class Predictor:
         self.endpoints = np.asarray(self._sel[4])           # the caller's numbering: node_off[design] + the design's own node id
         self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
         self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
+        self._perm32 = None                                # incremental=True: the same as int32, what update_rows_diff indexes by
         self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
         self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
         self._tensors = [t for root in (pmodel, cnn) if root is not None for t in list(root.parameters()) + list(root.buffers())]
         self._replay = self._sig = self._out = None
+        # incremental sweeps: which feature rows changed since the last predict() / which rows that predict() swept (static
+        # addresses: the replayed graph reads and writes them); whether h may be trusted, and under which signature it was made
+        self.incremental = bool(incremental) and pmodel.gnn is not None
+        self.incremental_active = False
+        self.seed = torch.zeros(b.N, dtype=torch.uint8, device=self.device) if self.incremental else None
+        self.dirty = torch.zeros(b.N, dtype=torch.uint8, device=self.device) if self.incremental else None
+        self._trusted, self._trust_sig, self._incr_ok = False, None, {}
+        if self.incremental:
+            self._perm32 = [q.to(torch.int32) for q in self._perm]
         self._report = self._make_report(report) if report is not None else None
         self._placed = self._make_placed(designs) if placement else None
 
@@ -183,12 +244,21 @@ class Predictor:
         cur = torch.cuda.current_stream(self.device)
         h_gnn = None
         if pm_.gnn is not None:
+            def sweep():
+                if not self.incremental_active:
+                    return _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
+                # dirty = fan-out of the seeds, the sweep over the dirty rows, then the seeds are spent - in this order on one
+                # stream, so a seed set by an update() after this predict() survives until the next one
+                out = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone,
+                                               incremental=(self.seed, self.dirty))
+                self.seed.zero_()
+                return out
             if self.overlap:
                 self.side.wait_stream(cur)
                 with torch.cuda.stream(self.side):
-                    h_gnn = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
+                    h_gnn = sweep()
             else:
-                h_gnn = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
+                h_gnn = sweep()
         feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
         pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
         if h_gnn is not None and self.overlap:
@@ -218,17 +288,65 @@ class Predictor:
         with self._modes_kept(), frozen_statistics(self.cnn, self.frozen_stats):
             replay = self.graphed and not lib.PROF_ON and not torch.cuda.is_current_stream_capturing() and \
                 lib.get_math_mode() == 'bf16' and self._unet_is_fused_eval()
+            if self.incremental:
+                self._begin_incremental()
             if not replay:
-                return self._launches(), self.endpoints
+                out = self._launches()
+                self._trusted = self.incremental_active
+                return out, self.endpoints
             # the graph bakes in where the model lives and which modes it ran in
             sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
+            if self.incremental:
+                sig += (self.incremental_active,)                # ... and whether its sweep is the masked one
             if self._replay is None or sig != self._sig:
                 self._sig = sig
-                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed))
+                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed,
+                                                     self.seed, self.dirty))
             out = self._replay.run(self._launches)
+            self._trusted = self.incremental_active
             if out is not None:                                  # an eager or the capturing call
                 self._out = out
             return self._out, self.endpoints
+
+    def _begin_incremental(self):
+        """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is
+        not taken, else the masked one - over every row (all seeds set, here, on the current stream) unless h is the result
+        of a predict() under the same math mode, module modes, tensor addresses and tensor contents (the sum of the autograd
+        version counters, and gradsink.param_epoch() for FlatAdam's raw-pointer steps: host side, no launch)."""
+        from . import sweep as _sweep
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('Predictor(incremental=True).predict() under an outer stream capture: whether h can be trusted is '
+                               'decided on the host per call, a captured graph would replay one decision for ever')
+        mode = lib.get_math_mode()
+        ok = self._incr_ok.get(mode)
+        if ok is None:
+            self.batch.graph.ndata['h'] = self.h
+            ok = self._incr_ok[mode] = bool(_sweep.incremental_supported(self.pmodel.gnn, self.batch.graph, self.batch.level_nodes))
+        self.incremental_active = ok
+        trusted, self._trusted = self._trusted, False            # (an exception below or in the launches: not to be trusted)
+        if not ok:
+            return
+        sig = (mode, tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules),
+               sum(t._version for t in self._tensors), gradsink.param_epoch())
+        if not trusted or sig != self._trust_sig:
+            self.seed.fill_(1)
+        self._trust_sig = sig
+
+    def invalidate(self):
+        """The next predict() sweeps every row (incremental=True; a no-op otherwise): for a change of the model that the
+        Predictor cannot see, or of h itself."""
+        self._trusted = False
+
+    def dirty_mask(self, i=None):
+        """Host uint8 copy of the rows the LAST predict() swept: the whole batch in the batch's row order, or design i in
+        the design's own node order.  All ones after a predict() that fell back to the ordinary sweep.  One device->host
+        copy here, nothing in predict()."""
+        if not self.incremental:
+            raise RuntimeError('Predictor.dirty_mask(): built without incremental=True')
+        if i is not None and not 0 <= i < self.batch.B:
+            raise IndexError(f'dirty_mask: design {i} of {self.batch.B}')
+        d = self.dirty.cpu().numpy() if self.incremental_active else np.ones(self.batch.N, dtype=np.uint8)
+        return d if i is None else d[self._perm[i].cpu().numpy()]
 
     def report(self):
         """The timing report of the LAST predict(): one dict per design (mmft.report.decode: n, n_nan, violations, wns,
@@ -241,12 +359,16 @@ class Predictor:
             raise RuntimeError('Predictor.report(): predict() has not run yet')
         return R.decode(*self._report['bufs'].host()[0], endpoints=self.endpoints)
 
-    def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None):
+    def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None, rows=None):
         """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the
         design's image shape) for design i; numpy arrays or tensors.  Copied into the resident buffers on the current stream:
-        the next predict() sees them, eager or replayed.  pin_x / pin_y (placement=True only; both or neither): new map-cell
-        coordinates of the design's pins, int32 / int64 [N_i]; any value is allowed, boxes are clamped to the map.  All
-        arguments of a call are validated before any is written."""
+        the next predict() sees them, eager or replayed.  rows (int64 node ids in design i's own numbering, distinct): the
+        feature arrays hold those rows only, float32 [len(rows), width].  pin_x / pin_y (placement=True only; both or
+        neither): new map-cell coordinates of the design's pins, int32 / int64 [N_i]; any value is allowed, boxes are clamped to
+        the map.  All arguments of a call are validated before any is written.
+        With incremental=True the features - whole tables as well - are written by a kernel that flags every row whose bits
+        changed: the next predict() sweeps the fan-out of exactly those rows.  Images and pins flag nothing (the U-Net and the
+        projection run in full anyway)."""
         if not 0 <= i < self.batch.B:
             raise IndexError(f'update: design {i} of {self.batch.B}')
         pins = None
@@ -256,7 +378,8 @@ class Predictor:
             if pin_x is None or pin_y is None:
                 raise ValueError('update: pin_x and pin_y go together')
             pins = self._placed.check_pins(i, pin_x, pin_y)
-        update_design(self.batch, self._perm[i], i, cell_feat, net_feat, image)
+        update_design(self.batch, self._perm[i], i, cell_feat, net_feat, image, rows=rows, seed=self.seed,
+                      perm32=self._perm32[i] if self._perm32 is not None else None)
         if pins is not None:
             self._placed.set_pins(i, *pins)
 

@@ -1,5 +1,6 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
-include/mmft_report.h, called through `ext`, and in include/mmft_place.h, called through `place`).
+include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, and in include/mmft_incr.h,
+called through `incr`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -17,6 +18,7 @@ LIB_PATH = os.environ.get('MMFT_LIB') or os.path.join(PKG_DIR, 'lib', 'libmmft_h
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft.h')
 EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report.h')      # extensions: not the reference's path
 PLACE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_place.h')     # masks that follow a placement
+INCR_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_incr.h')       # sweeps over the fan-out of an edit
 
 _lib = None
 
@@ -65,6 +67,11 @@ def ext_decls():
 def place_decls():
     """The same for include/mmft_place.h (called through `place`)."""
     return _parse_header(PLACE_HEADER_PATH)
+
+
+def incr_decls():
+    """The same for include/mmft_incr.h (called through `incr`)."""
+    return _parse_header(INCR_HEADER_PATH)
 
 
 def header_symbols():
@@ -164,6 +171,26 @@ def place(name, *args):
         fn = getattr(load(), name)
         fn.restype, fn.argtypes = decls[name]
         _PLACE[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_INCR = {}
+
+
+def incr(name, *args):
+    """Call an `int mmft_*(...)` entry point of include/mmft_incr.h, bound from that header on first use; raises like `call`
+    and returns the code (0), as `place` does."""
+    fn = _INCR.get(name)
+    if fn is None:
+        decls = incr_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {INCR_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _INCR[name] = fn
     rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
     if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")

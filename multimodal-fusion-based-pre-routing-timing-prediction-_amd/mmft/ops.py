@@ -439,9 +439,10 @@ def mlp2_feat_fusable(fin, HD, D2):
     return 1 <= fin <= 64 and HD == 256 and D2 == 128
 
 
-def mlp2_feat_fwd_bf16(x, rows, w1, b1, w2, b2, out, relu_out=False):
+def mlp2_feat_fwd_bf16(x, rows, w1, b1, w2, b2, out, relu_out=False, active=None):
     """out[rows] = (relu)(w2 relu(w1 x[rows] + b1) + b2) over a contiguous node range rows = (row0, n), no hidden tensor
-    stored (mmft_mlp2_feat_fwd_bf16; bf16 math mode)."""
+    stored (mmft_mlp2_feat_fwd_bf16; bf16 math mode).  active (uint8 per node): only flagged rows are computed and written,
+    bitwise as without it (mmft_mlp2_feat_fwd_bf16_masked)."""
     _rows2d(x, 'x'); _rows2d(out, 'out')
     for t, nm in ((w1, 'w1'), (b1, 'b1'), (w2, 'w2'), (b2, 'b2')):
         _chk(t, nm)
@@ -454,8 +455,31 @@ def mlp2_feat_fwd_bf16(x, rows, w1, b1, w2, b2, out, relu_out=False):
     if rt is not None:
         raise ValueError('mlp2_feat_fwd_bf16: rows must be a (row0, n) range')
     dev, st = lib.stream_args(x)
+    if active is not None:
+        lib.incr('mmft_mlp2_feat_fwd_bf16_masked', x, x.stride(0), row0, n, fin, w1, b1, w2, b2, out, out.stride(0), int(relu_out),
+                 _active(active, x.shape[0]), dev, st)
+        return out
     lib.call('mmft_mlp2_feat_fwd_bf16', x, x.stride(0), row0, n, fin, w1, b1, w2, b2, out, out.stride(0), int(relu_out), dev, st)
     return out
+
+
+def update_rows_diff(dst, src, seed, idx=None, row0=0):
+    """dst[idx[i]] (or dst[row0 + i]) = src[i], and seed[that row] = 1 where the row changed bitwise; flags are only ever set
+    (mmft_update_rows_diff).  idx: int32 device tensor of DISTINCT rows inside dst - the caller has checked both."""
+    _rows2d(dst, 'dst'); _rows2d(src, 'src')
+    _chk(seed, 'seed', torch.uint8)
+    n, width = src.shape
+    if dst.shape[1] != width or not 1 <= width <= 64:
+        raise ValueError(f'update_rows_diff: rows of {width} and {dst.shape[1]} floats (equal, at most 64)')
+    if seed.numel() != dst.shape[0] or not seed.is_contiguous():
+        raise ValueError('update_rows_diff: one uint8 flag per row of dst expected')
+    if idx is not None:
+        _idx(idx, 'idx', n)
+    elif row0 < 0 or row0 + n > dst.shape[0]:
+        raise ValueError('update_rows_diff: row range outside dst')
+    dev, st = lib.stream_args(dst)
+    lib.incr('mmft_update_rows_diff', dst, dst.stride(0), idx, int(row0), n, width, src, src.stride(0), seed, dev, st)
+    return dst
 
 
 def mlp2_feat_bwd_bf16(g, x, rows, w1, b1, w2, dw1=None, db1=None, dw2=None, db2=None):

@@ -103,6 +103,35 @@ def cone_mask(in_csrs, level_nodes, targets, out=None):
     return mark
 
 
+def fanout_cone_mask(in_csrs, level_nodes, seed, within=None, out=None):
+    """uint8[N] on the device: 1 for every node flagged in `seed` (uint8[N]) and every node in the transitive fan-out of one -
+    what an edit of the seeds' features can change.  The twin of cone_mask: `seed` is copied into `out` and one fixed-size
+    launch per level 1 .. L - 1 (mmft_fanout_cone_step, ascending) pulls the marks up, no host synchronisation, so it can run
+    inside a captured graph while the seeds change from replay to replay.  within (uint8[N], e.g. cone_mask's result): the
+    result is intersected with it - a node outside is never marked, and level 0 gets a launch as well, which only drops its
+    seeds outside `within`.  `seed` is left as it is."""
+    p = _csr_pair(in_csrs)
+    ops._chk(seed, 'seed', torch.uint8)
+    n_nodes = p[0].numel() - 1
+    if seed.numel() != n_nodes or not seed.is_contiguous():
+        raise ValueError('fanout_cone_mask: one uint8 seed flag per node expected')
+    if within is not None:
+        ops._chk(within, 'within', torch.uint8)
+        if within.numel() != n_nodes or not within.is_contiguous() or within.device != seed.device:
+            raise ValueError('fanout_cone_mask: one uint8 `within` flag per node expected, on the seeds\' device')
+    mark = out if (out is not None and out.numel() == n_nodes and out.device == seed.device and out.dtype == torch.uint8
+                   and out.is_contiguous()) else torch.empty(n_nodes, dtype=torch.uint8, device=seed.device)
+    if mark.data_ptr() == seed.data_ptr():
+        raise ValueError('fanout_cone_mask: out must not be the seed array')
+    mark.copy_(seed)
+    dev, st = lib.stream_args(mark)
+    levels = list(level_nodes)
+    for nodes in (levels if within is not None else levels[1:]):
+        idx, row0, n = ops._rowspec(nodes, n_nodes, 'level_nodes')
+        lib.incr('mmft_fanout_cone_step', idx, row0, n, p[0], p[1], p[2], p[3], within, mark, dev, st)
+    return mark
+
+
 def trace_critical_paths(in_csrs, level, endpoints, stop=None, maxlen=None):
     """paths int32[P, maxlen] (-1 padded, endpoint first) and lens int32[P]; `stop`: optional uint8 flags per node."""
     p = _csr_pair(in_csrs)

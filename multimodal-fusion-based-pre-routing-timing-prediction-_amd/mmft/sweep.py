@@ -30,7 +30,7 @@ class SweepState:
     the whole-sweep entry (_run_sweep, SweepFn) and the deferred head (model.py) overwrite theirs."""
     __slots__ = ('graph', 'h', 'N', 'D', 'Hd', 'relu', 'cell_feat', 'net_feat', 'params', 'need_grad', '_bufs',
                  'HN', 'G', 'DA', 'DHN', 'tflag', 'level_meta', 'levels', 'token', 'next_level',
-                 'bwd_active', 'complete', 'fold', 'level_lists', 'PRE', 'attn', 'wpack', 'active', 'record',
+                 'bwd_active', 'complete', 'fold', 'level_lists', 'PRE', 'attn', 'wpack', 'active', 'seed', 'record',
                  'spec_lists', 'spec_token', 'spec_tix', 'target_order', 'targets_unique',
                  'hid16', 'feat_fused', 'prep', 'row_sets', 'head_batch', '_empty_rows')
     # what a forward sweep decides and its backward needs: a replayed forward skips the code that sets these
@@ -81,6 +81,7 @@ class SweepState:
         self.attn = None                    # attention branch (flag_attn): dict(key, c12, alpha, dcp, o2i)
         self.wpack = None                   # bf16 math mode: fc_cell_neigh pre-packed as bf16 (W1, W2, W2^T, W1^T)
         self.active = None                  # uint8 per node: fan-in cone of the step's endpoints (None: every node)
+        self.seed = None                    # incremental sweep: uint8 per node, rows whose features changed (active = their fan-out)
         self.record = None                  # _SweepRecord of the schedule (static level lists), or None
         self.spec_lists = None              # speculative drop-in sweep: the level lists it ran with, its token, target rows
         self.spec_token = None
@@ -529,6 +530,34 @@ SWEEP_REPLAY = True      # drop-in loop: the speculative sweep's forward / rever
 #  6.69, + own stream 6.59, + replay 5.94)
 
 
+def _sweep_form(st, attn):
+    """Which form a forward sweep of st's schedule takes (st.levels, st.level_meta, st.fold, st.need_grad set; attn: the
+    attention branch runs) - decided HERE and nowhere else: SweepFn._forward_launches launches by it, incremental_supported
+    answers from it.
+      packed      bf16 mode and fusable widths: the level chain's MLP takes pre-packed bf16 weights
+      r0s, rc2, rn, rc   the rows of level 0, of the cell levels >= 2, of the net levels, of all cell levels (range, index, None)
+      hid16       bf16 mode on range-numbered graphs: fc_cell_neigh's hidden activations and their gradients are STORED as bf16 -
+                  every consumer rounds them to bf16 anyway (MFMA operands of the weight gradients) or reads the sign only (ReLU
+                  mask); only the first layer's bias gradient then sums the rounded hidden gradients instead of the fp32 ones
+      fold        the folded chain's static facts, or None
+      fwd_only    nobody will ask for this sweep's backward.  Only the bf16 folded chain has launches that keep less; fp32 mode,
+                  the attention branch and unfolded schedules run what they always ran
+      feat_fused  bf16 mode: the feature MLPs run as one kernel each and their hidden activations (268 MB per MLP at config B)
+                  are never stored - the backward recomputes them (mmft_mlp2_feat_*); needs contiguous row ranges"""
+    packed = lib.get_math_mode() == 'bf16' and ops.mlp2_fusable(st.D, st.Hd, st.D)
+    r0s = _cat_rows(st, lambda l: l == 0)
+    rc2 = _cat_rows(st, lambda l: l % 2 == 0 and l > 0)
+    rn = _cat_rows(st, lambda l: l % 2 == 1)
+    rc = _cat_rows(st, lambda l: l % 2 == 0)
+    fold = st.fold if (FOLD_LEVELS and not attn) else None
+    return dict(packed=packed, r0s=r0s, rc2=rc2, rn=rn, rc=rc, fold=fold,
+                hid16=bool(HIDDEN_BF16 and packed and isinstance(rc2, tuple) and not attn),
+                fwd_only=bool(FORWARD_ONLY and not st.need_grad and not attn and packed and fold is not None),
+                feat_fused=bool(FEAT_MLP_NO_HIDDEN and packed and all(isinstance(r, tuple) for r in (r0s, rc2, rn) if r is not None)
+                                and isinstance(rc, tuple) and ops.mlp2_feat_fusable(st.cell_feat.shape[1], st.Hd, st.D)
+                                and ops.mlp2_feat_fusable(st.net_feat.shape[1], st.Hd, st.D)))
+
+
 class _SweepRecord:
     """What eager sweeps of one schedule keep from step to step while the level list objects and the addresses of h, the
     features, the parameters and their gradient sinks stay (`sig`; the graph's buffers are persistent): `calls`, recorded
@@ -606,8 +635,9 @@ class SweepFn(torch.autograd.Function):
         (w1c, b1c, w2c, b2c, w1n, b1n, w2n, b2n, w1g, b1g, w2g, b2g) = P
         act = ops.ACT_RELU if st.relu else ops.ACT_NONE
         st.levels = [(l, r) for l, r in enumerate(level_rows)]
+        form = _sweep_form(st, c12 is not None)
         st.wpack = None
-        if lib.get_math_mode() == 'bf16' and ops.mlp2_fusable(st.D, st.Hd, st.D):
+        if form['packed']:
             # the level chain's fused MLP takes its weights pre-packed as bf16 (forward: W1, W2; reverse: W2^T, W1^T)
             # (static buffers per graph: their addresses are part of the recorded launches below)
             wp = st._bufs.get('wpack')
@@ -616,47 +646,43 @@ class SweepFn(torch.autograd.Function):
                 wp = st._bufs['wpack'] = (mk(st.Hd, st.D), mk(st.D, st.Hd), mk(st.Hd, st.D), mk(st.D, st.Hd))
             st.wpack = (ops.pack_bf16(w1g, out=wp[0]), ops.pack_bf16(w2g, out=wp[1]), ops.pack_bf16(w2g, transpose=True, out=wp[2]),
                         ops.pack_bf16(w1g, transpose=True, out=wp[3]))
-        r0 = level_rows[0]
-        rc2 = _cat_rows(st, lambda l: l % 2 == 0 and l > 0)
-        # bf16 mode on range-numbered graphs: fc_cell_neigh's hidden activations and their gradients are STORED as bf16 - every
-        # consumer rounds them to bf16 anyway (MFMA operands of the weight gradients) or reads the sign only (ReLU mask); only
-        # the first layer's bias gradient now sums the rounded hidden gradients instead of the fp32 ones
-        st.hid16 = bool(HIDDEN_BF16 and st.wpack is not None and isinstance(rc2, tuple) and st.attn is None)
-        fold = st.fold if (FOLD_LEVELS and st.attn is None) else None
-        # forward-only: nobody will ask for this sweep's backward.  Only the bf16 folded chain has launches that keep less;
-        # fp32 mode, the attention branch and unfolded schedules run what they always ran
-        fwd_only = bool(FORWARD_ONLY and not st.need_grad and c12 is None and st.wpack is not None and fold is not None)
+        r0s, rc2, rn, fold, fwd_only = form['r0s'], form['rc2'], form['rn'], form['fold'], form['fwd_only']
+        st.hid16, st.feat_fused, st.row_sets = form['hid16'], form['feat_fused'], (form['rc'], rn, rc2)
         st.HN = None if fwd_only else (st._buf('HN16', st.Hd, torch.bfloat16) if st.hid16 else st._buf('HN', st.Hd))
         st.DHN = None
         # recorded launches of the two per-level kernels (ops.relaunch), kept in the sweep's record
         st.prep = prep = st.record.calls if (RECORD_LAUNCHES and st.record is not None) else None
         dev_, stream_ = lib.stream_args(st.h)
-        rn = _cat_rows(st, lambda l: l % 2 == 1)
-        st.row_sets = (_cat_rows(st, lambda l: l % 2 == 0), rn, rc2)
-        r0s = _cat_rows(st, lambda l: l == 0) if r0.numel() else None
-        # bf16 mode: the feature MLPs run as one kernel each and their hidden activations (268 MB per MLP at config B)
-        # are never stored - the backward recomputes them (mmft_mlp2_feat_*); needs contiguous row ranges
-        st.feat_fused = (FEAT_MLP_NO_HIDDEN and st.wpack is not None and all(isinstance(r, tuple) for r in (r0s, rc2, rn) if r is not None)
-                         and isinstance(st.row_sets[0], tuple) and ops.mlp2_feat_fusable(st.cell_feat.shape[1], st.Hd, st.D)
-                         and ops.mlp2_feat_fusable(st.net_feat.shape[1], st.Hd, st.D)
-                         and all(p.is_contiguous() for p in P[:8]))
+        # incremental sweep (sweep_forward_all(incremental=)): h and PRE hold the previous sweep's values and only stale rows
+        # are written again.  A row that depends on features alone - level 0, PRE - is stale where the features changed
+        # (seed); a cell row of a level >= 2 holds its self term before its level runs and its final value afterwards, so it
+        # gets the self term again exactly where its level launch will run (dirty = st.active), and nowhere else
+        seed, dirty = st.seed, (st.active if st.seed is not None else None)
+        if seed is not None and not (fwd_only and st.feat_fused):
+            raise RuntimeError('sweep_forward_all(incremental=): needs the forward-only folded bf16 sweep with fused feature MLPs '
+                               '(bf16 math mode, a foldable schedule, no attention branch, no gradient) - every other path ignores '
+                               '`active` somewhere and would leave stale rows; sweep.incremental_supported() tells beforehand')
         if r0s is not None:                                                              # level 0, :148-153
             if st.feat_fused:
-                ops.mlp2_feat_fwd_bf16(st.cell_feat, r0s, w1c, b1c, w2c, b2c, st.h, relu_out=st.relu)
+                ops.mlp2_feat_fwd_bf16(st.cell_feat, r0s, w1c, b1c, w2c, b2c, st.h, relu_out=st.relu, active=seed)
             else:
                 _linear_rows(st.cell_feat, w1c, b1c, st.HS, r0s, act=ops.ACT_RELU)
                 _linear_rows(st.HS, w2c, b2c, st.h, r0s, act=act)
         if rc2 is not None:                                                              # fc_cell_self, all cell nodes
             if st.feat_fused:
-                ops.mlp2_feat_fwd_bf16(st.cell_feat, rc2, w1c, b1c, w2c, b2c, st.h)
+                ops.mlp2_feat_fwd_bf16(st.cell_feat, rc2, w1c, b1c, w2c, b2c, st.h, active=dirty)
             else:
                 _linear_rows(st.cell_feat, w1c, b1c, st.HS, rc2, act=ops.ACT_RELU)
                 _linear_rows(st.HS, w2c, b2c, st.h, rc2)
         if fold is not None:
-            st.PRE = st._buf('PRE', st.D)     # fc_net_self outputs live apart from h: the folded gather updates h in place
+            # fc_net_self outputs live apart from h: the folded gather updates h in place.  PRE (like the weight packs above)
+            # is a buffer of graph._sweep_bufs and PERSISTS from sweep to sweep: that is what makes an incremental sweep
+            # correct - a net row whose features did not change still finds its fc_net_self output here, and a level kernel
+            # that recomputes a clean in-neighbour from PRE gets the value h holds for it
+            st.PRE = st._buf('PRE', st.D)
         if rn is not None:                                                               # fc_net_self, all net nodes
             if st.feat_fused:
-                ops.mlp2_feat_fwd_bf16(st.net_feat, rn, w1n, b1n, w2n, b2n, st.PRE if fold is not None else st.h)
+                ops.mlp2_feat_fwd_bf16(st.net_feat, rn, w1n, b1n, w2n, b2n, st.PRE if fold is not None else st.h, active=seed)
             else:
                 _linear_rows(st.net_feat, w1n, b1n, st.HS, rn, act=ops.ACT_RELU)
                 _linear_rows(st.HS, w2n, b2n, st.PRE if fold is not None else st.h, rn)
@@ -822,17 +848,24 @@ class TargetGatherFn(torch.autograd.Function):
         return ctx.state.h.new_zeros(1), None, None, None
 
 
-def _run_sweep(conv, graph, level_nodes, tix, target_order=None, targets_unique=None, active=None):
-    """Build the sweep state for the given level lists and run SweepFn (tix None: deferred per-level target gathers)."""
-    graph._sweep = st = SweepState(graph, conv)
-    st.active = active
+def _set_schedule(st, graph, conv, level_nodes):
+    """The schedule's facts on a fresh sweep state (complete, fold, level_lists, level_meta); returns the levels' row tensors."""
     st.complete = graph.level_set_is_complete(level_nodes)
     st.fold = graph.fold_schedule(level_nodes) if (FOLD_LEVELS and st.complete and not getattr(conv, 'flag_attn', False)) else None
     st.level_lists = level_nodes if st.fold is not None else None       # key of the static slot tables (PinGraph.level_slots)
-    st.target_order, st.targets_unique = target_order, targets_unique
-    level_rows = [graph.level_rows(l, nodes, 'nodes') for l, nodes in enumerate(level_nodes)]
     st.level_meta = [graph.level_meta(l, nodes, st.D) if not torch.is_tensor(nodes) else None
                      for l, nodes in enumerate(level_nodes)]
+    return [graph.level_rows(l, nodes, 'nodes') for l, nodes in enumerate(level_nodes)]
+
+
+def _run_sweep(conv, graph, level_nodes, tix, target_order=None, targets_unique=None, active=None, seed=None):
+    """Build the sweep state for the given level lists and run SweepFn (tix None: deferred per-level target gathers)."""
+    graph._sweep = st = SweepState(graph, conv)
+    st.active, st.seed = active, seed
+    st.target_order, st.targets_unique = target_order, targets_unique
+    if seed is not None and st.need_grad:
+        raise RuntimeError('sweep_forward_all(incremental=): a sweep that will be differentiated runs over every row')
+    level_rows = _set_schedule(st, graph, conv, level_nodes)
     st.next_level = len(level_rows)
     c12 = None
     if getattr(conv, 'flag_attn', False):
@@ -852,7 +885,27 @@ def _run_sweep(conv, graph, level_nodes, tix, target_order=None, targets_unique=
         return st, SweepFn.apply(st, level_rows, tix, c12, None)
 
 
-def sweep_forward_all(conv, graph, level_nodes, targets, target_order=None, targets_unique=None, cone=False):
+def _level_specs(graph, level_nodes):
+    """Per level its (start, n) range where the list is one, else its device row tensor: what the cone launches take."""
+    specs = []
+    for l, nodes in enumerate(level_nodes):
+        meta = graph.level_meta(l, nodes) if not torch.is_tensor(nodes) else None
+        specs.append(meta['range'] if (meta and meta['range']) else graph.level_rows(l, nodes, 'nodes'))
+    return specs
+
+
+def incremental_supported(conv, graph, level_nodes):
+    """True when a sweep of these lists, now, takes the one form in which every launch honours `active` - the forward-only
+    folded bf16 sweep with fused feature MLPs (bf16 math mode, a foldable schedule of contiguous level ranges, no attention
+    branch, no gradient) - so that sweep_forward_all(incremental=) is allowed.  The answer is _sweep_form's, the function
+    SweepFn._forward_launches launches by."""
+    st = SweepState(graph, conv)
+    st.levels = list(enumerate(_set_schedule(st, graph, conv, level_nodes)))
+    form = _sweep_form(st, bool(getattr(conv, 'flag_attn', False)))
+    return form['fwd_only'] and form['feat_fused']
+
+
+def sweep_forward_all(conv, graph, level_nodes, targets, target_order=None, targets_unique=None, cone=False, incremental=None):
     """All levels of one sweep in one call. level_nodes: list (per level) of python int lists or device int32
     tensors; targets: device int32 tensor (or list) of node ids whose embeddings are returned, in order.
     target_order: optional device int32 stable argsort of `targets` (the host has it for free when it packs a
@@ -861,17 +914,25 @@ def sweep_forward_all(conv, graph, level_nodes, targets, target_order=None, targ
     the level kernels skip every node that cannot influence `targets`.  The cone is a per-node flag array built ON THE
     DEVICE by L - 1 fixed-size launches (mmft_fanin_cone_step), the launches of the sweep keep their full grids and
     skip flagged-off rows, so a captured HIP graph of the step stays valid while the sampled endpoints - and with them
-    the cone - change from replay to replay."""
+    the cone - change from replay to replay.
+    incremental=(seed, dirty), two uint8[N] device arrays the caller owns: graph.ndata['h'] holds the result of an earlier
+    sweep of the same lists with the same parameters, and since then only the feature rows flagged in `seed` changed.  The
+    sweep writes `dirty` = the seeds and their transitive fan-out (prep.fanout_cone_mask; intersected with the fan-in cone
+    under cone=True) and runs over those rows alone; every other row of h keeps its value, which is the value a full sweep
+    would give it.  Only where incremental_supported() holds - anywhere else this raises.  `seed` is read, not cleared."""
     tix = graph.level_rows(-1, targets, 'sweep_targets')
-    active = None
-    if cone:
+    active = seed = None
+    if cone or incremental is not None:
         from . import prep
-        specs = []
-        for l, nodes in enumerate(level_nodes):
-            meta = graph.level_meta(l, nodes) if not torch.is_tensor(nodes) else None
-            specs.append(meta['range'] if (meta and meta['range']) else graph.level_rows(l, nodes, 'nodes'))
-        active = graph._cone_mask = prep.cone_mask([graph.csr('in', 'net'), graph.csr('in', 'cell')], specs, tix, out=graph._cone_mask)
-    return _run_sweep(conv, graph, level_nodes, tix, target_order, targets_unique, active)[1]
+        specs, csrs = _level_specs(graph, level_nodes), [graph.csr('in', 'net'), graph.csr('in', 'cell')]
+    if cone:
+        active = graph._cone_mask = prep.cone_mask(csrs, specs, tix, out=graph._cone_mask)
+    if incremental is not None:
+        seed, dirty = incremental
+        active = prep.fanout_cone_mask(csrs, specs, seed, within=active, out=dirty)
+        if active is not dirty:
+            raise ValueError('sweep_forward_all(incremental=): dirty must be a contiguous uint8[N] tensor on the graph\'s device')
+    return _run_sweep(conv, graph, level_nodes, tix, target_order, targets_unique, active, seed)[1]
 
 
 # Speculative drop-in sweep.  The reference loop calls the model once per level with the SAME node lists every step
