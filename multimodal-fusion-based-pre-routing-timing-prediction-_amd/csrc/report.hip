@@ -14,6 +14,7 @@
 // order, integer counts, and the k smallest of the parts' sorted lists.  Whichever part that is, the bits are the same.
 // Nobody waits for anybody, and there are no float atomics.
 #include "common.h"
+#include "slack_key.h"
 #include "../../include/mmft_report.h"
 
 #include <math.h>
@@ -45,15 +46,8 @@ struct TimingReportArgs {
   long long slot_bytes;
 };
 
-// unsigned order of the result == numeric order of the floats (-inf lowest, +inf highest)
-__device__ __forceinline__ unsigned ordered_bits(float s) {
-  const unsigned u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float key_slack(u64 key) {
-  const unsigned o = (unsigned)(key >> 32);
-  return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
-}
+using mmft::ordered_bits;                     // slack_key.h: unsigned order of the bits == numeric order of the floats
+__device__ __forceinline__ float key_slack(u64 key) { return mmft::ordered_float((unsigned)(key >> 32)); }
 __device__ __forceinline__ int key_row(u64 key) { return (int)(unsigned)(key & 0xffffffffull); }
 
 __device__ __forceinline__ u64 wave_min(u64 v) {
@@ -139,7 +133,7 @@ __global__ void __launch_bounds__(TR_THREADS) timing_report_kernel(TimingReportA
     const int r = a.design_rows[r0 + i];
     u64 key = KEY_NONE;
     float s = __uint_as_float(0x7fc00000u);
-    if ((unsigned)r < (unsigned)a.T) s = (a.required[r] - a.pred[r]) + 0.0f;        // + 0.0f: -0.0 becomes +0.0
+    if ((unsigned)r < (unsigned)a.T) s = mmft::slack_of(a.required[r], a.pred[r]);  // -0.0 becomes +0.0
     if (s != s) {
       ++nn;
     } else {

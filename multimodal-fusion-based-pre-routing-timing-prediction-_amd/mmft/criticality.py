@@ -1,0 +1,198 @@
+"""Timing criticality per pin and per map cell, on the device: for every pin the worst slack of any predicted path through it,
+the batch row of that path, the number of violating paths through it and a criticality in [0, 1]; for every cell of every
+design's map the worst slack and the number of violating paths whose mask covers it - what a timing-driven placer turns into
+net weights and into regions to spread.  One entry point (mmft_criticality, include/mmft_crit.h: three small launches) on
+the tables a `placement.PlacedPaths` already holds, and one device->host copy, instead of a copy of the predictions, a walk
+over the path nodes and a re-rasterisation of the masks on the host.
+
+The rules (the header states them, `reference_criticality` restates them in numpy):
+  slack = required - pred, one fp32 subtraction, -0.0 canonicalised to +0.0 (report.reference_slack: the rule of the timing
+  report); a row is valid unless its slack is NaN and violates when slack < 0; minima are taken over valid rows, the smaller
+  batch row first on equal slack; node_crit = node_slack / (worst slack of the design), one fp32 division, 1 when they are
+  equal, 0 without a violation; the mask of a row is the mask rule of include/mmft_place.h (placement.rasterize_host).
+"""
+import numpy as np
+import torch
+
+from . import lib
+from .placement import MAX_CELLS, rasterize_host
+from .report import reference_slack
+
+FIELDS = ('node_slack', 'node_row', 'node_viol', 'node_crit', 'cell_slack', 'cell_viol', 'counts')
+
+
+def workspace_bytes(N, B, P):
+    """Bytes of the keyed words; P = 0 without the cell outputs."""
+    return lib.crit('mmft_criticality_workspace_bytes', int(N), int(B), int(P))
+
+
+class CritBuffers:
+    """The static output buffers of one criticality launch, carved out of ONE buffer of 4-byte words so that `host()` is one
+    device->host copy: node_slack fp32, node_row, node_viol int32, node_crit fp32 [N]; counts int32 [B, 2]; with cells
+    cell_slack fp32 and cell_viol int32 [B, P]."""
+
+    def __init__(self, N, B, P, device, cells=True):
+        self.N, self.B, self.cells = int(N), int(B), bool(cells)
+        self.P = int(P) if self.cells else 0
+        if self.N < 1 or self.B < 1 or (self.cells and (self.P < 64 or self.P % 64 or self.P > MAX_CELLS)):
+            raise ValueError(f'CritBuffers: need N >= 1, B >= 1 and, with cells, a map of a multiple of 64 cells up to {MAX_CELLS} '
+                             f'(N {N}, B {B}, P {P})')
+        bp = self.B * self.P
+        self._layout = (('node_slack', 'f4', (self.N,)), ('node_row', 'i4', (self.N,)), ('node_viol', 'i4', (self.N,)),
+                        ('node_crit', 'f4', (self.N,)), ('counts', 'i4', (self.B, 2))) + \
+            ((('cell_slack', 'f4', (self.B, self.P)), ('cell_viol', 'i4', (self.B, self.P))) if self.cells else ())
+        self.raw = torch.empty(4 * self.N + 2 * self.B + 2 * bp, dtype=torch.int32, device=device)
+
+    def _carve(self, raw, view):
+        out, pos = dict.fromkeys(FIELDS), 0
+        for name, dt, shape in self._layout:
+            n = int(np.prod(shape))
+            out[name] = view(raw[pos:pos + n], dt, shape)
+            pos += n
+        return tuple(out[k] for k in FIELDS)
+
+    def tensors(self):
+        """(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts): views of the one buffer; the two cell
+        tensors are None without cells."""
+        return self._carve(self.raw, lambda t, dt, shape: (t.view(torch.float32) if dt == 'f4' else t).view(shape))
+
+    def host(self):
+        """One device->host copy -> the same seven as numpy arrays (`decode` takes them)."""
+        return self._carve(self.raw.cpu().numpy(), lambda a, dt, shape: a.view(dt).reshape(shape))
+
+
+def _vec(fn, t, name, dtype, n=None):
+    if not torch.is_tensor(t):
+        raise TypeError(f'{fn}: {name} must be a tensor')
+    if t.dtype != dtype:
+        raise TypeError(f'{fn}: {name} must be {dtype}, got {t.dtype}')
+    if t.dim() != 1 or not t.is_contiguous():
+        raise ValueError(f'{fn}: {name} must be a contiguous 1-D tensor, got shape {tuple(t.shape)} with strides {t.stride()}')
+    if n is not None and t.numel() != n:
+        raise ValueError(f'{fn}: {name} holds {t.numel()} entries, {n} expected')
+    return t
+
+
+def criticality(pred, required, placed, paths, row_design, B, cells=True, out=None, workspace=None):
+    """Launch mmft_criticality on the current stream -> (node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol,
+    counts) on the device (the two cell tensors None with cells=False); `decode` turns their host copies into per-design dicts.
+
+    pred, required     fp32, contiguous 1-D, T rows each
+    placed             placement.PlacedPaths: path nodes and lengths, the pins' current coordinates, the map
+    paths              int32 [T]: the row of placed.nodes that each batch row predicts
+    row_design         int32 [T], the design of each batch row in [0, B), or None: every row belongs to design 0
+    B                  designs; pins are numbered as placed.nodes numbers them (N = placed.loc_x.numel())
+    out, workspace     buffers the caller owns (CritBuffers.tensors(); a tensor of workspace_bytes bytes on the same device):
+                       a captured launch needs static ones.  Without `workspace` the scratch comes from lib.workspace, which
+                       never grows during a capture.
+
+    Everything is validated on the host, dtypes, shapes and contiguity first, before anything is launched."""
+    fn = 'criticality'
+    _vec(fn, pred, 'pred', torch.float32)
+    T = pred.numel()
+    _vec(fn, required, 'required', torch.float32, T)
+    _vec(fn, paths, 'paths', torch.int32, T)
+    if row_design is not None:
+        _vec(fn, row_design, 'row_design', torch.int32, T)
+    B, cells = int(B), bool(cells)
+    N = int(placed.loc_x.numel())
+    P = int(placed.P) if cells else 0
+    if T < 1 or T > 1 << 24 or B < 1 or N < 1:
+        raise ValueError(f'{fn}: need 1 <= T <= 2^24, B >= 1, N >= 1 (T {T}, B {B}, N {N})')
+    if cells and (P % 64 or P > MAX_CELLS or P < 64):
+        raise ValueError(f'{fn}: cells=True needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {P}')
+    if out is None:
+        out = CritBuffers(N, B, P, pred.device, cells=cells).tensors()
+    if len(out) != 7:
+        raise ValueError(f'{fn}: out must be the seven tensors of CritBuffers.tensors()')
+    shapes = dict(node_slack=(torch.float32, (N,)), node_row=(torch.int32, (N,)), node_viol=(torch.int32, (N,)),
+                  node_crit=(torch.float32, (N,)), cell_slack=(torch.float32, (B, P)), cell_viol=(torch.int32, (B, P)),
+                  counts=(torch.int32, (B, 2)))
+    for name, t in zip(FIELDS, out):
+        if name.startswith('cell_') and not cells:
+            continue
+        dt, shape = shapes[name]
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'{fn}: {name} must be a contiguous {dt} tensor of shape {shape}')
+    dev = placed.nodes.device
+    every = [pred, required, paths, placed.lens, placed.loc_x, placed.loc_y] + ([row_design] if row_design is not None else []) + \
+        [t for name, t in zip(FIELDS, out) if cells or not name.startswith('cell_')]
+    if any(t.device != dev for t in every):
+        raise ValueError(f'{fn}: every tensor must live on the device of the placement tables ({dev})')
+    if dev.type != 'cuda':
+        raise RuntimeError(f'{fn}: the mmft hot path runs on the GPU only (got {dev} tensors); there is no CPU fallback')
+    need = workspace_bytes(N, B, P)
+    if workspace is None:
+        workspace = lib.workspace(dev, need)
+    elif not (torch.is_tensor(workspace) and workspace.device == dev and workspace.is_contiguous()):
+        raise ValueError(f'{fn}: workspace must be a contiguous tensor on {dev}')
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f'{fn}: workspace of {need} bytes needed, got {workspace.numel() * workspace.element_size()}')
+    node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts = out
+    lib.crit('mmft_criticality', pred, required, placed.nodes, placed.lens, placed.maxlen,
+             placed.loc_x if cells else None, placed.loc_y if cells else None, placed.map_x if cells else 0, placed.map_y if cells else 0,
+             paths, row_design, T, N, B, node_slack, node_row, node_viol, node_crit,
+             cell_slack if cells else None, cell_viol if cells else None, counts,
+             workspace, workspace.numel() * workspace.element_size(), *lib.stream_args(pred))
+    return node_slack, node_row, node_viol, node_crit, (cell_slack if cells else None), (cell_viol if cells else None), counts
+
+
+def reference_criticality(pred, required, path_nodes, path_lens, pin_x, pin_y, map_x, map_y, paths, row_design, N, B,
+                          cells=True, masks=None):
+    """The contract of include/mmft_crit.h in plain numpy from host arrays -> the seven arrays in the layout of the device
+    buffers (cell_slack / cell_viol None with cells=False).  The masks come from placement.rasterize_host - the mask rule
+    lives there - or from `masks` = (indptr, cols) of the rows of path_nodes, rasterised by somebody else from the same pins."""
+    nodes, lens = np.asarray(path_nodes).astype(np.int64), np.asarray(path_lens).astype(np.int64)
+    paths = np.asarray(paths).astype(np.int64)
+    T, maxlen = paths.shape[0], nodes.shape[1]
+    design = np.zeros(T, dtype=np.int64) if row_design is None else np.asarray(row_design).astype(np.int64)
+    slack = reference_slack(pred, required)
+    P = int(map_x) * int(map_y) if cells else 0
+    inf = np.float32(np.inf)
+    node_slack, node_row = np.full(N, inf, dtype=np.float32), np.full(N, -1, dtype=np.int32)
+    node_viol, node_crit = np.zeros(N, dtype=np.int32), np.zeros(N, dtype=np.float32)
+    cell_slack = np.full((B, P), inf, dtype=np.float32) if cells else None
+    cell_viol = np.zeros((B, P), dtype=np.int32) if cells else None
+    counts = np.zeros((B, 2), dtype=np.int32)
+    worst = np.full(B, inf, dtype=np.float32)                      # per design, over every valid row
+    if cells:
+        indptr, cols = masks if masks is not None else rasterize_host(nodes, lens, pin_x, pin_y, map_x, map_y)
+    for t in range(T):                                             # ascending rows: a strict `<` keeps the smaller row on a tie
+        s, b, q = slack[t], int(design[t]), int(paths[t])
+        if np.isnan(s):
+            counts[b, 1] += 1
+            continue
+        counts[b, 0] += 1
+        worst[b] = min(worst[b], s)
+        for n in nodes[q, :min(int(lens[q]), maxlen)]:
+            if node_row[n] < 0 or s < node_slack[n]:
+                node_slack[n], node_row[n] = s, t
+            if s < 0:
+                node_viol[n] += 1
+        if cells:
+            c = np.asarray(cols[indptr[q]:indptr[q + 1]]).astype(np.int64)
+            cell_slack[b, c] = np.minimum(cell_slack[b, c], s)
+            if s < 0:
+                cell_viol[b, c] += 1
+    for n in np.flatnonzero((node_row >= 0) & (node_slack < 0)):
+        w = worst[design[node_row[n]]]
+        with np.errstate(invalid='ignore'):
+            node_crit[n] = np.float32(1.0) if node_slack[n] == w else np.float32(node_slack[n]) / np.float32(w)
+    return node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts
+
+
+def decode(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts, node_off, map_x=None, map_y=None):
+    """Host copies of the seven buffers -> one dict per design: node_slack, node_row, node_viol, node_crit as arrays in the
+    design's own node order (node_off [B + 1]: the designs' offsets in the numbering of the path nodes; node_row stays a row
+    of the batch), cell_slack, cell_viol as [map_x, map_y] arrays or None, n (valid rows) and n_nan."""
+    node_off, counts = np.asarray(node_off).astype(np.int64), np.asarray(counts)
+    out = []
+    for b in range(counts.shape[0]):
+        lo, hi = int(node_off[b]), int(node_off[b + 1])
+        d = dict(node_slack=np.asarray(node_slack)[lo:hi], node_row=np.asarray(node_row)[lo:hi], node_viol=np.asarray(node_viol)[lo:hi],
+                 node_crit=np.asarray(node_crit)[lo:hi], cell_slack=None, cell_viol=None, n=int(counts[b, 0]), n_nan=int(counts[b, 1]))
+        if cell_slack is not None:
+            d['cell_slack'] = np.asarray(cell_slack)[b].reshape(int(map_x), int(map_y))
+            d['cell_viol'] = np.asarray(cell_viol)[b].reshape(int(map_x), int(map_y))
+        out.append(d)
+    return out

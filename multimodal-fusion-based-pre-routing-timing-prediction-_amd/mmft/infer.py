@@ -126,11 +126,22 @@ class Predictor:
                           (fp32 mode, the attention branch, an unfolded schedule: sweep.incremental_supported) predict() runs
                           the ordinary full sweep and `incremental_active` is False.  The U-Net, the masked projection and
                           the head run in full on every call
+    criticality           None, True or dict(cells=True): every predict() also launches the criticality kernels
+                          (mmft.criticality, include/mmft_crit.h) on the predictions, the endpoints' required times and the
+                          paths' nodes, after the report launch, as the last launches of the call - inside the replayed graph in
+                          bf16 mode; criticality() decodes the last call's buffers: per pin the worst slack of any predicted
+                          path through it, that path's row, the number of violating paths and a criticality in [0, 1]; with
+                          cells=True the worst slack and the number of violating paths per map cell, from the masks of the
+                          pins as they are now (a map of a multiple of 64 cells, at most 65536).  Every design carries
+                          placement data; placement=True is NOT needed: without it the option keeps tables of its own and
+                          the pins never move, with it the same tables serve both and the cell maps follow
+                          update(i, pin_x=..., pin_y=...).  Regression task only.  predict() returns what it returns without it
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
-                 cone=False, report=None, placement=False, incremental=False):
+                 cone=False, report=None, placement=False, incremental=False, criticality=None):
+        criticality = self._criticality_spec(criticality)
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
@@ -162,8 +173,10 @@ class Predictor:
         self._trusted, self._trust_sig, self._incr_ok = False, None, {}
         if self.incremental:
             self._perm32 = [q.to(torch.int32) for q in self._perm]
+        self._slack = None
         self._report = self._make_report(report) if report is not None else None
         self._placed = self._make_placed(designs) if placement else None
+        self._crit = self._make_criticality(criticality, designs) if criticality is not None else None
 
     def _make_placed(self, designs):
         """The batch's placement tables; refuses designs without placement data and designs whose stored masks are not the
@@ -188,6 +201,57 @@ class Predictor:
                                  '(placement.attach_placement rebuilds them)')
         return placed
 
+    def _slack_rows(self, option):
+        """What slack needs, from the static selection: (required fp32 [T] on the device, design of each batch row as a host
+        int64 array).  Made once and shared by the options that form slacks (report=, criticality=); refuses a model whose
+        head is not the regression head."""
+        nlabels = self.pmodel.mlp_fuse.layers[-1].out_features
+        if nlabels != 1:
+            raise ValueError(f'Predictor: {option} needs the regression head (nlabels = 1), the model has {nlabels} labels')
+        if self._slack is None:
+            b = self.batch
+            T = self._sel[0].numel()
+            required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
+            # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
+            design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
+            self._slack = (required, design)
+        return self._slack
+
+    @staticmethod
+    def _criticality_spec(spec):
+        """criticality= as a dict, or None when the option is off; refuses anything else before a device is touched."""
+        if spec is None or spec is False:
+            return None
+        spec = {} if spec is True else spec
+        if not isinstance(spec, dict):
+            raise ValueError(f'Predictor: criticality= takes None, True or dict(cells=...), got {spec!r}')
+        unknown = set(spec) - {'cells'}
+        if unknown:
+            raise ValueError(f'Predictor: criticality= takes cells, got {sorted(unknown)}')
+        return spec
+
+    def _make_criticality(self, spec, designs):
+        """Everything the criticality launch needs: the placement tables (those of placement=True, which follow update(); or
+        tables of its own, whose pins never move), the rows' required times and designs, static output buffers and the
+        keyed-word workspace - static addresses, kept alive with the replay."""
+        from . import criticality as K, placement as PL
+        cells = bool(spec.get('cells', True))
+        required, design = self._slack_rows('criticality=')
+        for i, d in enumerate(designs):
+            if not PL.has_placement(d):
+                raise ValueError(f'Predictor: criticality= needs the paths\' nodes, but design {i} carries no placement data '
+                                 f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
+        b, dev = self.batch, self.device
+        if cells and (b.P % 64 or b.P > PL.MAX_CELLS):
+            raise ValueError(f'Predictor: criticality=dict(cells=True) needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; '
+                             f'it has {b.P}')
+        placed = self._placed if self._placed is not None else PL.PlacedPaths(designs, b.node_off, dev)
+        row_design = torch.from_numpy(design.astype(np.int32)).to(dev) if b.B > 1 else None
+        N = int(b.node_off[-1])
+        bufs = K.CritBuffers(N, b.B, placed.P, dev, cells=cells)
+        scratch = torch.empty((K.workspace_bytes(N, b.B, placed.P if cells else 0) + 7) // 8, dtype=torch.int64, device=dev)
+        return dict(cells=cells, placed=placed, required=required, row_design=row_design, bufs=bufs, scratch=scratch, ready=False)
+
     def _make_report(self, spec):
         """Everything the report launch needs that the static selection decides: the endpoints' required times, the rows of
         each design, the output buffers and the scratch - static addresses, kept alive with the replay."""
@@ -195,15 +259,10 @@ class Predictor:
         unknown = set(spec) - {'k', 'hist'}
         if unknown:
             raise ValueError(f'Predictor: report= takes k and hist, got {sorted(unknown)}')
-        nlabels = self.pmodel.mlp_fuse.layers[-1].out_features
-        if nlabels != 1:
-            raise ValueError(f'Predictor: report= needs the regression head (nlabels = 1), the model has {nlabels} labels')
         b, dev = self.batch, self.device
         k, hist = int(spec.get('k', 32)), spec.get('hist')
-        T = self._sel[0].numel()
-        required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
-        # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
-        design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
+        required, design = self._slack_rows('report=')
+        T = required.numel()
         ptr, rows = R.group_rows(design, b.B)
         bufs = R.ReportBuffers(b.B, k, hist, dev)
         scratch = torch.empty((R.workspace_bytes(T, b.B, k, hist) + 7) // 8, dtype=torch.int64, device=dev)
@@ -277,6 +336,12 @@ class Predictor:
             R.timing_report(pred.contiguous(), r['required'], r['design_ptr'], r['design_rows'], r['k'], r['hist'],
                             out=r['bufs'].tensors(), workspace=r['scratch'])
             r['ready'] = True
+        if self._crit is not None:
+            from . import criticality as K
+            c = self._crit
+            K.criticality(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B, cells=c['cells'],
+                          out=c['bufs'].tensors(), workspace=c['scratch'])
+            c['ready'] = True
         return pred
 
     @torch.no_grad()
@@ -301,7 +366,7 @@ class Predictor:
             if self._replay is None or sig != self._sig:
                 self._sig = sig
                 self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed,
-                                                     self.seed, self.dirty))
+                                                     self.seed, self.dirty, self._crit))
             out = self._replay.run(self._launches)
             self._trusted = self.incremental_active
             if out is not None:                                  # an eager or the capturing call
@@ -358,6 +423,21 @@ class Predictor:
         if not self._report['ready']:
             raise RuntimeError('Predictor.report(): predict() has not run yet')
         return R.decode(*self._report['bufs'].host()[0], endpoints=self.endpoints)
+
+    def criticality(self, i=None):
+        """The criticality of the LAST predict(): one dict per design, or design i's (mmft.criticality.decode: node_slack,
+        node_row, node_viol, node_crit in the design's own node order - node_row is a row of `pred` -, cell_slack and
+        cell_viol as [map, map] arrays or None, n, n_nan).  One device->host copy."""
+        from . import criticality as K
+        if self._crit is None:
+            raise RuntimeError('Predictor.criticality(): no criticality was requested (criticality=True or dict(cells=...))')
+        if not self._crit['ready']:
+            raise RuntimeError('Predictor.criticality(): predict() has not run yet')
+        if i is not None and not 0 <= i < self.batch.B:
+            raise IndexError(f'criticality: design {i} of {self.batch.B}')
+        placed = self._crit['placed']
+        out = K.decode(*self._crit['bufs'].host(), node_off=self.batch.node_off, map_x=placed.map_x, map_y=placed.map_y)
+        return out if i is None else out[i]
 
     def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None, rows=None):
         """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the

@@ -1,6 +1,6 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
-include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, and in include/mmft_incr.h,
-called through `incr`).
+include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, in include/mmft_incr.h,
+called through `incr`, and in include/mmft_crit.h, called through `crit`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -19,6 +19,7 @@ HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft.h')
 EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report.h')      # extensions: not the reference's path
 PLACE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_place.h')     # masks that follow a placement
 INCR_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_incr.h')       # sweeps over the fan-out of an edit
+CRIT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit.h')       # criticality per pin and map cell
 
 _lib = None
 
@@ -72,6 +73,11 @@ def place_decls():
 def incr_decls():
     """The same for include/mmft_incr.h (called through `incr`)."""
     return _parse_header(INCR_HEADER_PATH)
+
+
+def crit_decls():
+    """The same for include/mmft_crit.h (called through `crit`)."""
+    return _parse_header(CRIT_HEADER_PATH)
 
 
 def header_symbols():
@@ -193,6 +199,26 @@ def incr(name, *args):
         _INCR[name] = fn
     rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
     if rc != 0:
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_CRIT = {}
+
+
+def crit(name, *args):
+    """Call an entry point of include/mmft_crit.h, bound from that header on first use, exactly like `ext`: an `int` entry
+    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
+    fn = _CRIT.get(name)
+    if fn is None:
+        decls = crit_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {CRIT_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _CRIT[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
     return int(rc)
 

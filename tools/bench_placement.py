@@ -2,6 +2,7 @@
 
     python tools/bench_placement.py [--designs 8] [--paths 1350] [--reps 20] [--rounds 7] [--rebuilds 3] [--out FILE]
     python tools/bench_placement.py --trace        (the launches alone, for a kernel trace of its own)
+    python tools/bench_placement.py --criticality  (what Predictor(criticality=...) adds to a replayed predict(), see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -16,6 +17,14 @@ Predictor rebuilt on the moved pins; predict_placed must equal predict_static.  
 
 --trace runs eager predict() calls of both Predictors and PlacedPaths.csr() (the two path_mask_kernel launches), nothing
 else: run it under a kernel tracer to read placed_fc_fwd_kernel next to masked_fc_fwd_runs_kernel and path_mask_kernel.
+
+--criticality, on the same designs (nothing of the above is run): a replayed predict() of Predictor(placement=True) without the
+option, with criticality=dict(cells=False) and with criticality=True, alternating inside each round as above (predict_plain /
+predict_crit_pins / predict_crit); the three launches of mmft_criticality alone on the same static buffers (crit_alone_pins /
+crit_alone), next to the number of (row, pin) and (row, covered cell) pairs, so that the rate of the integer atomics can be read
+off; and the host route from the same predictions: copy `pred` back and np.minimum.at over path_nodes for the pins (host_pins),
+rasterize_host plus np.minimum.at / np.add.at over the mask columns for the cells, at design 0 only (host_cells_design0).  The
+device result must equal reference_criticality bitwise.
 Needs a GPU."""
 import argparse
 import copy
@@ -52,6 +61,107 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
+def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    from mmft import criticality as K
+    from mmft.report import reference_slack
+    m = designs[0].map_size
+    # required times at the median prediction: about half of the endpoints violate (the batch copies them when it is built)
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for d in designs:
+        d.required_time[:] = median
+    preds = {'predict_plain': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True),
+             'predict_crit_pins': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, criticality=dict(cells=False)),
+             'predict_crit': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, criticality=True)}
+    for _ in range(3):
+        ys = [q.predict()[0].clone() for q in preds.values()]
+    assert all(torch.equal(ys[0], y) for y in ys) and all(q._replay.graph is not None for q in preds.values())
+    p = preds['predict_crit']
+    c = p._crit
+    paths = p._sel[1].cpu().numpy().astype(np.int64)
+    nodes, lens = c['placed'].nodes.cpu().numpy(), c['placed'].lens.cpu().numpy()
+    design = np.zeros(paths.shape[0], dtype=np.int64) if c['row_design'] is None else c['row_design'].cpu().numpy().astype(np.int64)
+    cells_of = np.concatenate([np.diff(d.mask_indptr) for d in designs])
+    pin_pairs, cell_pairs = int(np.minimum(lens, nodes.shape[1])[paths].sum()), int(cells_of[paths].sum())
+    emit(row='shapes', designs=a.designs, map=m, rows=int(paths.shape[0]), pins=int(nodes.max()) + 1, maxlen=int(nodes.shape[1]),
+         row_pin_pairs=pin_pairs, row_cell_pairs=cell_pairs, cells_per_row_mean=float(cells_of[paths].mean()))
+
+    # the device result against the numpy restatement, from the same predictions
+    pred = ys[0].cpu().numpy().reshape(-1)
+    required = c['required'].cpu().numpy()
+    px, py = np.concatenate([d.pin_x for d in designs]), np.concatenate([d.pin_y for d in designs])
+    got = c['bufs'].host()
+    ref = K.reference_criticality(pred, required, nodes, lens, px, py, m, m, paths, design if len(designs) > 1 else None, got[0].shape[0],
+                                  len(designs), masks=(np.concatenate([[0], np.cumsum(cells_of)]), np.concatenate([d.mask_cols for d in designs])))
+    bits = lambda x: np.ascontiguousarray(x).view(np.int32)
+    same = all(np.array_equal(bits(g), bits(r)) for g, r in zip(got, ref))
+    slack = reference_slack(pred, required)
+    emit(row='outputs', equals_reference_bitwise=bool(same), violating_rows=int((slack < 0).sum()), pins_with_a_path=int((ref[1] >= 0).sum()),
+         critical_pins=int((ref[3] > 0).sum()), cells_with_a_violation=int((ref[5] > 0).sum()))
+    assert same
+
+    # replayed predict() with and without the option, and the three launches alone
+    def alone(q):
+        k = q._crit
+        return lambda: K.criticality(ys[0].reshape(-1), k['required'], k['placed'], q._sel[1], k['row_design'], len(designs), cells=k['cells'],
+                                     out=k['bufs'].tensors(), workspace=k['scratch'])
+    rows = {nm: (lambda q=q: q.predict()[0]) for nm, q in preds.items()}
+    rows['crit_alone_pins'], rows['crit_alone'] = alone(preds['predict_crit_pins']), alone(p)
+    for fn in rows.values():
+        timed(fn, a.reps)
+    ms = {nm: [] for nm in rows}
+    for _ in range(a.rounds):
+        for nm, fn in rows.items():
+            ms[nm].append(timed(fn, a.reps))
+    for nm in rows:
+        med = statistics.median(ms[nm])
+        extra = {}
+        if nm.startswith('crit_alone'):
+            pairs = pin_pairs + (cell_pairs if nm == 'crit_alone' else 0)
+            extra = dict(pairs=pairs, ns_per_pair_median=1e6 * med / pairs)
+        emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=med, ms_min=min(ms[nm]), ms_max=max(ms[nm]), **extra)
+
+    # the host route, from the same predictions
+    def host_pins():
+        t0 = time.perf_counter()
+        s = reference_slack(ys[0].cpu().numpy().reshape(-1), required)
+        live = np.arange(nodes.shape[1])[None, :] < np.minimum(lens, nodes.shape[1])[paths][:, None]
+        live &= ~np.isnan(s)[:, None]
+        node_slack = np.full(got[0].shape[0], np.inf, dtype=np.float32)
+        np.minimum.at(node_slack, nodes[paths][live], np.broadcast_to(s[:, None], live.shape)[live])
+        weights = torch.from_numpy(node_slack).to(dev)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, node_slack, weights
+
+    def host_cells(i):
+        d = designs[i]
+        t0 = time.perf_counter()
+        s = reference_slack(ys[0].cpu().numpy().reshape(-1), required)
+        ip, cols = PL.rasterize_host(d.path_nodes, d.path_lens, d.pin_x, d.pin_y, m, m)
+        t1 = time.perf_counter()
+        cell_slack, cell_viol = np.full(m * m, np.inf, dtype=np.float32), np.zeros(m * m, dtype=np.int32)
+        off = int(p.batch.path_off[i])
+        for t in np.flatnonzero((design == i) & ~np.isnan(s)):
+            cc = cols[ip[paths[t] - off]:ip[paths[t] - off + 1]]
+            cell_slack[cc] = np.minimum(cell_slack[cc], s[t])
+            cell_viol[cc] += s[t] < 0
+        weights = torch.from_numpy(cell_slack).to(dev)
+        torch.cuda.synchronize()
+        return t1 - t0, time.perf_counter() - t1, cell_slack, cell_viol, weights
+    t = []
+    for _ in range(a.rebuilds):
+        dt, node_slack, _ = host_pins()
+        t.append(dt)
+    assert np.array_equal(bits(node_slack), bits(ref[0]))
+    emit(row='host_pins', repetitions=a.rebuilds, s_median=statistics.median(t), s_min=min(t), s_max=max(t))
+    t = []
+    for _ in range(a.rebuilds):
+        r0, r1, cell_slack, cell_viol, _ = host_cells(0)
+        t.append((r0 + r1, r0))
+    assert np.array_equal(bits(cell_slack), bits(ref[4][0])) and np.array_equal(cell_viol, ref[5][0])
+    emit(row='host_cells_design0', repetitions=a.rebuilds, s_median=statistics.median(x for x, _ in t), s_min=min(x for x, _ in t),
+         s_max=max(x for x, _ in t), s_rasterise_median=statistics.median(x for _, x in t))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -60,6 +170,7 @@ def main():
     ap.add_argument('--rounds', type=int, default=7)
     ap.add_argument('--rebuilds', type=int, default=3)
     ap.add_argument('--trace', action='store_true')
+    ap.add_argument('--criticality', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -82,6 +193,10 @@ def main():
     pmodel, cnn = build_models(map_size=m, device=dev, seed=9294)
     with torch.no_grad():
         cnn.outc.conv[0].bias.fill_(2.0)        # a feature map that is not all zero behind the last ReLU: the masks matter to the outputs compared
+    if a.criticality:
+        with lib.math_mode('bf16'), torch.no_grad():
+            criticality_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
         moving = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True)
