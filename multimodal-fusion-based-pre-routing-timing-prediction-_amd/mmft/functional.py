@@ -52,6 +52,69 @@ def linear_act(x, w, b=None, slope=None):
     return LinearActFn.apply(x, w, b, slope)
 
 
+FUSED_HEAD_MLP = True   # bf16 mode: mlp_fuse (288 -> 576 -> 1, ReLU) as the three kernels of include/mmft_head.h (False: the layer loop)
+
+
+def head_mlp_usable(x, w1, b1, w2, b2, slope):
+    """True when Linear(w1, b1) - ReLU - Linear(w2, b2) over the rows of x is what mmft_head_mlp_fwd / _bwd compute: the
+    switch, bf16 math mode, ReLU, the one supported shape, fp32 device tensors the kernels can read in place.  Anything else
+    (CPU tensors included: their refusal is the layer path's) keeps the generic layers."""
+    if not (FUSED_HEAD_MLP and slope == 0 and b1 is not None and b2 is not None and torch.is_tensor(x) and x.is_cuda
+            and x.dim() == 2 and x.dtype == torch.float32 and w1.dim() == 2 and w2.dim() == 2 and x.shape[1] == w1.shape[1]
+            and w2.shape[1] == w1.shape[0] and x.shape[0] > 0):
+        return False
+    if not lib.head('mmft_head_mlp_supported', w1.shape[1], w1.shape[0], w2.shape[0]) or lib.get_math_mode() != 'bf16':
+        return False
+    return all(p.is_cuda and p.dtype == torch.float32 and p.is_contiguous() and p.data_ptr() % 16 == 0 for p in (w1, b1, w2)) \
+        and b2.is_cuda and b2.dtype == torch.float32
+
+
+class Mlp2HeadFn(torch.autograd.Function):
+    """pred = relu(x @ w1.T + b1) @ w2.T + b2 for the fusion head's mlp_fuse (src/model.py:267,291) in bf16 math mode, one
+    kernel forward and two plus the reductions backward (include/mmft_head.h).  The only saved activation is the bf16 hidden
+    tensor; no weight pack outlives the call that made it.  Stateless like LinearActFn: nothing is freed or mutated in
+    backward, so backward(retain_graph=True) may run it twice."""
+
+    @staticmethod
+    def forward(ctx, x, w1, b1, w2, b2, grad_on):
+        xs = ops.strided_rows(x)
+        T, (hidden, inn) = xs.shape[0], w1.shape
+        # grad_on: the caller's grad mode (it is off inside forward).  needs_input_grad mirrors requires_grad whatever the mode:
+        # under torch.no_grad() with trainable weights (Predictor.predict) nothing is saved and nothing is stored for it
+        keep = bool(grad_on) and any(ctx.needs_input_grad)
+        hid = torch.empty((T, hidden), dtype=torch.bfloat16, device=x.device) if keep else None
+        pred = torch.empty((T, 1), dtype=torch.float32, device=x.device)
+        lib.head('mmft_head_mlp_fwd', xs, xs.stride(0), w1, b1, w2, b2, hid, pred, T, inn, hidden, 1, *lib.stream_args(xs))
+        ctx.sinks = tuple(gradsink.of(p) for p in (w1, b1, w2, b2))
+        ctx.save_for_backward(xs, w1, w2, hid)
+        return pred
+
+    @staticmethod
+    def backward(ctx, gy):
+        xs, w1, w2, hid = ctx.saved_tensors
+        T, (hidden, inn) = xs.shape[0], w1.shape
+        dpred = gy.reshape(-1)
+        if not dpred.is_contiguous():
+            dpred = dpred.contiguous()
+        dev = xs.device
+        dx = torch.empty((T, inn), dtype=torch.float32, device=dev) if ctx.needs_input_grad[0] else None
+        ws = lib.workspace(dev, lib.head('mmft_head_mlp_workspace_bytes', T))
+
+        def compute(*outs):
+            shapes = ((hidden, inn), (hidden,), (1, hidden), (1,))
+            res = [o if o is not None else torch.empty(s, dtype=torch.float32, device=dev) for o, s in zip(outs, shapes)]
+            lib.head('mmft_head_mlp_bwd', dpred, hid, xs, xs.stride(0), w1, w2, dx, inn, res[0], res[1], res[2], res[3],
+                     T, inn, hidden, 1, 0, ws, ws.numel() * 4, *lib.stream_args(xs))
+            return res
+
+        dw1, db1, dw2, db2 = gradsink.deliver_many(ctx.sinks, compute)
+        return dx, dw1, db1, dw2, db2, None
+
+
+def head_mlp(x, w1, b1, w2, b2):
+    return Mlp2HeadFn.apply(x, w1, b1, w2, b2, torch.is_grad_enabled())
+
+
 class GatherRowsFn(torch.autograd.Function):
     """out[i] = table[idx[i]] (idx int32 on the device); backward = segmented row sums in a fixed order (bitwise
     reproducible): by binary search when the caller states that idx is ascending (endpoints ordered by level), through a

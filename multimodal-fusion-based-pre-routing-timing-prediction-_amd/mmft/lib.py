@@ -1,6 +1,6 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
 include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, in include/mmft_incr.h,
-called through `incr`, and in include/mmft_crit.h, called through `crit`).
+called through `incr`, in include/mmft_crit.h, called through `crit`, and in include/mmft_head.h, called through `head`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -20,6 +20,7 @@ EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report
 PLACE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_place.h')     # masks that follow a placement
 INCR_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_incr.h')       # sweeps over the fan-out of an edit
 CRIT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit.h')       # criticality per pin and map cell
+HEAD_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_head.h')       # the fusion head's fused MLP
 
 _lib = None
 
@@ -78,6 +79,11 @@ def incr_decls():
 def crit_decls():
     """The same for include/mmft_crit.h (called through `crit`)."""
     return _parse_header(CRIT_HEADER_PATH)
+
+
+def head_decls():
+    """The same for include/mmft_head.h (called through `head`)."""
+    return _parse_header(HEAD_HEADER_PATH)
 
 
 def header_symbols():
@@ -217,6 +223,26 @@ def crit(name, *args):
         fn = getattr(load(), name)
         fn.restype, fn.argtypes = decls[name]
         _CRIT[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_HEAD = {}
+
+
+def head(name, *args):
+    """Call an entry point of include/mmft_head.h, bound from that header on first use, exactly like `crit`: an `int` entry
+    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
+    fn = _HEAD.get(name)
+    if fn is None:
+        decls = head_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {HEAD_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _HEAD[name] = fn
     rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
     if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")

@@ -41,6 +41,9 @@ class MLP(th.nn.Module):
 
     def forward(self, x):
         mods = list(self.layers)
+        if len(mods) == 3 and MF.head_mlp_usable(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, self.negative_slope):
+            # mlp_fuse in bf16 mode: Linear - ReLU - Linear as one fused forward / backward (include/mmft_head.h)
+            return MF.head_mlp(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias)
         i = 0
         while i < len(mods):
             lin = mods[i]
