@@ -10,6 +10,9 @@ The rules (the header states them, `reference_criticality` restates them in nump
   report); a row is valid unless its slack is NaN and violates when slack < 0; minima are taken over valid rows, the smaller
   batch row first on equal slack; node_crit = node_slack / (worst slack of the design), one fp32 division, 1 when they are
   equal, 0 without a violation; the mask of a row is the mask rule of include/mmft_place.h (placement.rasterize_host).
+
+The second half of the module (mmft_criticality_sums, include/mmft_crit_sums.h) adds the sums of negative slack per pin, per
+cell and per design as exact integer sums of quanta, and each pin's and cell's share of its design's TNS.
 """
 import numpy as np
 import torch
@@ -195,4 +198,197 @@ def decode(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, co
             d['cell_slack'] = np.asarray(cell_slack)[b].reshape(int(map_x), int(map_y))
             d['cell_viol'] = np.asarray(cell_viol)[b].reshape(int(map_x), int(map_y))
         out.append(d)
+    return out
+
+
+# ------------------------------------------------------------------------------------------------ negative-slack sums and shares
+# include/mmft_crit_sums.h (mmft_criticality_sums, bound by lib.csum): the seven outputs above, bitwise, and next to them how
+# much negative slack flows through every pin and every cell.  A violating row contributes q = rint(min(-slack, 2^(32 - L)) *
+# 2^L) quanta of 2^-L (L = scale_log2), an integer, so the sums are integer sums: exact, the same in every order.
+SUM_FIELDS = ('node_nsum', 'cell_nsum', 'design_nsum', 'saturated', 'node_share', 'cell_share')
+MAX_ROW_PINS = 1 << 30                             # T * maxlen: every sum is then at most 2^62
+
+
+def sums_workspace_bytes(N, B, P):
+    """Bytes of the keyed words (the sums accumulate in their outputs); P = 0 without the cell outputs."""
+    return lib.csum('mmft_criticality_sums_workspace_bytes', int(N), int(B), int(P))
+
+
+class CritSumsBuffers:
+    """The static output buffers of one mmft_criticality_sums launch, carved out of ONE buffer of 4-byte words so that `host()`
+    is one device->host copy.  The int64 fields come first - node_nsum [N], design_nsum [B], with cells cell_nsum [B, P] - so
+    that they are 8-byte aligned; then the fields of CritBuffers, saturated int32 [B], node_share fp32 [N] and, with cells,
+    cell_share fp32 [B, P]."""
+
+    def __init__(self, N, B, P, device, cells=True):
+        self.N, self.B, self.cells = int(N), int(B), bool(cells)
+        self.P = int(P) if self.cells else 0
+        if self.N < 1 or self.B < 1 or (self.cells and (self.P < 64 or self.P % 64 or self.P > MAX_CELLS)):
+            raise ValueError(f'CritSumsBuffers: need N >= 1, B >= 1 and, with cells, a map of a multiple of 64 cells up to {MAX_CELLS} '
+                             f'(N {N}, B {B}, P {P})')
+        n, b, bp = (self.N,), (self.B,), (self.B, self.P)
+        c = self.cells
+        self._layout = (('node_nsum', 'i8', n), ('design_nsum', 'i8', b)) + ((('cell_nsum', 'i8', bp),) if c else ()) + \
+            (('node_slack', 'f4', n), ('node_row', 'i4', n), ('node_viol', 'i4', n), ('node_crit', 'f4', n), ('counts', 'i4', (self.B, 2)),
+             ('saturated', 'i4', b), ('node_share', 'f4', n)) + \
+            ((('cell_slack', 'f4', bp), ('cell_viol', 'i4', bp), ('cell_share', 'f4', bp)) if c else ())
+        self.raw = torch.empty(sum(int(np.prod(s)) * int(dt[1]) // 4 for _, dt, s in self._layout), dtype=torch.int32, device=device)
+
+    def _carve(self, raw, view):
+        out, pos = dict.fromkeys(FIELDS + SUM_FIELDS), 0
+        for name, dt, shape in self._layout:
+            n = int(np.prod(shape)) * int(dt[1]) // 4
+            out[name] = view(raw[pos:pos + n], dt, shape)
+            pos += n
+        return tuple(out[k] for k in FIELDS + SUM_FIELDS)
+
+    def tensors(self):
+        """The seven of CritBuffers.tensors(), then (node_nsum, cell_nsum, design_nsum, saturated, node_share, cell_share):
+        views of the one buffer; the four cell tensors are None without cells."""
+        kinds = dict(f4=torch.float32, i4=torch.int32, i8=torch.int64)
+        return self._carve(self.raw, lambda t, dt, shape: t.view(kinds[dt]).view(shape))
+
+    def host(self):
+        """One device->host copy -> the same thirteen as numpy arrays (`decode_sums` takes them)."""
+        return self._carve(self.raw.cpu().numpy(), lambda a, dt, shape: a.view(dt).reshape(shape))
+
+
+def criticality_sums(pred, required, placed, paths, row_design, B, scale_log2=20, cells=True, out=None, workspace=None):
+    """Launch mmft_criticality_sums on the current stream -> the seven tensors of `criticality` (bitwise the same) followed by
+    node_nsum, cell_nsum, design_nsum, saturated, node_share, cell_share on the device (the four cell tensors None with
+    cells=False); `decode_sums` turns their host copies into per-design dicts.
+
+    The arguments are those of `criticality`; scale_log2 in [0, 30] is the binary logarithm of the quanta per unit of slack,
+    T * maxlen may be at most 2^30, `out` is CritSumsBuffers.tensors() and `workspace` holds sums_workspace_bytes bytes.
+
+    Everything is validated on the host, dtypes, shapes and contiguity first, before anything is launched."""
+    fn = 'criticality_sums'
+    _vec(fn, pred, 'pred', torch.float32)
+    T = pred.numel()
+    _vec(fn, required, 'required', torch.float32, T)
+    _vec(fn, paths, 'paths', torch.int32, T)
+    if row_design is not None:
+        _vec(fn, row_design, 'row_design', torch.int32, T)
+    if isinstance(scale_log2, bool) or not isinstance(scale_log2, (int, np.integer)) or not 0 <= scale_log2 <= 30:
+        raise ValueError(f'{fn}: scale_log2 must be an integer in [0, 30], got {scale_log2!r}')
+    B, cells, scale_log2 = int(B), bool(cells), int(scale_log2)
+    N = int(placed.loc_x.numel())
+    P = int(placed.P) if cells else 0
+    if T < 1 or T > 1 << 24 or B < 1 or N < 1:
+        raise ValueError(f'{fn}: need 1 <= T <= 2^24, B >= 1, N >= 1 (T {T}, B {B}, N {N})')
+    if T * int(placed.maxlen) > MAX_ROW_PINS:
+        raise ValueError(f'{fn}: T * maxlen must be at most 2^30 for the sums to fit int64 (T {T}, maxlen {placed.maxlen})')
+    if cells and (P % 64 or P > MAX_CELLS or P < 64):
+        raise ValueError(f'{fn}: cells=True needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {P}')
+    if out is None:
+        out = CritSumsBuffers(N, B, P, pred.device, cells=cells).tensors()
+    names = FIELDS + SUM_FIELDS
+    if len(out) != len(names):
+        raise ValueError(f'{fn}: out must be the thirteen tensors of CritSumsBuffers.tensors()')
+    shapes = dict(node_slack=(torch.float32, (N,)), node_row=(torch.int32, (N,)), node_viol=(torch.int32, (N,)),
+                  node_crit=(torch.float32, (N,)), cell_slack=(torch.float32, (B, P)), cell_viol=(torch.int32, (B, P)),
+                  counts=(torch.int32, (B, 2)), node_nsum=(torch.int64, (N,)), cell_nsum=(torch.int64, (B, P)),
+                  design_nsum=(torch.int64, (B,)), saturated=(torch.int32, (B,)), node_share=(torch.float32, (N,)),
+                  cell_share=(torch.float32, (B, P)))
+    given = [(name, t) for name, t in zip(names, out) if cells or not name.startswith('cell_')]
+    for name, t in given:
+        dt, shape = shapes[name]
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'{fn}: {name} must be a contiguous {dt} tensor of shape {shape}')
+    dev = placed.nodes.device
+    every = [pred, required, paths, placed.lens, placed.loc_x, placed.loc_y] + ([row_design] if row_design is not None else []) + \
+        [t for _, t in given]
+    if any(t.device != dev for t in every):
+        raise ValueError(f'{fn}: every tensor must live on the device of the placement tables ({dev})')
+    if dev.type != 'cuda':
+        raise RuntimeError(f'{fn}: the mmft hot path runs on the GPU only (got {dev} tensors); there is no CPU fallback')
+    need = sums_workspace_bytes(N, B, P)
+    if workspace is None:
+        workspace = lib.workspace(dev, need)
+    elif not (torch.is_tensor(workspace) and workspace.device == dev and workspace.is_contiguous()):
+        raise ValueError(f'{fn}: workspace must be a contiguous tensor on {dev}')
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f'{fn}: workspace of {need} bytes needed, got {workspace.numel() * workspace.element_size()}')
+    o = dict(zip(names, out))
+    if not cells:
+        o.update(cell_slack=None, cell_viol=None, cell_nsum=None, cell_share=None)
+    lib.csum('mmft_criticality_sums', pred, required, placed.nodes, placed.lens, placed.maxlen,
+             placed.loc_x if cells else None, placed.loc_y if cells else None, placed.map_x if cells else 0, placed.map_y if cells else 0,
+             paths, row_design, T, N, B, o['node_slack'], o['node_row'], o['node_viol'], o['node_crit'], o['cell_slack'], o['cell_viol'],
+             o['counts'], scale_log2, o['node_nsum'], o['cell_nsum'], o['design_nsum'], o['saturated'], o['node_share'], o['cell_share'],
+             workspace, workspace.numel() * workspace.element_size(), *lib.stream_args(pred))
+    return tuple(o[k] for k in names)
+
+
+def reference_quanta(slack, scale_log2):
+    """(q int64 [T], saturated bool [T]) of fp32 slacks: q = rint(min(-slack, 2^(32 - scale_log2)) * 2^scale_log2) for a row
+    that violates (slack < 0, -inf included), 0 for every other row, NaN rows among them.  In fp64, where the scaling of an
+    fp32 value by a power of two is exact; np.rint rounds to nearest, ties to even."""
+    s = np.asarray(slack, dtype=np.float32).astype(np.float64)
+    with np.errstate(invalid='ignore'):
+        viol = s < 0
+    cap = 2.0 ** (32 - int(scale_log2))
+    m = np.where(viol, -s, 0.0)
+    return np.rint(np.minimum(m, cap) * 2.0 ** int(scale_log2)).astype(np.int64), viol & (m >= cap)
+
+
+def reference_share(nsum, total):
+    """fp32 shares of int64 sums: 0 where total == 0, else float32(float64(nsum) / float64(total)), every step rounded to nearest."""
+    nsum, total = np.asarray(nsum, dtype=np.int64), np.asarray(total, dtype=np.int64)
+    with np.errstate(invalid='ignore', divide='ignore'):
+        return np.where(total == 0, np.float64(0), nsum.astype(np.float64) / total.astype(np.float64)).astype(np.float32)
+
+
+def reference_criticality_sums(pred, required, path_nodes, path_lens, pin_x, pin_y, map_x, map_y, paths, row_design, N, B,
+                               scale_log2=20, cells=True, masks=None):
+    """The contract of include/mmft_crit_sums.h in plain numpy from host arrays -> the thirteen arrays in the layout of the
+    device buffers: the seven of `reference_criticality`, then node_nsum, cell_nsum, design_nsum, saturated, node_share,
+    cell_share (the four cell arrays None with cells=False).  `masks` as in `reference_criticality`."""
+    nodes, lens = np.asarray(path_nodes).astype(np.int64), np.asarray(path_lens).astype(np.int64)
+    paths = np.asarray(paths).astype(np.int64)
+    T, maxlen = paths.shape[0], nodes.shape[1]
+    if cells and masks is None:
+        masks = rasterize_host(nodes, lens, pin_x, pin_y, map_x, map_y)
+    old = reference_criticality(pred, required, nodes, lens, pin_x, pin_y, map_x, map_y, paths, row_design, N, B, cells=cells, masks=masks)
+    design = np.zeros(T, dtype=np.int64) if row_design is None else np.asarray(row_design).astype(np.int64)
+    slack = reference_slack(pred, required)
+    q, sat = reference_quanta(slack, scale_log2)
+    P = int(map_x) * int(map_y) if cells else 0
+    node_nsum, design_nsum = np.zeros(N, dtype=np.int64), np.zeros(B, dtype=np.int64)
+    cell_nsum = np.zeros((B, P), dtype=np.int64) if cells else None
+    saturated = np.zeros(B, dtype=np.int32)
+    with np.errstate(invalid='ignore'):
+        violating = np.flatnonzero(slack < 0)                      # the violating valid rows (a NaN is not below zero)
+    for t in violating:
+        b, p = int(design[t]), int(paths[t])
+        design_nsum[b] += q[t]                                     # every such row, whatever its path holds
+        saturated[b] += sat[t]
+        np.add.at(node_nsum, nodes[p, :min(int(lens[p]), maxlen)], q[t])        # once per live position
+        if cells:
+            c = np.asarray(masks[1][masks[0][p]:masks[0][p + 1]]).astype(np.int64)
+            cell_nsum[b, c] += q[t]                                # a mask is a set: once per row
+    node_row = old[1]
+    total = np.where(node_row >= 0, design_nsum[design[np.maximum(node_row, 0)]], 0)
+    node_share = reference_share(node_nsum, total)
+    cell_share = reference_share(cell_nsum, design_nsum[:, None]) if cells else None
+    return tuple(old) + (node_nsum, cell_nsum, design_nsum, saturated, node_share, cell_share)
+
+
+def decode_sums(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts, node_nsum, cell_nsum, design_nsum,
+                saturated, node_share, cell_share, node_off, scale_log2, map_x=None, map_y=None):
+    """Host copies of the thirteen buffers -> one dict per design: what `decode` gives, and node_tns (fp64, the design's own
+    node order) and cell_tns (fp64 [map_x, map_y] or None) = -nsum / 2^scale_log2, so <= 0 like the report's tns; tns, the
+    design's own; node_share, cell_share (fp32) and saturated, the number of rows that hit the cap."""
+    out = decode(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts, node_off, map_x=map_x, map_y=map_y)
+    node_off, unit = np.asarray(node_off).astype(np.int64), 2.0 ** int(scale_log2)
+    for b, d in enumerate(out):
+        lo, hi = int(node_off[b]), int(node_off[b + 1])
+        d['node_tns'] = 0.0 - np.asarray(node_nsum)[lo:hi].astype(np.float64) / unit
+        d['node_share'] = np.asarray(node_share)[lo:hi]
+        d['cell_tns'] = d['cell_share'] = None
+        if cell_nsum is not None:
+            d['cell_tns'] = 0.0 - np.asarray(cell_nsum)[b].astype(np.float64).reshape(int(map_x), int(map_y)) / unit
+            d['cell_share'] = np.asarray(cell_share)[b].reshape(int(map_x), int(map_y))
+        d['tns'] = 0.0 - float(np.asarray(design_nsum)[b]) / unit
+        d['saturated'] = int(np.asarray(saturated)[b])
     return out

@@ -135,7 +135,13 @@ class Predictor:
                           pins as they are now (a map of a multiple of 64 cells, at most 65536).  Every design carries
                           placement data; placement=True is NOT needed: without it the option keeps tables of its own and
                           the pins never move, with it the same tables serve both and the cell maps follow
-                          update(i, pin_x=..., pin_y=...).  Regression task only.  predict() returns what it returns without it
+                          update(i, pin_x=..., pin_y=...).  Regression task only.  predict() returns what it returns without it.
+                          dict(cells=..., sums=True, scale_log2=20): the launches are those of mmft_criticality_sums
+                          (include/mmft_crit_sums.h) INSTEAD - the same outputs, bitwise, and from the same walk the sums of
+                          negative slack per pin, per cell and per design as exact integer sums of quanta of 2^-scale_log2
+                          (scale_log2 in [0, 30], refused without sums), every pin's and cell's share of its design's TNS and
+                          the rows that hit the cap; criticality() then also returns node_tns, cell_tns, tns, node_share,
+                          cell_share and saturated (mmft.criticality.decode_sums).  Without sums nothing about the call changes
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
@@ -225,9 +231,15 @@ class Predictor:
         spec = {} if spec is True else spec
         if not isinstance(spec, dict):
             raise ValueError(f'Predictor: criticality= takes None, True or dict(cells=...), got {spec!r}')
-        unknown = set(spec) - {'cells'}
+        unknown = set(spec) - {'cells', 'sums', 'scale_log2'}
         if unknown:
-            raise ValueError(f'Predictor: criticality= takes cells, got {sorted(unknown)}')
+            raise ValueError(f'Predictor: criticality= takes cells, sums and scale_log2, got {sorted(unknown)}')
+        if 'scale_log2' in spec:
+            L = spec['scale_log2']
+            if not spec.get('sums'):
+                raise ValueError(f'Predictor: criticality= takes scale_log2 only with sums=True, got {spec!r}')
+            if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 0 <= L <= 30:
+                raise ValueError(f'Predictor: criticality= takes an integer scale_log2 in [0, 30], got {L!r}')
         return spec
 
     def _make_criticality(self, spec, designs):
@@ -235,7 +247,7 @@ class Predictor:
         tables of its own, whose pins never move), the rows' required times and designs, static output buffers and the
         keyed-word workspace - static addresses, kept alive with the replay."""
         from . import criticality as K, placement as PL
-        cells = bool(spec.get('cells', True))
+        cells, sums, scale_log2 = bool(spec.get('cells', True)), bool(spec.get('sums', False)), int(spec.get('scale_log2', 20))
         required, design = self._slack_rows('criticality=')
         for i, d in enumerate(designs):
             if not PL.has_placement(d):
@@ -248,9 +260,14 @@ class Predictor:
         placed = self._placed if self._placed is not None else PL.PlacedPaths(designs, b.node_off, dev)
         row_design = torch.from_numpy(design.astype(np.int32)).to(dev) if b.B > 1 else None
         N = int(b.node_off[-1])
-        bufs = K.CritBuffers(N, b.B, placed.P, dev, cells=cells)
-        scratch = torch.empty((K.workspace_bytes(N, b.B, placed.P if cells else 0) + 7) // 8, dtype=torch.int64, device=dev)
-        return dict(cells=cells, placed=placed, required=required, row_design=row_design, bufs=bufs, scratch=scratch, ready=False)
+        if sums and required.numel() * int(placed.maxlen) > K.MAX_ROW_PINS:
+            raise ValueError(f'Predictor: criticality=dict(sums=True) needs rows * maxlen <= 2^30 for the sums to fit int64; '
+                             f'it has {required.numel()} * {placed.maxlen}')
+        bufs = (K.CritSumsBuffers if sums else K.CritBuffers)(N, b.B, placed.P, dev, cells=cells)
+        need = (K.sums_workspace_bytes if sums else K.workspace_bytes)(N, b.B, placed.P if cells else 0)
+        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        return dict(cells=cells, sums=sums, scale_log2=scale_log2, placed=placed, required=required, row_design=row_design, bufs=bufs,
+                    scratch=scratch, ready=False)
 
     def _make_report(self, spec):
         """Everything the report launch needs that the static selection decides: the endpoints' required times, the rows of
@@ -339,8 +356,12 @@ class Predictor:
         if self._crit is not None:
             from . import criticality as K
             c = self._crit
-            K.criticality(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B, cells=c['cells'],
-                          out=c['bufs'].tensors(), workspace=c['scratch'])
+            if c['sums']:                                        # one launch group: the sums' kernels write the other outputs too
+                K.criticality_sums(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B,
+                                   scale_log2=c['scale_log2'], cells=c['cells'], out=c['bufs'].tensors(), workspace=c['scratch'])
+            else:
+                K.criticality(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B, cells=c['cells'],
+                              out=c['bufs'].tensors(), workspace=c['scratch'])
             c['ready'] = True
         return pred
 
@@ -427,7 +448,8 @@ class Predictor:
     def criticality(self, i=None):
         """The criticality of the LAST predict(): one dict per design, or design i's (mmft.criticality.decode: node_slack,
         node_row, node_viol, node_crit in the design's own node order - node_row is a row of `pred` -, cell_slack and
-        cell_viol as [map, map] arrays or None, n, n_nan).  One device->host copy."""
+        cell_viol as [map, map] arrays or None, n, n_nan; with sums=True also node_tns, cell_tns, tns, node_share, cell_share and
+        saturated: mmft.criticality.decode_sums).  One device->host copy."""
         from . import criticality as K
         if self._crit is None:
             raise RuntimeError('Predictor.criticality(): no criticality was requested (criticality=True or dict(cells=...))')
@@ -436,7 +458,11 @@ class Predictor:
         if i is not None and not 0 <= i < self.batch.B:
             raise IndexError(f'criticality: design {i} of {self.batch.B}')
         placed = self._crit['placed']
-        out = K.decode(*self._crit['bufs'].host(), node_off=self.batch.node_off, map_x=placed.map_x, map_y=placed.map_y)
+        if self._crit['sums']:
+            out = K.decode_sums(*self._crit['bufs'].host(), node_off=self.batch.node_off, scale_log2=self._crit['scale_log2'],
+                                map_x=placed.map_x, map_y=placed.map_y)
+        else:
+            out = K.decode(*self._crit['bufs'].host(), node_off=self.batch.node_off, map_x=placed.map_x, map_y=placed.map_y)
         return out if i is None else out[i]
 
     def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None, rows=None):

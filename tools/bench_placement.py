@@ -24,7 +24,12 @@ predict_crit_pins / predict_crit); the three launches of mmft_criticality alone 
 crit_alone), next to the number of (row, pin) and (row, covered cell) pairs, so that the rate of the integer atomics can be read
 off; and the host route from the same predictions: copy `pred` back and np.minimum.at over path_nodes for the pins (host_pins),
 rasterize_host plus np.minimum.at / np.add.at over the mask columns for the cells, at design 0 only (host_cells_design0).  The
-device result must equal reference_criticality bitwise.
+device result must equal reference_criticality bitwise.  Next to them, alternating inside the same rounds, the same two
+Predictors with sums=True (predict_crit_sums_pins / predict_crit_sums: mmft_criticality_sums instead of mmft_criticality, the
+sums of negative slack and the TNS shares from the same walk), whose device result must equal reference_criticality_sums
+bitwise; the launches alone (crit_sums_alone_pins / crit_sums_alone); and the host route for the sums: np.add.at over path_nodes
+(host_sums_pins), the mask columns of design 0 (host_sums_cells_design0, masks given: the rasterisation is host_cells_design0's).
+--no-sums leaves every sums row out: for a run on an older build of the library (MMFT_LIB), which does not export the entry point.
 Needs a GPU."""
 import argparse
 import copy
@@ -72,6 +77,10 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     preds = {'predict_plain': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True),
              'predict_crit_pins': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, criticality=dict(cells=False)),
              'predict_crit': Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, criticality=True)}
+    if not a.no_sums:
+        for nm, cells in (('predict_crit_sums_pins', False), ('predict_crit_sums', True)):
+            preds[nm] = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True,
+                                  criticality=dict(cells=cells, sums=True, scale_log2=a.scale_log2))
     for _ in range(3):
         ys = [q.predict()[0].clone() for q in preds.values()]
     assert all(torch.equal(ys[0], y) for y in ys) and all(q._replay.graph is not None for q in preds.values())
@@ -98,6 +107,21 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     emit(row='outputs', equals_reference_bitwise=bool(same), violating_rows=int((slack < 0).sum()), pins_with_a_path=int((ref[1] >= 0).sum()),
          critical_pins=int((ref[3] > 0).sum()), cells_with_a_violation=int((ref[5] > 0).sum()))
     assert same
+    if not a.no_sums:
+        masks = (np.concatenate([[0], np.cumsum(cells_of)]), np.concatenate([d.mask_cols for d in designs]))
+        ref13 = K.reference_criticality_sums(pred, required, nodes, lens, px, py, m, m, paths, design if len(designs) > 1 else None,
+                                             got[0].shape[0], len(designs), scale_log2=a.scale_log2, masks=masks)
+        bits13 = lambda x: np.ascontiguousarray(x).view(np.int32 if x.dtype.itemsize == 4 else np.int64)
+        got13 = preds['predict_crit_sums']._crit['bufs'].host()
+        pins13 = preds['predict_crit_sums_pins']._crit['bufs'].host()
+        same13 = all(np.array_equal(bits13(g), bits13(r)) for g, r in zip(got13, ref13))
+        same_pins = all(np.array_equal(bits13(g), bits13(r)) for g, r in zip(pins13, ref13) if g is not None)
+        emit(row='outputs_sums', equals_reference_bitwise=bool(same13), pins_only_equals_reference_bitwise=bool(same_pins),
+             old_seven_equal_criticality_bitwise=bool(all(np.array_equal(bits(g), bits(r)) for g, r in zip(got13[:7], got))),
+             scale_log2=a.scale_log2, saturated_rows=int(ref13[10].sum()), tns=[-float(x) / 2.0 ** a.scale_log2 for x in ref13[9]],
+             pins_with_a_sum=int((ref13[7] > 0).sum()), cells_with_a_sum=int((ref13[8] > 0).sum()),
+             largest_pin_share=float(ref13[11].max()), largest_cell_share=float(ref13[12].max()))
+        assert same13 and same_pins
 
     # replayed predict() with and without the option, and the three launches alone
     def alone(q):
@@ -106,6 +130,13 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
                                      out=k['bufs'].tensors(), workspace=k['scratch'])
     rows = {nm: (lambda q=q: q.predict()[0]) for nm, q in preds.items()}
     rows['crit_alone_pins'], rows['crit_alone'] = alone(preds['predict_crit_pins']), alone(p)
+
+    def sums_alone(q):
+        k = q._crit
+        return lambda: K.criticality_sums(ys[0].reshape(-1), k['required'], k['placed'], q._sel[1], k['row_design'], len(designs),
+                                          scale_log2=k['scale_log2'], cells=k['cells'], out=k['bufs'].tensors(), workspace=k['scratch'])
+    if not a.no_sums:
+        rows['crit_sums_alone_pins'], rows['crit_sums_alone'] = sums_alone(preds['predict_crit_sums_pins']), sums_alone(preds['predict_crit_sums'])
     for fn in rows.values():
         timed(fn, a.reps)
     ms = {nm: [] for nm in rows}
@@ -115,8 +146,8 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     for nm in rows:
         med = statistics.median(ms[nm])
         extra = {}
-        if nm.startswith('crit_alone'):
-            pairs = pin_pairs + (cell_pairs if nm == 'crit_alone' else 0)
+        if nm.startswith('crit_alone') or nm.startswith('crit_sums_alone'):
+            pairs = pin_pairs + (cell_pairs if nm in ('crit_alone', 'crit_sums_alone') else 0)
             extra = dict(pairs=pairs, ns_per_pair_median=1e6 * med / pairs)
         emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=med, ms_min=min(ms[nm]), ms_max=max(ms[nm]), **extra)
 
@@ -160,6 +191,44 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     assert np.array_equal(bits(cell_slack), bits(ref[4][0])) and np.array_equal(cell_viol, ref[5][0])
     emit(row='host_cells_design0', repetitions=a.rebuilds, s_median=statistics.median(x for x, _ in t), s_min=min(x for x, _ in t),
          s_max=max(x for x, _ in t), s_rasterise_median=statistics.median(x for _, x in t))
+    if a.no_sums:
+        return
+
+    # the host route for the sums, from the same predictions
+    def host_sums_pins():
+        t0 = time.perf_counter()
+        q, _ = K.reference_quanta(reference_slack(ys[0].cpu().numpy().reshape(-1), required), a.scale_log2)
+        live = np.arange(nodes.shape[1])[None, :] < np.minimum(lens, nodes.shape[1])[paths][:, None]
+        live &= (q > 0)[:, None]
+        node_nsum = np.zeros(got[0].shape[0], dtype=np.int64)
+        np.add.at(node_nsum, nodes[paths][live], np.broadcast_to(q[:, None], live.shape)[live])
+        total = np.zeros(len(designs), dtype=np.int64)
+        np.add.at(total, design, q)
+        weights = torch.from_numpy(node_nsum).to(dev)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, node_nsum, total, weights
+
+    def host_sums_cells(i):
+        t0 = time.perf_counter()
+        q, _ = K.reference_quanta(reference_slack(ys[0].cpu().numpy().reshape(-1), required), a.scale_log2)
+        cell_nsum = np.zeros(m * m, dtype=np.int64)
+        for t in np.flatnonzero((design == i) & (q > 0)):
+            cell_nsum[masks[1][masks[0][paths[t]]:masks[0][paths[t] + 1]]] += q[t]
+        weights = torch.from_numpy(cell_nsum).to(dev)
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0, cell_nsum, weights
+    t = []
+    for _ in range(a.rebuilds):
+        dt, node_nsum, total, _ = host_sums_pins()
+        t.append(dt)
+    assert np.array_equal(node_nsum, ref13[7]) and np.array_equal(total, ref13[9])
+    emit(row='host_sums_pins', repetitions=a.rebuilds, s_median=statistics.median(t), s_min=min(t), s_max=max(t))
+    t = []
+    for _ in range(a.rebuilds):
+        dt, cell_nsum, _ = host_sums_cells(0)
+        t.append(dt)
+    assert np.array_equal(cell_nsum, ref13[8][0])
+    emit(row='host_sums_cells_design0', repetitions=a.rebuilds, s_median=statistics.median(t), s_min=min(t), s_max=max(t))
 
 
 def main():
@@ -171,6 +240,8 @@ def main():
     ap.add_argument('--rebuilds', type=int, default=3)
     ap.add_argument('--trace', action='store_true')
     ap.add_argument('--criticality', action='store_true')
+    ap.add_argument('--no-sums', action='store_true', help='--criticality without the sums rows (a library older than version 207)')
+    ap.add_argument('--scale-log2', type=int, default=20)
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
