@@ -507,6 +507,32 @@ def mlp2_feat_bwd_bf16(g, x, rows, w1, b1, w2, dw1=None, db1=None, dw2=None, db2
     return dw1, db1, dw2, db2
 
 
+def mlp2_feat_dx_bf16(g, x, rows, w1, b1, w2, dx=None):
+    """dx[rows, :fin] = ((g[rows] w2) * relu'(x[rows] w1^T + b1)) w1 over a contiguous node range rows = (row0, n): the gradient
+    of that MLP with respect to its input rows, the hidden activations recomputed (mmft_mlp2_feat_dx_bf16; bf16 math mode).
+    dx (fp32 [N, >= fin], unit inner stride; None: zeros [N, fin]): only the rows of the range and their first fin columns
+    are written."""
+    _rows2d(g, 'g'); _rows2d(x, 'x')
+    fin = x.shape[1]
+    rt, row0, n = _rowspec(rows, x.shape[0], 'rows')
+    if rt is not None or g.shape[0] != x.shape[0] or g.shape[1] != 128:
+        raise ValueError('mlp2_feat_dx_bf16: rows must be a (row0, n) range over node-indexed g [N, 128] / x [N, fin]')
+    if dx is None:
+        dx = torch.zeros((x.shape[0], fin), dtype=torch.float32, device=x.device)
+    _rows2d(dx, 'dx')
+    if dx.shape[0] != x.shape[0] or dx.shape[1] < fin or dx.device != x.device:
+        raise ValueError('mlp2_feat_dx_bf16: dx must be a node-indexed [N, >= fin] tensor on the device of x')
+    for t, nm in ((w1, 'w1'), (b1, 'b1'), (w2, 'w2')):
+        _chk(t, nm)
+        if not t.is_contiguous():
+            raise ValueError(f'mlp2_feat_dx_bf16: {nm} must be contiguous')
+    if tuple(w1.shape) != (256, fin) or b1.numel() != 256 or tuple(w2.shape) != (128, 256):
+        raise ValueError('mlp2_feat_dx_bf16: fin -> 256 -> 128')
+    dev, st = lib.stream_args(x)
+    lib.sens('mmft_mlp2_feat_dx_bf16', g, g.stride(0), x, x.stride(0), row0, n, fin, w1, b1, w2, dx, dx.stride(0), dev, st)
+    return dx
+
+
 def _edge_drivers(drv, indices):
     if drv is None:
         return None

@@ -1,0 +1,223 @@
+"""Sensitivity of the predicted timing: `Sensitivity` holds a batch of designs on the device like `infer.Predictor` and answers
+"which change would help" with one reverse sweep - the gradient of a weighted sum of the predictions,
+
+    J = sum_r w_r pred_r,
+
+with respect to every row of cell_feat and net_feat, handed out per design in the design's own node order.
+
+What runs.  The U-Net, the masked projection and h_cnn run under no_grad exactly as in Predictor._launches: they do not
+depend on the features.  The netlist sweep runs in its training form (sweep.SweepFn keeps A / LSE / the hidden rows) and the
+fusion head on top of it; torch.autograd.grad seeds the existing reverse sweep with w as the gradient of the predictions.
+After it the sweep's G holds, for every cell and net row, the gradient at the output of fc_cell_self / fc_net_self - the rows
+mlp2_feat_bwd_kernel reads for the weight gradients.  The last hop, through the two feature MLPs to their inputs, is
+mmft_mlp2_feat_dx_bf16 (include/mmft_sens.h, csrc/mlp_feat_dx.hip): two launches over the row ranges of
+sweep._batched_param_grads, in bf16 mode on a schedule where the sweep's feat_fused holds.  In fp32 mode, or where the rows
+are not a range, the same result comes from the generic layers (linear_fwd recomputes H, linear_dgrad(mask=H), linear_dgrad).
+
+Eager only: the forward + backward pair is not captured and replayed.  Nothing of the model is written - no parameter, no
+buffer, no .grad (torch.autograd.grad, not .backward()), no requires_grad flag, no module mode.  A model whose parameters carry
+gradient sinks (mmft.gradsink: a trainer with the fused optimizer owns it) is refused: the reverse sweep would deliver its
+weight gradients into that trainer's flat gradient buffer.
+"""
+import contextlib
+
+import numpy as np
+import torch
+
+from . import gradsink, lib, ops
+from .evaluate import frozen_statistics
+from .fusion import MaskedPathMap
+from .infer import design_permutations, update_design
+from .train import DesignBatch
+
+OBJECTIVES = ('tns', 'sum')
+
+
+def check_model(pmodel):
+    """The refusals that the model alone decides, on the host: no netlist branch, the attention branch, a head that is not the
+    regression head (ValueError); gradient sinks on a parameter (RuntimeError)."""
+    if getattr(pmodel, 'gnn', None) is None:
+        raise ValueError('Sensitivity: the model has no netlist branch (pmodel.gnn is None): nothing depends on the features')
+    if getattr(pmodel.gnn, 'flag_attn', False):
+        raise ValueError('Sensitivity: PathConv(flag_attn=True) is not supported (the attention branch reads net_feat through '
+                         'h_drive and keeps the per-level sweep)')
+    nlabels = pmodel.mlp_fuse.layers[-1].out_features
+    if nlabels != 1:
+        raise ValueError(f'Sensitivity: needs the regression head (nlabels = 1), the model has {nlabels} labels')
+    check_no_sinks(pmodel)
+
+
+def check_no_sinks(pmodel):
+    sunk = [n for n, p in pmodel.named_parameters() if gradsink.of(p) is not None]
+    if sunk:
+        raise RuntimeError(f'Sensitivity: {len(sunk)} parameters of the model carry gradient sinks ({sunk[0]}, ...): a trainer with '
+                           'the fused optimizer owns it, and the reverse sweep would write into its flat gradient buffer')
+
+
+def check_objective(objective):
+    if objective not in OBJECTIVES:
+        raise ValueError(f'Sensitivity.run: unknown objective {objective!r} (expected one of {OBJECTIVES})')
+    return objective
+
+
+def check_weights(weights, T):
+    """weights= of run(): None, or a float32 [T] numpy array or tensor (host or device); TypeError / ValueError otherwise."""
+    if weights is None:
+        return None
+    w = torch.from_numpy(weights) if isinstance(weights, np.ndarray) else weights
+    if not torch.is_tensor(w):
+        raise TypeError('Sensitivity.run: weights must be a numpy array or a tensor')
+    if w.dtype != torch.float32:
+        raise TypeError(f'Sensitivity.run: weights must be float32, got {w.dtype}')
+    if w.dim() != 1 or w.numel() != T:
+        raise ValueError(f'Sensitivity.run: weights has shape {tuple(w.shape)}, one weight per predicted path expected ({T},)')
+    return w
+
+
+class Sensitivity:
+    """Sensitivity(pmodel, cnn, designs, device).run() -> (pred, endpoints, grads).
+
+    path_ids_per_design   per design the paths that are predicted and weighted (None: every path of every design); one static
+                          selection, made here
+    frozen_stats          the U-Net normalises with its running statistics for the call (evaluate.frozen_statistics)
+    overlap               the netlist sweep on a side stream under the U-Net (as Predictor)
+
+    Attributes: endpoints (host int64 [T], as Predictor's), required (fp32 [T] on the device: the rows' required times),
+    row_design (host int64 [T]: the design of each row of pred), feat_map (the U-Net's output of the last run(), [B, P]),
+    last_hop ('fused' / 'layers': which route the last run() took through the feature MLPs).
+    force_layers = True sends the last hop through the generic layers also where the fused kernel would run."""
+
+    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, overlap=True):
+        check_model(pmodel)
+        self.pmodel, self.cnn = pmodel, cnn
+        self.device = torch.device(device)
+        self.frozen_stats, self.overlap = bool(frozen_stats), bool(overlap)
+        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
+        b = self.batch = DesignBatch(designs, device, pmodel.gnn.out_feat_dim)
+        if path_ids_per_design is None:
+            path_ids_per_design = [np.arange(d.num_paths) for d in designs]
+        T = int(sum(len(p) for p in path_ids_per_design))
+        if T == 0:
+            raise ValueError('Sensitivity: no path selected')
+        self.T = T
+        self._sel = b.select(path_ids_per_design)
+        self._links, self._end_order = b.links, b.end_order
+        self.endpoints = np.asarray(self._sel[4])
+        self.required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
+        self.row_design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
+        self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
+        self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
+        self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
+        self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
+        nd = b.graph.ndata
+        # rows outside the (even / odd) levels are never written: zero for the life of the object
+        self._dx = {k: torch.zeros_like(nd[k]) for k in ('cell_feat', 'net_feat')}
+        self.feat_map = self.last_hop = None
+        self.force_layers = False
+
+    @contextlib.contextmanager
+    def _modes_kept(self):
+        """Module modes and the U-Net's statistics-per-image switch back as found, also on an exception (Predictor._modes_kept)."""
+        modes = [(m, m.training) for m in self._modules]
+        per = [(m, m.per_sample_stats) for m in self._per_sample]
+        try:
+            for m in self._per_sample:
+                m.per_sample_stats = True
+            yield
+        finally:
+            for m, was in per:
+                m.per_sample_stats = was
+            for m, was in modes:
+                m.training = was
+
+    def update(self, i, cell_feat=None, net_feat=None, image=None, rows=None):
+        """New features / a new layout image of design i, as Predictor.update (infer.update_design): the next run() sees them."""
+        update_design(self.batch, self._perm[i] if 0 <= i < self.batch.B else None, i, cell_feat, net_feat, image, rows=rows)
+
+    def _forward(self):
+        """pred [T] with the sweep and the head on the autograd tape; everything in front of them under no_grad."""
+        from . import sweep as _sweep
+        b, g, pm_ = self.batch, self.batch.graph, self.pmodel
+        ends_d, paths_d, foff_d, _, _, lv_d = self._sel
+        g.ndata['h'] = self.h
+        cur = torch.cuda.current_stream(self.device)
+        sweep = lambda: _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order)
+        with torch.enable_grad():
+            if self.overlap:
+                self.side.wait_stream(cur)
+                with torch.cuda.stream(self.side):
+                    h_gnn = sweep()
+            else:
+                h_gnn = sweep()
+        st = g._sweep
+        with torch.no_grad():
+            feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
+            pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
+            if self.overlap:
+                # joined BEFORE the masked projection, as TrainStep.forward does
+                cur.wait_stream(self.side)
+                h_gnn.record_stream(cur)
+            h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
+        self.feat_map = feat
+        with torch.enable_grad():
+            pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+        return pred, st
+
+    def _last_hop(self, st):
+        """G -> d J / d cell_feat, d J / d net_feat over the rows of the even / odd levels (sweep._batched_param_grads' row sets)."""
+        from .sweep import _cat_rows, _rows_of, _w
+        P = [_w(p) for p in st.params]
+        (w1c, b1c, w2c, _, w1n, b1n, w2n, _) = P[0:8]
+        rc = _cat_rows(st, lambda l: l % 2 == 0)
+        rn = _cat_rows(st, lambda l: l % 2 == 1)
+        fused = bool(st.feat_fused) and not self.force_layers and all(isinstance(r, tuple) for r in (rc, rn) if r is not None)
+        self.last_hop = 'fused' if fused else 'layers'
+        for rows, X, w1, b1, w2, dx in ((rc, st.cell_feat, w1c, b1c, w2c, self._dx['cell_feat']),
+                                        (rn, st.net_feat, w1n, b1n, w2n, self._dx['net_feat'])):
+            if rows is None:
+                continue
+            if fused:
+                ops.mlp2_feat_dx_bf16(st.G, X, rows, w1, b1, w2, dx=dx)
+                continue
+            Xv, idx = _rows_of(X, rows)
+            Gv, _ = _rows_of(st.G, rows)
+            Dv, _ = _rows_of(dx, rows)
+            H = ops.linear_fwd(Xv, w1, b1, xidx=idx, act=ops.ACT_RELU)               # [n, 256], materialised
+            dH = ops.linear_dgrad(Gv, w2, gidx=idx, mask=H)
+            ops.linear_dgrad(dH, w1, dx=Dv, dxidx=idx)
+
+    def run(self, weights=None, objective='tns'):
+        """(pred, endpoints, grads).  pred [T] on the device and endpoints (host int64 [T]) are what Predictor.predict() returns;
+        grads[i] = dict(cell_feat=[N_i, Fc], net_feat=[N_i, Fn]): fp32 device tensors in design i's own node order, the
+        gradient of J = sum_r w_r pred_r.  weights: float32 [T], host or device, one per row of pred.  Without weights,
+        objective='tns': w_r = 1 where required_r - pred_r < 0 on this call's own predictions (NaN rows get 0) - the gradient
+        of the magnitude of the total negative slack; objective='sum': w_r = 1.  cell_feat gradients live on the rows of even
+        levels, net_feat gradients on the rows of odd levels; every other row is exactly 0."""
+        check_objective(objective)
+        w = check_weights(weights, self.T)
+        check_no_sinks(self.pmodel)
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError('Sensitivity.run() under an outer stream capture: the forward + backward pair runs eagerly '
+                               '(its weights may depend on this call\'s predictions)')
+        from .sweep import _MLP_KEYS, _mlp2_params
+        if not any(p.requires_grad for k in _MLP_KEYS for p in _mlp2_params(getattr(self.pmodel.gnn, k))):
+            raise RuntimeError('Sensitivity.run: no parameter of fc_cell_self / fc_net_self / fc_cell_neigh requires a gradient - the '
+                               'sweep then runs in its forward-only form, which keeps nothing for a reverse sweep')
+        cur = torch.cuda.current_stream(self.device)
+        with self._modes_kept(), frozen_statistics(self.cnn, self.frozen_stats):
+            pred, st = self._forward()
+            out = pred.detach()
+            if w is not None:
+                w = w.to(self.device, non_blocking=True).contiguous()
+            elif objective == 'tns':
+                w = ((self.required - out) < 0).to(torch.float32)
+            else:
+                w = torch.ones_like(out)
+            inputs = [p for p in st.params if p.requires_grad]
+            torch.autograd.grad(pred, inputs, grad_outputs=w.reshape(pred.shape), allow_unused=True)
+            if self.overlap:
+                cur.wait_stream(self.side)            # the reverse sweep ran on the stream of its forward
+            self._last_hop(st)
+        grads = [dict(cell_feat=self._dx['cell_feat'].index_select(0, p), net_feat=self._dx['net_feat'].index_select(0, p))
+                 for p in self._perm]
+        return out, self.endpoints, grads

@@ -1,0 +1,141 @@
+"""What "which change would help" costs, in bf16 math mode at config B shapes (8 designs x 65 536 nodes, 64 levels).
+
+    python tools/bench_sensitivity.py [--designs 8] [--paths 1350] [--reps 10] [--rounds 5] [--out FILE]
+
+Every row is the HOST clock around the call + synchronise - what a sizing loop waits for:
+  run            Sensitivity.run(objective='sum'): forward in the training form, reverse sweep, the last hop on
+                 mmft_mlp2_feat_dx_bf16 - the gradient of the summed arrival times with respect to EVERY cell_feat and net_feat
+                 row ('sum', not the default 'tns': the freshly initialised model of this tool predicts no violation on the
+                 synthetic designs, and all-zero weights would make the comparison of the two routes empty; the launches and
+                 their cost do not depend on the weights)
+  run_layers     the same run() with the last hop forced onto the generic layers (linear_fwd, linear_dgrad(mask=H),
+                 linear_dgrad), which materialises the hidden tensor H and its gradient
+  trial_one_row  Predictor.update(i, cell_feat=, rows=[one cell]) + a replayed predict(): the per-row cost of finding the
+                 same thing out by trial (the edited values alternate between two tables)
+The rows alternate inside each of `rounds` rounds; per row the median and min .. max over the rounds of the mean over `reps`
+calls.  Then one profiled pass of run and of run_layers gives the kernel time of the last hop alone (the launch profiler's
+device events) and the bytes its kernels need, and the two routes' gradients are compared.  One JSON line per row.  Needs a
+GPU."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PKG = os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd')
+for p in (ROOT, PKG):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+from mmft import lib                                               # noqa: E402
+from mmft.infer import Predictor                                   # noqa: E402
+from mmft.sensitivity import Sensitivity                           # noqa: E402
+from mmft.synth import config_design                               # noqa: E402
+from mmft.train import build_models                                # noqa: E402
+
+def host_ms(fn, reps):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(reps):
+        fn()
+        torch.cuda.synchronize()
+    return 1e3 * (time.perf_counter() - t0) / reps
+
+
+def rel_err(a, b):
+    return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--designs', type=int, default=8)
+    ap.add_argument('--paths', type=int, default=1350, help='endpoints per design (0: all)')
+    ap.add_argument('--reps', type=int, default=10)
+    ap.add_argument('--rounds', type=int, default=5)
+    ap.add_argument('--out', default=None)
+    a = ap.parse_args()
+    assert torch.cuda.is_available(), 'needs a GPU'
+    dev = torch.device('cuda:0')
+    lines = []
+
+    def emit(**row):
+        lines.append(json.dumps(row))
+        print(lines[-1], flush=True)
+        if a.out:
+            os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+            with open(a.out, 'w') as f:
+                f.write('\n'.join(lines) + '\n')
+
+    designs = [config_design('B', i) for i in range(a.designs)]
+    rng = np.random.default_rng(6)
+    ids = [np.sort(rng.permutation(d.num_paths)[:a.paths]) if a.paths else np.arange(d.num_paths) for d in designs]
+    pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=9294)
+    mid = (designs[0].L // 2) & ~1                                  # the middle CELL level
+    cell = np.asarray(designs[0].levels[mid][:1], dtype=np.int64)
+    tables = [torch.from_numpy(designs[0].cell_feat[cell] + np.float32(0.25 * (k + 1))).to(dev) for k in (0, 1)]
+    flip = [0]
+
+    with lib.math_mode('bf16'):
+        sens = Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+        pred_ = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+
+        def run(layers):
+            sens.force_layers = layers
+            out = sens.run(objective='sum')
+            assert sens.last_hop == ('layers' if layers else 'fused'), sens.last_hop
+            return out
+
+        def trial():
+            flip[0] ^= 1
+            pred_.update(0, cell_feat=tables[flip[0]], rows=cell)
+            with torch.no_grad():
+                return pred_.predict()[0]
+
+        rows = {'run': lambda: run(False), 'run_layers': lambda: run(True), 'trial_one_row': trial}
+        for fn in rows.values():                                     # warm-up of every row (the third predict() replays)
+            host_ms(fn, 3)
+        assert pred_._replay is not None and pred_._replay.graph is not None
+        b = sens.batch
+        n_cell = sum(len(l) for l in b.level_nodes[0::2])
+        n_net = sum(len(l) for l in b.level_nodes[1::2])
+        emit(row='shapes', designs=a.designs, nodes=int(b.N), levels=int(b.L), endpoints=int(sens.T), cell_rows=n_cell, net_rows=n_net,
+             feature_rows=n_cell + n_net)
+        ms = {nm: [] for nm in rows}
+        for _ in range(a.rounds):
+            for nm, fn in rows.items():
+                ms[nm].append(host_ms(fn, a.reps))
+        for nm in rows:
+            emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=statistics.median(ms[nm]), ms_min=min(ms[nm]), ms_max=max(ms[nm]))
+        emit(row='trial_of_every_feature_row_over_run',
+             ratio=(n_cell + n_net) * statistics.median(ms['trial_one_row']) / statistics.median(ms['run']))
+        # the two routes' results
+        _, _, gf = run(False)
+        _, _, gl = run(True)
+        emit(row='outputs', fused_vs_layers={k: max(rel_err(x[k], y[k]) for x, y in zip(gf, gl)) for k in ('cell_feat', 'net_feat')},
+             nonzero_rows={k: int(sum(int((g[k].abs().amax(1) > 0).sum()) for g in gf)) for k in ('cell_feat', 'net_feat')})
+        # kernel time of the last hop alone: one profiled (device events) pass per route; the bytes the fused kernel needs
+        fc, fn_ = b.graph.ndata['cell_feat'].shape[1], b.graph.ndata['net_feat'].shape[1]
+        need = 4.0 * (n_cell * (128 + 2 * fc) + n_net * (128 + 2 * fn_))
+        for layers in (False, True):
+            run(layers)
+            lib.prof_reset()
+            lib.prof_enable(True)
+            try:
+                sens._last_hop(b.graph._sweep)
+                torch.cuda.synchronize()
+            finally:
+                lib.prof_enable(False)
+            prof = lib.prof_report()
+            t = sum(r['ms'] for r in prof)
+            emit(row='last_hop_layers_kernels' if layers else 'last_hop_fused_kernels', launches=sum(r['launches'] for r in prof),
+                 ms=t, kernels={r['name']: round(r['ms'], 4) for r in prof},
+                 **({} if layers else dict(bytes_needed=need, tb_per_s=need / (t * 1e-3) / 1e12 if t else None)))
+
+
+if __name__ == '__main__':
+    main()
