@@ -1,7 +1,8 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
 include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, in include/mmft_incr.h,
 called through `incr`, in include/mmft_crit.h, called through `crit`, in include/mmft_head.h, called through `head`, in
-include/mmft_crit_sums.h, called through `csum`, and in include/mmft_sens.h, called through `sens`).
+include/mmft_crit_sums.h, called through `csum`, in include/mmft_sens.h, called through `sens`, and in include/mmft_sens_image.h, called through
+`simg`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -24,6 +25,7 @@ CRIT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit.
 HEAD_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_head.h')       # the fusion head's fused MLP
 CSUM_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit_sums.h')  # negative-slack sums and TNS shares
 SENS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens.h')       # gradient with respect to the features
+SIMG_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens_image.h')  # gradient with respect to the image
 
 _lib = None
 
@@ -97,6 +99,11 @@ def csum_decls():
 def sens_decls():
     """The same for include/mmft_sens.h (called through `sens`)."""
     return _parse_header(SENS_HEADER_PATH)
+
+
+def simg_decls():
+    """The same for include/mmft_sens_image.h (called through `simg`)."""
+    return _parse_header(SIMG_HEADER_PATH)
 
 
 def header_symbols():
@@ -296,6 +303,26 @@ def sens(name, *args):
         fn = getattr(load(), name)
         fn.restype, fn.argtypes = decls[name]
         _SENS[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_SIMG = {}
+
+
+def simg(name, *args):
+    """Call an entry point of include/mmft_sens_image.h, bound from that header on first use, exactly like `sens`: an `int` entry
+    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
+    fn = _SIMG.get(name)
+    if fn is None:
+        decls = simg_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {SIMG_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _SIMG[name] = fn
     rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
     if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")

@@ -14,6 +14,12 @@ mmft_mlp2_feat_dx_bf16 (include/mmft_sens.h, csrc/mlp_feat_dx.hip): two launches
 sweep._batched_param_grads, in bf16 mode on a schedule where the sweep's feat_fused holds.  In fp32 mode, or where the rows
 are not a range, the same result comes from the generic layers (linear_fwd recomputes H, linear_dgrad(mask=H), linear_dgrad).
 
+image=True adds the third input, the layout image.  The U-Net then runs through unet16.unet_forward_eval_taped (the same 19
+launches and bits as the eval forward) and its output, the feature map, is a leaf of the autograd tape: the masked projection
+runs on the tape, MaskedFcFn.backward hands back d J / d feature map (`feat_grad`, the map-level answer), and
+unet16.unet_eval_input_grad carries it through the eval-mode U-Net to the image - data gradient only, 32 launches, the two
+kernels of include/mmft_sens_image.h among them.  bf16 mode on the fused eval path only; everything else is refused on the host.
+
 Eager only: the forward + backward pair is not captured and replayed.  Nothing of the model is written - no parameter, no
 buffer, no .grad (torch.autograd.grad, not .backward()), no requires_grad flag, no module mode.  A model whose parameters carry
 gradient sinks (mmft.gradsink: a trainer with the fused optimizer owns it) is refused: the reverse sweep would deliver its
@@ -54,6 +60,37 @@ def check_no_sinks(pmodel):
                            'the fused optimizer owns it, and the reverse sweep would write into its flat gradient buffer')
 
 
+def check_image_model(pmodel, cnn):
+    """image=True at construction: there must be a CNN whose output reaches the predictions (ValueError otherwise)."""
+    if cnn is None:
+        raise ValueError('Sensitivity(image=True): there is no CNN, so nothing depends on the layout image')
+    if getattr(pmodel, 'fcn', None) is None:
+        raise ValueError('Sensitivity(image=True): the model has no masked projection (pmodel.fcn is None): the predictions '
+                         'do not depend on the layout image')
+
+
+def check_image_route(cnn, images, frozen_stats):
+    """image=True at run(): the U-Net call must be unet16's fused eval forward - the condition of
+    Predictor._unet_is_fused_eval under the statistics the call would freeze.  ValueError before anything is launched."""
+    from . import cnn as C, unet16
+    why = None
+    if lib.get_math_mode() != 'bf16':
+        why = 'the math mode is fp32 (the eval-mode input gradient exists on the bf16-storage kernels only)'
+    elif not hasattr(cnn, 'inc') or not hasattr(cnn, 'outc'):
+        why = f'{type(cnn).__name__} is not the U-Net'
+    else:
+        bns = [m for m in cnn.modules() if isinstance(m, torch.nn.BatchNorm2d)]
+        with frozen_statistics(cnn, frozen_stats):
+            frozen = bool(bns) and all(C.bn_uses_running_stats(bn) for bn in bns)
+        if not frozen:
+            why = 'a BatchNorm layer would normalise with batch statistics (frozen_stats=False on a net in train mode, or ' \
+                  'no tracked running statistics): they couple the pixels of an image'
+        elif not unet16.supported(cnn, images, frozen_stats=True):
+            why = f'the image batch {tuple(images.shape)} is outside the fused eval path (unet16.supported)'
+    if why is not None:
+        raise ValueError(f'Sensitivity.run(image=True): {why}')
+
+
 def check_objective(objective):
     if objective not in OBJECTIVES:
         raise ValueError(f'Sensitivity.run: unknown objective {objective!r} (expected one of {OBJECTIVES})')
@@ -81,14 +118,20 @@ class Sensitivity:
                           selection, made here
     frozen_stats          the U-Net normalises with its running statistics for the call (evaluate.frozen_statistics)
     overlap               the netlist sweep on a side stream under the U-Net (as Predictor)
+    image                 run() also returns grads[i]['image'], fp32 [3, H, W]: the gradient of J with respect to design i's
+                          layout image (bf16 mode, the U-Net on its fused eval path)
 
     Attributes: endpoints (host int64 [T], as Predictor's), required (fp32 [T] on the device: the rows' required times),
     row_design (host int64 [T]: the design of each row of pred), feat_map (the U-Net's output of the last run(), [B, P]),
+    feat_grad (image=True: d J / d feat_map of the last run(), [B, P]),
     last_hop ('fused' / 'layers': which route the last run() took through the feature MLPs).
     force_layers = True sends the last hop through the generic layers also where the fused kernel would run."""
 
-    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, overlap=True):
+    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, overlap=True, image=False):
         check_model(pmodel)
+        if image:
+            check_image_model(pmodel, cnn)
+        self.image = bool(image)
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.overlap = bool(frozen_stats), bool(overlap)
@@ -112,7 +155,7 @@ class Sensitivity:
         nd = b.graph.ndata
         # rows outside the (even / odd) levels are never written: zero for the life of the object
         self._dx = {k: torch.zeros_like(nd[k]) for k in ('cell_feat', 'net_feat')}
-        self.feat_map = self.last_hop = None
+        self.feat_map = self.last_hop = self.feat_grad = None
         self.force_layers = False
 
     @contextlib.contextmanager
@@ -135,7 +178,8 @@ class Sensitivity:
         update_design(self.batch, self._perm[i] if 0 <= i < self.batch.B else None, i, cell_feat, net_feat, image, rows=rows)
 
     def _forward(self):
-        """pred [T] with the sweep and the head on the autograd tape; everything in front of them under no_grad."""
+        """pred [T] with the sweep and the head on the autograd tape; everything in front of them under no_grad - but for
+        image=True: the feature map is then a leaf and the masked projection runs on the tape too."""
         from . import sweep as _sweep
         b, g, pm_ = self.batch, self.batch.graph, self.pmodel
         ends_d, paths_d, foff_d, _, _, lv_d = self._sel
@@ -150,15 +194,23 @@ class Sensitivity:
             else:
                 h_gnn = sweep()
         st = g._sweep
-        with torch.no_grad():
-            feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
+        self._tape = None
+        with torch.set_grad_enabled(self.image):
+            if self.image:
+                from . import unet16
+                with torch.no_grad():
+                    out, self._tape = unet16.unet_forward_eval_taped(self.cnn, b.images)
+                feat = out.reshape(b.B, -1).requires_grad_(True)
+            else:
+                feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
             pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
             if self.overlap:
                 # joined BEFORE the masked projection, as TrainStep.forward does
                 cur.wait_stream(self.side)
                 h_gnn.record_stream(cur)
             h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
-        self.feat_map = feat
+        self.feat_map = feat.detach() if self.image else feat
+        self._feat_leaf = feat if self.image else None
         with torch.enable_grad():
             pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
         return pred, st
@@ -192,7 +244,8 @@ class Sensitivity:
         gradient of J = sum_r w_r pred_r.  weights: float32 [T], host or device, one per row of pred.  Without weights,
         objective='tns': w_r = 1 where required_r - pred_r < 0 on this call's own predictions (NaN rows get 0) - the gradient
         of the magnitude of the total negative slack; objective='sum': w_r = 1.  cell_feat gradients live on the rows of even
-        levels, net_feat gradients on the rows of odd levels; every other row is exactly 0."""
+        levels, net_feat gradients on the rows of odd levels; every other row is exactly 0.  With image=True each
+        dict also holds image=[3, H, W], the gradient with respect to the design's layout image."""
         check_objective(objective)
         w = check_weights(weights, self.T)
         check_no_sinks(self.pmodel)
@@ -203,6 +256,8 @@ class Sensitivity:
         if not any(p.requires_grad for k in _MLP_KEYS for p in _mlp2_params(getattr(self.pmodel.gnn, k))):
             raise RuntimeError('Sensitivity.run: no parameter of fc_cell_self / fc_net_self / fc_cell_neigh requires a gradient - the '
                                'sweep then runs in its forward-only form, which keeps nothing for a reverse sweep')
+        if self.image:
+            check_image_route(self.cnn, self.batch.images, self.frozen_stats)
         cur = torch.cuda.current_stream(self.device)
         with self._modes_kept(), frozen_statistics(self.cnn, self.frozen_stats):
             pred, st = self._forward()
@@ -214,10 +269,21 @@ class Sensitivity:
             else:
                 w = torch.ones_like(out)
             inputs = [p for p in st.params if p.requires_grad]
-            torch.autograd.grad(pred, inputs, grad_outputs=w.reshape(pred.shape), allow_unused=True)
+            if self.image:
+                inputs = inputs + [self._feat_leaf]
+            got = torch.autograd.grad(pred, inputs, grad_outputs=w.reshape(pred.shape), allow_unused=True)
             if self.overlap:
                 cur.wait_stream(self.side)            # the reverse sweep ran on the stream of its forward
             self._last_hop(st)
+            dimg = None
+            if self.image:
+                from . import unet16
+                self.feat_grad = got[-1].reshape(self.batch.B, -1)
+                dimg = unet16.unet_eval_input_grad(self.cnn, self._tape, self.feat_grad)
+                self._tape = self._feat_leaf = None
         grads = [dict(cell_feat=self._dx['cell_feat'].index_select(0, p), net_feat=self._dx['net_feat'].index_select(0, p))
                  for p in self._perm]
+        if dimg is not None:
+            for i, gr in enumerate(grads):
+                gr['image'] = dimg[i]                 # NCHW, the layout of DesignBatch.images: a view
         return out, self.endpoints, grads

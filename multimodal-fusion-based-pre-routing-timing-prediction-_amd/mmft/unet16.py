@@ -322,10 +322,8 @@ def _run_forward_eval(net, xn, pool_mode, packs, T, out, geom):
              pool_mode, dev, st)
 
 
-def unet_forward_eval(net, x):
-    """UNet.forward in eval mode on the bf16-storage kernels; x: fp32 (N,3,H,W).  Forward only: no autograd node, no replay
-    bookkeeping - the launch sequence has no host decision that depends on data, so a caller may capture it
-    (torch.cuda.graph) after one eager call has built the weight-pack table."""
+def _forward_eval(net, x):
+    """unet_forward_eval and everything it ran on: (out, pool_mode, packs, xn, arena, T)."""
     N, _, H, W = x.shape
     if not all(bn.affine for _, bn in _layers(net)):
         raise NotImplementedError('unet16: BatchNorm2d without affine is not on the reference path')
@@ -335,10 +333,133 @@ def unet_forward_eval(net, x):
     if packs is None or packs.device != x.device:
         packs = net.__dict__['_u16_packs'] = _Packs(net, x.device)
     xn = ops.to_nhwc(x.detach())                        # fp32 [N][H][W][3]
-    _abuf, T = _arena(_eval_sizes(N, H, W), torch.bfloat16, x.device)
+    abuf, T = _arena(_eval_sizes(N, H, W), torch.bfloat16, x.device)
     out = torch.empty((N, 1, H // 2, W // 2), dtype=torch.float32, device=x.device)
     _run_forward_eval(net, xn, pool_mode, packs, T, out, (N, H, W))
-    return out
+    return out, pool_mode, packs, xn, abuf, T
+
+
+def unet_forward_eval(net, x):
+    """UNet.forward in eval mode on the bf16-storage kernels; x: fp32 (N,3,H,W).  Forward only: no autograd node, no replay
+    bookkeeping - the launch sequence has no host decision that depends on data, so a caller may capture it
+    (torch.cuda.graph) after one eager call has built the weight-pack table."""
+    return _forward_eval(net, x)[0]
+
+
+# ------------------------------------------------------------------------------------------------ eval mode: the input gradient
+# (level, channels per pixel) of every buffer of the eval arena
+_EVAL_SHAPE = {'a1': (0, 16), 'cat3': (0, 32), 'p1': (1, 16), 'a3': (1, 32), 'cat2': (1, 64), 'p2': (2, 32), 'a5': (2, 64),
+               'cat1': (2, 128), 'p3': (3, 64), 'a7': (3, 128), 'a8': (3, 128), 'a9': (2, 64), 'a10': (2, 64), 'a11': (1, 32),
+               'a12': (1, 32), 'a13': (0, 16), 'a14': (0, 16)}
+
+
+def _param_state(net):
+    """What tells that the parameters a tape was made with are still the ones in place: their addresses (_Packs.key), their
+    versions, and the epoch the fused optimizer bumps when it rewrites parameters through raw pointers."""
+    ps = _params(net)
+    return tuple(p.data_ptr() for p in ps), tuple(p._version for p in ps), gradsink.param_epoch()
+
+
+class EvalTape:
+    """What unet_forward_eval_taped leaves for unet_eval_input_grad: the arena of stored activations, the NHWC input, the
+    geometry, the pooling mode and the weight-pack object (its mode-1 "b" packs are the input-gradient fragments the
+    forward's pack launch already filled).  Nothing here is a copy: the tape keeps the forward's own buffers alive."""
+
+    def __init__(self, net, geom, pool_mode, packs, xn, abuf, T):
+        self.net, self.geom, self.pool_mode, self.packs, self.xn, self.arena, self.T = net, geom, pool_mode, packs, xn, abuf, T
+        self.pack_buf, self.state = packs.buf, _param_state(net)
+        self.scratch = None                # OutConv's weight-gradient slabs land here and are dropped
+
+    @property
+    def acts(self):
+        """{name: bf16 [N, h, w, channels]} - the stored activations by the names of _ACT / _eval_sizes (views of the arena).
+        A concatenation buffer holds the skip half in its first channels and the transposed convolution's in the rest."""
+        N, H, W = self.geom
+        lv, _ = _geometry(N, H, W)
+        return {name: self.T[name].view(N, lv[l][0], lv[l][1], C) for name, (l, C) in _EVAL_SHAPE.items()}
+
+
+def unet_forward_eval_taped(net, x):
+    """(out, tape): unet_forward_eval - the same 19 launches, the same bits, nothing of the model written - with what it ran
+    on kept alive in `tape` for unet_eval_input_grad."""
+    N, _, H, W = x.shape
+    out, pool_mode, packs, xn, abuf, T = _forward_eval(net, x)
+    return out, EvalTape(net, (N, H, W), pool_mode, packs, xn, abuf, T)
+
+
+@functools.lru_cache(maxsize=16)
+def _eval_bwd_sizes(N, H, W):
+    """Arena of the eval-mode input gradient: the activation gradients of _bwd_sizes (bf16) without g2, g4, g6 - at the
+    pooled layers the skip half of gcat and the pooled gradient are read in place, their sum is never stored."""
+    return [(name, n) for name, n in _bwd_sizes(N, H, W)[0] if name not in ('g2', 'g4', 'g6')]
+
+
+def _run_eval_input_grad(net, pool_mode, packs, T, g, G, so, dx, geom):
+    """Every launch of the eval-mode input gradient, in order: OutConv's backward (its weight-gradient slabs dropped), per
+    layer 14 .. 1 the frozen affine + ReLU backward (mmft_u16_frozen_bwd; at layers 6, 4, 2 it also routes the pooled
+    tensor's gradient and adds the skip connection's), for layers 14 .. 2 the input gradient on the forward's mode-1 packs,
+    the three transposed convolutions' input gradients, and the image gradient of layer 1 - 32 launches, no host
+    synchronisation, no data-dependent host decision, nothing written but G, so and dx."""
+    N, H, W = geom
+    dev, st = lib.stream_args(g)
+    lv, _ = _geometry(N, H, W)
+    convs = _layers(net)
+    oc = net.outc.conv[0]
+    lib.call('mmft_u16_outconv_bwd', T['a14'], oc.weight.detach(), oc.bias.detach() if oc.bias is not None else None, g, G['g14'],
+             None, None, 0, N, H, W, pool_mode, so, so.numel() * 4, dev, st)
+    grad_of = {'cat1': 'gcat1', 'cat2': 'gcat2', 'cat3': 'gcat3', 'p1': 'gp1', 'p2': 'gp2', 'p3': 'gp3'}
+    pooled_grad = {2: 'gp1', 4: 'gp2', 6: 'gp3'}
+
+    def layer_backward(i):
+        Ci, Co, l, inp = _CONV[i]
+        h, w = lv[l]
+        cv, bn = convs[i - 1]
+        abuf_name, lda, pooled = _ACT[i]
+        if pooled:                                     # the skip half of the concatenation and the pooled copy meet here
+            gin, ldg, gp = G['g' + abuf_name], lda, G[pooled_grad[i]]
+        else:
+            gin, ldg, gp = G['g%d' % i], Co, None
+        lib.simg('mmft_u16_frozen_bwd', T[abuf_name], lda, gin, ldg, gp, bn.weight.detach(), bn.running_var, float(bn.eps),
+                 G['dz%d' % i], N, h, w, Co, pool_mode, dev, st)
+        if inp == 'x':
+            lib.simg('mmft_u16_conv3x3_dgrad_image', G['dz1'], cv.weight.detach(), dx, N, h, w, dev, st)
+            return
+        tgt = grad_of.get(inp) or 'g%d' % (i - 1)
+        lib.call('mmft_u16_conv3x3', G['dz%d' % i], 0, packs.ptr('b%d' % (i - 1)), G[tgt], None, N, h, w, Co, Ci, dev, st)
+
+    def up_backward(k, g_target):
+        uCi, uin, cat, coff, ul = _UP[k]
+        uh, uw = lv[ul]
+        lib.call('mmft_u16_convt_dgrad', G['g' + cat].data_ptr() + coff * 2, uCi, packs.ptr('tb%d' % k), G[g_target], N, uh, uw, uCi,
+                 dev, st)
+
+    layer_backward(14); layer_backward(13); up_backward(2, 'g12')
+    layer_backward(12); layer_backward(11); up_backward(1, 'g10')
+    layer_backward(10); layer_backward(9); up_backward(0, 'g8')
+    for i in range(8, 0, -1):
+        layer_backward(i)
+
+
+def unet_eval_input_grad(net, tape, gout):
+    """d (sum of out * gout) / d x of the eval-mode forward that made `tape`: fp32 [N, 3, H, W].  gout: fp32 [N, 1, H/2, W/2]
+    (any shape with as many elements).  An explicit entry, not autograd: UNet.forward in eval mode with gradients enabled
+    still refuses.  Refused: another net or shape than the tape's, and parameters that moved or were written since."""
+    if not isinstance(tape, EvalTape) or tape.net is not net:
+        raise ValueError('unet_eval_input_grad: the tape was made by another network')
+    N, H, W = tape.geom
+    if not torch.is_tensor(gout) or gout.dtype != torch.float32 or gout.device != tape.arena.device or gout.numel() != N * (H // 2) * (W // 2):
+        raise ValueError(f'unet_eval_input_grad: gout must be a float32 tensor of {N} x 1 x {H // 2} x {W // 2} elements on the tape\'s device')
+    if _param_state(net) != tape.state or tape.packs.key != tape.state[0] or tape.packs.buf is not tape.pack_buf:
+        raise ValueError('unet_eval_input_grad: the network\'s parameters moved or were written after the taped forward '
+                         '(the packed input-gradient weights no longer belong to the stored activations)')
+    g = gout.detach()
+    g = g if g.is_contiguous() else g.contiguous()
+    if tape.scratch is None:
+        tape.scratch = torch.empty(lib.query('mmft_u16_outconv_bwd_workspace_bytes', N, H, W) // 4, dtype=torch.float32, device=g.device)
+    _gbuf, G = _arena(_eval_bwd_sizes(N, H, W), torch.bfloat16, g.device)
+    dx = torch.empty((N, 3, H, W), dtype=torch.float32, device=g.device)
+    _run_eval_input_grad(net, tape.pool_mode, tape.packs, tape.T, g, G, tape.scratch, dx, tape.geom)
+    return dx
 
 
 def _make_sinks(net):

@@ -1,6 +1,6 @@
 """What "which change would help" costs, in bf16 math mode at config B shapes (8 designs x 65 536 nodes, 64 levels).
 
-    python tools/bench_sensitivity.py [--designs 8] [--paths 1350] [--reps 10] [--rounds 5] [--out FILE]
+    python tools/bench_sensitivity.py [--designs 8] [--paths 1350] [--reps 10] [--rounds 5] [--out FILE] [--image]
 
 Every row is the HOST clock around the call + synchronise - what a sizing loop waits for:
   run            Sensitivity.run(objective='sum'): forward in the training form, reverse sweep, the last hop on
@@ -15,7 +15,14 @@ Every row is the HOST clock around the call + synchronise - what a sizing loop w
 The rows alternate inside each of `rounds` rounds; per row the median and min .. max over the rounds of the mean over `reps`
 calls.  Then one profiled pass of run and of run_layers gives the kernel time of the last hop alone (the launch profiler's
 device events) and the bytes its kernels need, and the two routes' gradients are compared.  One JSON line per row.  Needs a
-GPU."""
+GPU.
+
+--image measures the gradient with respect to the layout image instead:
+  run / run_image    Sensitivity.run(objective='sum') of an image=False and of an image=True object on the same modules,
+                     alternating as above; run is the parent code path (nothing of it changes with image=False)
+  eval_input_grad    unet16.unet_eval_input_grad alone on a tape of the batch's images (host clock), then one profiled pass:
+                     every kernel of the 32 launches with its device time, and for the two kernels of
+                     include/mmft_sens_image.h the bytes they must move and the rate achieved"""
 import argparse
 import json
 import os
@@ -51,6 +58,51 @@ def rel_err(a, b):
     return float((a.double() - b.double()).abs().max() / (b.double().abs().max() + 1e-30))
 
 
+def image_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    from mmft import unet16
+    from mmft.evaluate import frozen_statistics
+    with lib.math_mode('bf16'):
+        plain = Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+        withimg = Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids, image=True)
+        rows = {'run': lambda: plain.run(objective='sum'), 'run_image': lambda: withimg.run(objective='sum')}
+        for fn in rows.values():
+            host_ms(fn, 3)
+        N, _, H, W = withimg.batch.images.shape
+        emit(row='shapes', designs=a.designs, nodes=int(plain.batch.N), endpoints=int(plain.T), images=[int(N), 3, int(H), int(W)])
+        ms = {nm: [] for nm in rows}
+        for _ in range(a.rounds):
+            for nm, fn in rows.items():
+                ms[nm].append(host_ms(fn, a.reps))
+        for nm in rows:
+            emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=statistics.median(ms[nm]), ms_min=min(ms[nm]), ms_max=max(ms[nm]))
+        emit(row='run_image_over_run', ratio=statistics.median(ms['run_image']) / statistics.median(ms['run']))
+        (_, _, g0), (_, _, g1) = rows['run'](), rows['run_image']()
+        emit(row='outputs', same_feature_gradients=all(torch.equal(x[k], y[k]) for x, y in zip(g0, g1) for k in ('cell_feat', 'net_feat')),
+             image_grad_max=[float(g['image'].abs().max()) for g in g1], feat_grad_max=float(withimg.feat_grad.abs().max()))
+        with frozen_statistics(cnn), torch.no_grad():
+            _, tape = unet16.unet_forward_eval_taped(cnn, withimg.batch.images)
+            gout = withimg.feat_grad.clone()
+            grad = lambda: unet16.unet_eval_input_grad(cnn, tape, gout)
+            host_ms(grad, 3)
+            t = [host_ms(grad, a.reps) for _ in range(a.rounds)]
+            emit(row='eval_input_grad', reps=a.reps, rounds=a.rounds, ms_median=statistics.median(t), ms_min=min(t), ms_max=max(t))
+            lib.prof_reset()
+            lib.prof_enable(True)
+            try:
+                grad()
+                torch.cuda.synchronize()
+            finally:
+                lib.prof_enable(False)
+        prof = lib.prof_report()
+        emit(row='eval_input_grad_kernels', launches=sum(r['launches'] for r in prof), ms=sum(r['ms'] for r in prof),
+             kernels={r['name']: [r['launches'], round(r['ms'], 4)] for r in prof})
+        for r in prof:
+            if r['name'].startswith(('u16_frozen_bwd', 'u16_conv3x3_dgrad_image')):
+                emit(row='new_kernel', name=r['name'], launches=r['launches'], ms=r['ms'], bytes_needed=r['bytes'],
+                     tb_per_s=r['bytes'] / (r['ms'] * 1e-3) / 1e12 if r['ms'] else None,
+                     gflop_per_s=r['flops'] / (r['ms'] * 1e-3) / 1e9 if r['ms'] else None)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -58,6 +110,7 @@ def main():
     ap.add_argument('--reps', type=int, default=10)
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--out', default=None)
+    ap.add_argument('--image', action='store_true', help='the gradient with respect to the layout image (see the module docstring)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
     dev = torch.device('cuda:0')
@@ -75,6 +128,8 @@ def main():
     rng = np.random.default_rng(6)
     ids = [np.sort(rng.permutation(d.num_paths)[:a.paths]) if a.paths else np.arange(d.num_paths) for d in designs]
     pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=9294)
+    if a.image:
+        return image_rows(a, emit, designs, ids, pmodel, cnn, dev)
     mid = (designs[0].L // 2) & ~1                                  # the middle CELL level
     cell = np.asarray(designs[0].levels[mid][:1], dtype=np.int64)
     tables = [torch.from_numpy(designs[0].cell_feat[cell] + np.float32(0.25 * (k + 1))).to(dev) for k in (0, 1)]
