@@ -224,6 +224,18 @@ def masked_fc_prefix(feat_map, w, masks):
     return _fc_cached('GP', (w, feat_map), _gp)
 
 
+def fc_weight_t(w):
+    """fcn.weight [Dout, P] transposed to [P, Dout]: the per-step cached copy the masked projection itself uses."""
+    wc = w if w.is_contiguous() else w.contiguous()
+    Dout, P = wc.shape
+
+    def _wT():
+        t = torch.empty((P, Dout), dtype=torch.float32, device=wc.device)
+        lib.call('mmft_transpose', wc, t, Dout, P, *lib.stream_args(wc))
+        return t
+    return _fc_cached('wT', (w,), _wT)
+
+
 class HeadLevelCtx:
     """mmft_head_level_fwd with everything that is the same for all level calls of a step resolved ONCE (the prefix table,
     raw pointers, sizes): a level call then costs one output allocation and one C call.  `ok` is False when the

@@ -1,8 +1,8 @@
 """ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
 include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, in include/mmft_incr.h,
 called through `incr`, in include/mmft_crit.h, called through `crit`, in include/mmft_head.h, called through `head`, in
-include/mmft_crit_sums.h, called through `csum`, in include/mmft_sens.h, called through `sens`, and in include/mmft_sens_image.h, called through
-`simg`).
+include/mmft_crit_sums.h, called through `csum`, in include/mmft_sens.h, called through `sens`, in include/mmft_sens_image.h, called through
+`simg`, and in include/mmft_sens_pins.h, called through `pmove`).
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -26,6 +26,7 @@ HEAD_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_head.
 CSUM_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit_sums.h')  # negative-slack sums and TNS shares
 SENS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens.h')       # gradient with respect to the features
 SIMG_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens_image.h')  # gradient with respect to the image
+PMOVE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens_pins.h')  # change per one-cell move of a pin
 
 _lib = None
 
@@ -104,6 +105,11 @@ def sens_decls():
 def simg_decls():
     """The same for include/mmft_sens_image.h (called through `simg`)."""
     return _parse_header(SIMG_HEADER_PATH)
+
+
+def pmove_decls():
+    """The same for include/mmft_sens_pins.h (called through `pmove`)."""
+    return _parse_header(PMOVE_HEADER_PATH)
 
 
 def header_symbols():
@@ -325,6 +331,26 @@ def simg(name, *args):
         _SIMG[name] = fn
     rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
     if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
+        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
+    return int(rc)
+
+
+_PMOVE = {}
+
+
+def pmove(name, *args):
+    """Call an `int mmft_*(...)` entry point of include/mmft_sens_pins.h, bound from that header on first use; raises like `call`
+    and returns the code (0), as `place` does."""
+    fn = _PMOVE.get(name)
+    if fn is None:
+        decls = pmove_decls()
+        if name not in decls:
+            raise RuntimeError(f'{name} is not declared in {PMOVE_HEADER_PATH}')
+        fn = getattr(load(), name)
+        fn.restype, fn.argtypes = decls[name]
+        _PMOVE[name] = fn
+    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+    if rc != 0:
         raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
     return int(rc)
 

@@ -533,6 +533,67 @@ def mlp2_feat_dx_bf16(g, x, rows, w1, b1, w2, dx=None):
     return dx
 
 
+PIN_MOVE_MAX_LEN = 1024          # nodes of a path row that mmft_pin_move_rows stages (include/mmft_sens_pins.h)
+
+
+def pin_move_rows(nodes, lens, loc_x, loc_y, map_x, map_y, paths, f_off, feat, wT, g, row_move=None):
+    """row_move [T, maxlen, 4] of include/mmft_sens_pins.h: per batch row and first-occurrence position the change of g[t] . h_cnn[t]
+    when that pin moves one map cell (x + 1, x - 1, y + 1, y - 1), exactly 0 elsewhere (mmft_pin_move_rows).
+
+    nodes int32 [num_paths, maxlen], lens int32 [num_paths], loc_x / loc_y int32 [N]: the tables of placement.PlacedPaths;
+    paths int32 [T], f_off int32 [T] or None; feat fp32 [B * P] (any shape with that many elements), wT fp32 [P, Dout],
+    g fp32 [T, Dout] with unit inner stride and a row pitch that is a multiple of 4 (a column slice of a wider gradient is read in
+    place).  Every element of row_move is written."""
+    for t, nm in ((nodes, 'nodes'), (lens, 'lens'), (loc_x, 'loc_x'), (loc_y, 'loc_y'), (paths, 'paths')):
+        _chk(t, nm, torch.int32)
+        if not t.is_contiguous() or t.device != nodes.device:
+            raise ValueError(f'pin_move_rows: {nm} must be contiguous, on the device of nodes')
+    if nodes.dim() != 2 or lens.dim() != 1 or lens.numel() != nodes.shape[0] or loc_x.dim() != 1 or loc_x.shape != loc_y.shape or paths.dim() != 1:
+        raise ValueError('pin_move_rows: nodes [num_paths, maxlen], lens [num_paths], loc_x / loc_y [N], paths [T] expected')
+    T, maxlen, P = paths.numel(), nodes.shape[1], int(map_x) * int(map_y)
+    if not 1 <= maxlen <= PIN_MOVE_MAX_LEN:
+        raise ValueError(f'pin_move_rows: rows of 1 .. {PIN_MOVE_MAX_LEN} nodes, got {maxlen}')
+    _idx(f_off, 'f_off', T)
+    _chk(feat, 'feat'); _rows2d(wT, 'wT'); _rows2d(g, 'g')
+    if not feat.is_contiguous() or feat.numel() % P or not feat.numel() or not wT.is_contiguous() or wT.shape[0] != P:
+        raise ValueError(f'pin_move_rows: feat must be contiguous with B * {P} elements, wT contiguous [{P}, Dout]')
+    Dout = wT.shape[1]
+    if g.shape != (T, Dout) or (T > 1 and g.stride(0) % 4) or g.storage_offset() % 4:
+        raise ValueError(f'pin_move_rows: g must be [{T}, {Dout}] with a row pitch and an offset that are multiples of 4')
+    if any(t.device != nodes.device for t in (feat, wT, g) + ((f_off,) if f_off is not None else ())):
+        raise ValueError('pin_move_rows: all operands on one device')
+    if row_move is None:
+        row_move = torch.empty((T, maxlen, 4), dtype=torch.float32, device=nodes.device)
+    _chk(row_move, 'row_move')
+    if tuple(row_move.shape) != (T, maxlen, 4) or not row_move.is_contiguous() or row_move.device != nodes.device:
+        raise ValueError(f'pin_move_rows: row_move must be a contiguous [{T}, {maxlen}, 4] tensor on the device of nodes')
+    ldg = g.stride(0) if T > 1 else Dout                     # (one row: its pitch is never used)
+    lib.pmove('mmft_pin_move_rows', nodes, lens, maxlen, loc_x, loc_y, int(map_x), int(map_y), paths, f_off, T, feat, wT, Dout,
+              g, ldg, row_move, *lib.stream_args(row_move))
+    return row_move
+
+
+def pin_move_sum(row_move, inc_ptr, inc_slot, pin_move=None):
+    """pin_move [N, 4]: row_move [T, maxlen, 4] summed per pin over the incidence CSR of placement.pin_incidence (inc_ptr int32
+    [N + 1], inc_slot int32 [nnz]: the slots t * maxlen + j at which the pin occurs first in a row, ascending), in CSR order
+    (mmft_pin_move_sum).  Every element of pin_move is written."""
+    _chk(row_move, 'row_move')
+    if row_move.dim() != 3 or row_move.shape[2] != 4 or not row_move.is_contiguous():
+        raise ValueError('pin_move_sum: row_move must be a contiguous [T, maxlen, 4] tensor')
+    _idx(inc_ptr, 'inc_ptr'); _idx(inc_slot, 'inc_slot')
+    N = inc_ptr.numel() - 1
+    if N < 0 or inc_ptr.device != row_move.device or inc_slot.device != row_move.device:
+        raise ValueError('pin_move_sum: inc_ptr [N + 1] and inc_slot [nnz] on the device of row_move')
+    if pin_move is None:
+        pin_move = torch.empty((N, 4), dtype=torch.float32, device=row_move.device)
+    _chk(pin_move, 'pin_move')
+    if tuple(pin_move.shape) != (N, 4) or not pin_move.is_contiguous() or pin_move.device != row_move.device:
+        raise ValueError(f'pin_move_sum: pin_move must be a contiguous [{N}, 4] tensor on the device of row_move')
+    lib.pmove('mmft_pin_move_sum', row_move, row_move.shape[0] * row_move.shape[1], inc_ptr, inc_slot, inc_slot.numel(), N, pin_move,
+              *lib.stream_args(row_move))
+    return pin_move
+
+
 def _edge_drivers(drv, indices):
     if drv is None:
         return None

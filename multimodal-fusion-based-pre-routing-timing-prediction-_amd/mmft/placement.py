@@ -222,3 +222,124 @@ def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None):
     lib.place('mmft_placed_fc_fwd', placed.nodes, placed.lens, placed.maxlen, placed.loc_x, placed.loc_y, placed.map_x,
               placed.map_y, paths, f_off, T, GP, b, out, Dout, Dout, masks.run_block, stats, *lib.stream_args(GP))
     return out
+
+
+# ------------------------------------------------------------------------------------------------ one-cell moves of a pin
+def pin_incidence_host(path_nodes, path_lens, paths, n_nodes):
+    """(inc_ptr int64 [n_nodes + 1], inc_slot int64 [nnz]): per pin the slots t * maxlen + j of the batch rows t (path paths[t])
+    and live positions j < min(len, maxlen) at which the pin occurs FIRST in its row, ascending - the incidence CSR of
+    include/mmft_sens_pins.h.  The selection and the paths' nodes are static: built once, whatever the pins do."""
+    nodes, lens = np.asarray(path_nodes, dtype=np.int64), np.asarray(path_lens, dtype=np.int64)
+    paths = np.asarray(paths, dtype=np.int64).reshape(-1)
+    maxlen = nodes.shape[1]
+    R = nodes[paths].reshape(paths.shape[0], maxlen)
+    live = np.arange(maxlen)[None, :] < np.minimum(lens[paths], maxlen)[:, None]
+    if (live & ((R < 0) | (R >= n_nodes))).any():
+        raise ValueError(f'pin_incidence: a path node id outside [0, {n_nodes}) inside its row\'s length')
+    # a later occurrence follows its equal in a stable sort of the row (entries beyond the length sit behind the live ones)
+    order = np.argsort(R, axis=1, kind='stable')
+    Rs = np.take_along_axis(R, order, 1)
+    again = np.zeros(R.shape, dtype=bool)
+    again[:, 1:] = Rs[:, 1:] == Rs[:, :-1]
+    dup = np.zeros(R.shape, dtype=bool)
+    np.put_along_axis(dup, order, again, 1)
+    t, j = np.nonzero(live & ~dup)                                      # ascending (t, j)
+    pins, slots = R[t, j], t * maxlen + j
+    by_pin = np.argsort(pins, kind='stable')
+    ptr = np.zeros(n_nodes + 1, dtype=np.int64)
+    np.cumsum(np.bincount(pins, minlength=n_nodes), out=ptr[1:])
+    return ptr, slots[by_pin].astype(np.int64)
+
+
+def pin_incidence(placed, paths):
+    """The incidence CSR of a selection `paths` (rows of placed.nodes; host array or tensor) over `placed`'s pins as int32
+    device tensors (inc_ptr [N + 1], inc_slot [nnz]) for ops.pin_move_sum.  One device -> host copy of the node table."""
+    p = paths.detach().cpu().numpy() if torch.is_tensor(paths) else np.asarray(paths)
+    if p.ndim != 1 or p.dtype.kind not in 'iu' or (p.size and (p.min() < 0 or p.max() >= placed.nodes.shape[0])):
+        raise ValueError(f'pin_incidence: paths must be a 1-D integer array of rows of the {placed.nodes.shape[0]} placed paths')
+    if p.size * placed.maxlen >= 2 ** 29:
+        raise ValueError(f'pin_incidence: rows * maxlen must stay below 2^29, got {p.size} * {placed.maxlen}')
+    ptr, slot = pin_incidence_host(placed.nodes.cpu().numpy(), placed.lens.cpu().numpy(), p, int(placed.loc_x.numel()))
+    i32 = lambda a: torch.from_numpy(a.astype(np.int32)).to(placed.device)
+    return i32(ptr), i32(slot)
+
+
+def _axis_range(u, v, lim):
+    """[lo, hi] of the mask rule along one axis of `lim` cells for pins at u and v (arrays); empty where lo > hi."""
+    return np.maximum(np.minimum(u, v), 0), np.minimum(np.maximum(u, v), lim - 1)
+
+
+def _holds(boxes, v, pf):
+    """[len(pf)] bool: is the cell (v, pf[i]) - moving axis, fixed axis - inside one of `boxes` [n, 4] = (lo, hi, f1, f2)?"""
+    on_line = (boxes[:, 0] <= v) & (v <= boxes[:, 1])
+    b = boxes[on_line]
+    return ((b[None, :, 2] <= pf[:, None]) & (pf[:, None] <= b[None, :, 3])).any(1)
+
+
+def pin_move_host(path_nodes, path_lens, pin_x, pin_y, map_x, map_y, paths, f_off, feat, w, g):
+    """(row_move fp64 [T, maxlen, 4], pin_move fp64 [N, 4]) of include/mmft_sens_pins.h on the host: per batch row t (path
+    paths[t], feature-map offset f_off[t], or 0 without f_off) and first-occurrence position the change of g[t] . h_cnn[t] when
+    that pin alone moves one map cell - directions x + 1, x - 1, y + 1, y - 1 - and the sums per pin.  feat [B * P], w = fcn.weight
+    [Dout, P], g [T, Dout].
+
+    EXACT IN THE MASK: the cells are the set differences of the masks under the rule of include/mmft_place.h, the pin displaced
+    at all of its occurrences in the row before clamping.  LINEAR IN THE HEAD: the change of h_cnn is contracted with g - a
+    first-order estimate of the change of J, not a prediction of the moved design (that is update() followed by predict()).
+
+    Written in the segment form of the kernel, as rasterize_host restates the masks: the boxes next to an occurrence of the pin
+    each gain and lose at most two lines; a cell of such a line counts once, at the first box that proposes it, unless
+    another box of the row holds it."""
+    nodes, lens = np.asarray(path_nodes, dtype=np.int64), np.asarray(path_lens, dtype=np.int64)
+    px, py = np.asarray(pin_x).astype(np.int64), np.asarray(pin_y).astype(np.int64)
+    paths = np.asarray(paths, dtype=np.int64).reshape(-1)
+    map_x, map_y = int(map_x), int(map_y)
+    P, T, maxlen = map_x * map_y, paths.shape[0], nodes.shape[1]
+    feat = np.asarray(feat, dtype=np.float64).reshape(-1)
+    w, g = np.asarray(w, dtype=np.float64), np.asarray(g, dtype=np.float64)
+    if w.ndim != 2 or w.shape[1] != P or g.shape != (T, w.shape[0]) or feat.size % P:
+        raise ValueError(f'pin_move_host: feat [B * {P}], w [Dout, {P}] and g [{T}, Dout] expected')
+    off = np.zeros(T, dtype=np.int64) if f_off is None else np.asarray(f_off, dtype=np.int64).reshape(-1)
+    row_move = np.zeros((T, maxlen, 4), dtype=np.float64)
+    pin_move = np.zeros((px.shape[0], 4), dtype=np.float64)
+    for t in range(T):
+        q = int(paths[t])
+        ids = nodes[q, :max(min(int(lens[q]), maxlen), 0)]
+        if ids.shape[0] == 0:
+            continue
+        score = feat[off[t]:off[t] + P] * (g[t] @ w)                   # s_t(c) for every cell of the map
+        x, y = px[ids], py[ids]
+        seen = set()
+        for j, n in enumerate(ids.tolist()):
+            if n in seen:
+                continue
+            seen.add(n)
+            at = ids == n
+            touched = np.flatnonzero(at[:-1] | at[1:])                 # the boxes next to an occurrence, ascending
+            for d in range(4):
+                cm, cf, lim_m, lim_f = (x, y, map_x, map_y) if d < 2 else (y, x, map_y, map_x)
+                mv = cm + np.where(at, -1 if d & 1 else 1, 0)          # displaced before the rule clamps (int64: no overflow)
+                now = np.stack(_axis_range(cm[:-1], cm[1:], lim_m) + _axis_range(cf[:-1], cf[1:], lim_f), 1)
+                then = now.copy()
+                then[:, 0], then[:, 1] = _axis_range(mv[:-1], mv[1:], lim_m)
+                live = now[:, 2] <= now[:, 3]                          # an empty fixed-axis range: no box before or after
+                now_boxes, then_boxes = now[live & (now[:, 0] <= now[:, 1])], then[live & (then[:, 0] <= then[:, 1])]
+                total = 0.0
+                for k in touched.tolist():
+                    a1, a2, f1, f2 = now[k].tolist()
+                    b1, b2 = then[k, :2].tolist()
+                    if f1 > f2:
+                        continue
+                    pf = np.arange(f1, f2 + 1)
+                    gained = [v for v in dict.fromkeys((b1, b2)) if b1 <= b2 and not (a1 <= a2 and a1 <= v <= a2)]
+                    lost = [v for v in dict.fromkeys((a1, a2)) if a1 <= a2 and not (b1 <= b2 and b1 <= v <= b2)]
+                    earlier = touched[touched < k]
+                    for sign, lines, held_by, proposed_by in ((1.0, gained, now_boxes, then), (-1.0, lost, then_boxes, now)):
+                        first = proposed_by[earlier]
+                        first = first[(first[:, 0] <= first[:, 1]) & (first[:, 2] <= first[:, 3])]
+                        for v in lines:
+                            counts = ~(_holds(held_by, v, pf) | _holds(first, v, pf))
+                            cells = v * map_y + pf[counts] if d < 2 else pf[counts] * map_y + v
+                            total += sign * float(score[cells].sum())
+                row_move[t, j, d] = total
+            pin_move[n] += row_move[t, j]
+    return row_move, pin_move

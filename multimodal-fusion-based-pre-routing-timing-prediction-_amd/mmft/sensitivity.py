@@ -20,6 +20,16 @@ runs on the tape, MaskedFcFn.backward hands back d J / d feature map (`feat_grad
 unet16.unet_eval_input_grad carries it through the eval-mode U-Net to the image - data gradient only, 32 launches, the two
 kernels of include/mmft_sens_image.h among them.  bf16 mode on the fused eval path only; everything else is refused on the host.
 
+pins=True adds the placement, as a DISCRETE sensitivity (a pin is not differentiable through box masks: it moves a path's mask
+by whole cells): grads[i]['pin_move'][n][d] is the first-order change of J when pin n of design i alone moves one map cell in
+direction d (0: x + 1, 1: x - 1, 2: y + 1, 3: y - 1) - EXACT IN THE MASK (the set difference of the path masks under the rule of
+include/mmft_place.h: clamping, boxes that vanish or appear at the map's edge, cells another box of the path keeps alive) and
+LINEAR IN THE HEAD (the change of h_cnn is contracted with the gradient at h_cnn).  It is not a prediction of the moved design:
+the exact answer remains update() followed by predict().  h_cnn then comes from placement.placed_fc (bitwise masked_fc) as a
+leaf of the tape - with image=True it is on the tape already -, the one autograd.grad call also returns the gradient at it (a
+column slice of the head's dx, which the head kernel writes either way), and mmft_pin_move_rows / mmft_pin_move_sum
+(include/mmft_sens_pins.h, csrc/pin_move.hip) turn it into row_move and pin_move: two launches, no workspace, no atomics.
+
 Eager only: the forward + backward pair is not captured and replayed.  Nothing of the model is written - no parameter, no
 buffer, no .grad (torch.autograd.grad, not .backward()), no requires_grad flag, no module mode.  A model whose parameters carry
 gradient sinks (mmft.gradsink: a trainer with the fused optimizer owns it) is refused: the reverse sweep would deliver its
@@ -67,6 +77,35 @@ def check_image_model(pmodel, cnn):
     if getattr(pmodel, 'fcn', None) is None:
         raise ValueError('Sensitivity(image=True): the model has no masked projection (pmodel.fcn is None): the predictions '
                          'do not depend on the layout image')
+
+
+def check_pins_model(pmodel, cnn, designs):
+    """pins=True at construction: there must be a masked projection for the pins to move, and every design must carry
+    placement data (ValueError otherwise).  Host only."""
+    from . import placement as PL
+    if cnn is None:
+        raise ValueError('Sensitivity(pins=True): there is no CNN, so no prediction depends on the path masks')
+    if getattr(pmodel, 'fcn', None) is None:
+        raise ValueError('Sensitivity(pins=True): the model has no masked projection (pmodel.fcn is None): the predictions '
+                         'do not depend on the pins\' coordinates')
+    for i, d in enumerate(designs):
+        if not PL.has_placement(d):
+            raise ValueError(f'Sensitivity(pins=True): design {i} carries no placement data '
+                             f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
+
+
+def check_pin_update(pins, image, pin_x, pin_y):
+    """update(pin_x=, pin_y=): True when the call moves pins, False when it names none; ValueError where it cannot."""
+    if pin_x is None and pin_y is None:
+        return False
+    if not pins:
+        raise ValueError('update: pin_x / pin_y need a Sensitivity built with pins=True')
+    if image:
+        raise ValueError('update: pin_x / pin_y with image=True: that route\'s masks are the rasterised ones, and moving masks '
+                         'have no backward')
+    if pin_x is None or pin_y is None:
+        raise ValueError('update: pin_x and pin_y go together')
+    return True
 
 
 def check_image_route(cnn, images, frozen_stats):
@@ -120,18 +159,29 @@ class Sensitivity:
     overlap               the netlist sweep on a side stream under the U-Net (as Predictor)
     image                 run() also returns grads[i]['image'], fp32 [3, H, W]: the gradient of J with respect to design i's
                           layout image (bf16 mode, the U-Net on its fused eval path)
+    pins                  run() also returns grads[i]['pin_move'], fp32 [N_i, 4] in design i's own node order: the first-order
+                          change of J when that pin alone moves one map cell (x + 1, x - 1, y + 1, y - 1) - exact in the mask,
+                          linear in the head (module docstring); 0 for pins on no selected path.  Every design carries placement
+                          data (placement.attach_placement); update(i, pin_x=..., pin_y=...) then moves design i's pins in
+                          place (not with image=True) and the next run() predicts and differentiates on the moved pins.
+                          pred and the other gradients are bitwise those of pins=False
 
     Attributes: endpoints (host int64 [T], as Predictor's), required (fp32 [T] on the device: the rows' required times),
     row_design (host int64 [T]: the design of each row of pred), feat_map (the U-Net's output of the last run(), [B, P]),
     feat_grad (image=True: d J / d feat_map of the last run(), [B, P]),
+    proj_grad (pins=True: d J / d h_cnn of the last run(), [T, Dout] - a view), row_move (pins=True: fp32 [T, maxlen, 4], the
+    per-row terms of pin_move, include/mmft_sens_pins.h), placed (pins=True: the placement.PlacedPaths tables),
     last_hop ('fused' / 'layers': which route the last run() took through the feature MLPs).
     force_layers = True sends the last hop through the generic layers also where the fused kernel would run."""
 
-    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, overlap=True, image=False):
+    def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, overlap=True, image=False,
+                 pins=False):
         check_model(pmodel)
         if image:
             check_image_model(pmodel, cnn)
-        self.image = bool(image)
+        if pins:
+            check_pins_model(pmodel, cnn, designs)
+        self.image, self.pins = bool(image), bool(pins)
         self.pmodel, self.cnn = pmodel, cnn
         self.device = torch.device(device)
         self.frozen_stats, self.overlap = bool(frozen_stats), bool(overlap)
@@ -157,6 +207,32 @@ class Sensitivity:
         self._dx = {k: torch.zeros_like(nd[k]) for k in ('cell_feat', 'net_feat')}
         self.feat_map = self.last_hop = self.feat_grad = None
         self.force_layers = False
+        self.placed = self.proj_grad = self.row_move = self._incidence = self._pin_move = None
+        if self.pins:
+            self._make_pins(designs)
+
+    def _make_pins(self, designs):
+        """The placement tables, the incidence CSR of the selection and the static outputs of pins=True; refuses a map the
+        kernels do not take and designs whose stored masks are not the masks of their pins (pred would then differ from
+        pins=False) - what Predictor(placement=True) refuses."""
+        from . import placement as PL
+        b = self.batch
+        if not b.masks.run_block or b.P > PL.MAX_CELLS:
+            raise ValueError(f'Sensitivity(pins=True) needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; it has {b.P}')
+        placed = PL.PlacedPaths(designs, b.node_off, self.device)
+        if placed.maxlen > ops.PIN_MOVE_MAX_LEN:
+            raise ValueError(f'Sensitivity(pins=True): paths of up to {ops.PIN_MOVE_MAX_LEN} nodes, the designs\' rows hold {placed.maxlen}')
+        ip, cols = (t.cpu().numpy().astype(np.int64) for t in placed.csr())
+        for i in range(b.B):
+            q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
+            if not (np.array_equal(ip[q0:q1 + 1], b.masks.host_indptr[q0:q1 + 1]) and
+                    np.array_equal(cols[ip[q0]:ip[q1]], b.masks.host_cols[ip[q0]:ip[q1]])):
+                raise ValueError(f'Sensitivity(pins=True): the stored masks of design {i} are not the masks of its pins '
+                                 '(placement.attach_placement rebuilds them)')
+        self.placed = placed
+        self._incidence = PL.pin_incidence(placed, self._sel[1])
+        self.row_move = torch.zeros((self.T, placed.maxlen, 4), dtype=torch.float32, device=self.device)
+        self._pin_move = torch.zeros((int(b.node_off[-1]), 4), dtype=torch.float32, device=self.device)
 
     @contextlib.contextmanager
     def _modes_kept(self):
@@ -173,9 +249,17 @@ class Sensitivity:
             for m, was in modes:
                 m.training = was
 
-    def update(self, i, cell_feat=None, net_feat=None, image=None, rows=None):
-        """New features / a new layout image of design i, as Predictor.update (infer.update_design): the next run() sees them."""
+    def update(self, i, cell_feat=None, net_feat=None, image=None, rows=None, pin_x=None, pin_y=None):
+        """New features / a new layout image of design i, as Predictor.update (infer.update_design): the next run() sees them.
+        pin_x / pin_y (pins=True without image=True; both or neither): new map-cell coordinates of the design's pins, int32 /
+        int64 [N_i], any value (boxes are clamped to the map) - PlacedPaths.set_pins.  Everything is validated before anything
+        is written."""
+        xy = None
+        if check_pin_update(self.pins, self.image, pin_x, pin_y):
+            xy = self.placed.check_pins(i, pin_x, pin_y)
         update_design(self.batch, self._perm[i] if 0 <= i < self.batch.B else None, i, cell_feat, net_feat, image, rows=rows)
+        if xy is not None:
+            self.placed.set_pins(i, *xy)
 
     def _forward(self):
         """pred [T] with the sweep and the head on the autograd tape; everything in front of them under no_grad - but for
@@ -208,7 +292,15 @@ class Sensitivity:
                 # joined BEFORE the masked projection, as TrainStep.forward does
                 cur.wait_stream(self.side)
                 h_gnn.record_stream(cur)
-            h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
+            if self.pins and not self.image:
+                # the masks of the pins as they are now: bitwise masked_fc on masks rasterised from them (placement.placed_fc)
+                from .placement import placed_fc
+                h_cnn = placed_fc(self.placed, paths_d, foff_d if b.B > 1 else None, feat, pm_.fcn.weight, pm_.fcn.bias, b.masks)
+            else:
+                h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
+        if self.pins and not self.image:
+            h_cnn.requires_grad_(True)                    # a leaf of the tape: autograd.grad hands back the gradient at it
+        self._proj = h_cnn if self.pins else None
         self.feat_map = feat.detach() if self.image else feat
         self._feat_leaf = feat if self.image else None
         with torch.enable_grad():
@@ -238,6 +330,20 @@ class Sensitivity:
             dH = ops.linear_dgrad(Gv, w2, gidx=idx, mask=H)
             ops.linear_dgrad(dH, w1, dx=Dv, dxidx=idx)
 
+    def _pin_moves(self, g):
+        """proj_grad -> row_move -> pin_move (include/mmft_sens_pins.h): two launches on the current stream."""
+        from . import fusion
+        b, placed = self.batch, self.placed
+        _, paths_d, foff_d = self._sel[:3]
+        self._proj = None
+        if g is None:
+            raise RuntimeError('Sensitivity(pins=True): the predictions do not depend on the masked projection')
+        self.proj_grad = g = ops.strided_rows(g)      # a column slice of the head's dx: read in place
+        wT = fusion.fc_weight_t(self.pmodel.fcn.weight)          # the cached transpose of this run's masked projection
+        ops.pin_move_rows(placed.nodes, placed.lens, placed.loc_x, placed.loc_y, placed.map_x, placed.map_y, paths_d,
+                          foff_d if b.B > 1 else None, self.feat_map.reshape(-1), wT, g, row_move=self.row_move)
+        ops.pin_move_sum(self.row_move, *self._incidence, pin_move=self._pin_move)
+
     def run(self, weights=None, objective='tns'):
         """(pred, endpoints, grads).  pred [T] on the device and endpoints (host int64 [T]) are what Predictor.predict() returns;
         grads[i] = dict(cell_feat=[N_i, Fc], net_feat=[N_i, Fn]): fp32 device tensors in design i's own node order, the
@@ -245,7 +351,8 @@ class Sensitivity:
         objective='tns': w_r = 1 where required_r - pred_r < 0 on this call's own predictions (NaN rows get 0) - the gradient
         of the magnitude of the total negative slack; objective='sum': w_r = 1.  cell_feat gradients live on the rows of even
         levels, net_feat gradients on the rows of odd levels; every other row is exactly 0.  With image=True each
-        dict also holds image=[3, H, W], the gradient with respect to the design's layout image."""
+        dict also holds image=[3, H, W], the gradient with respect to the design's layout image; with pins=True pin_move=[N_i, 4],
+        the change of J per one-cell move of each pin (class docstring)."""
         check_objective(objective)
         w = check_weights(weights, self.T)
         check_no_sinks(self.pmodel)
@@ -269,12 +376,16 @@ class Sensitivity:
             else:
                 w = torch.ones_like(out)
             inputs = [p for p in st.params if p.requires_grad]
+            if self.pins:
+                inputs = inputs + [self._proj]
             if self.image:
                 inputs = inputs + [self._feat_leaf]
             got = torch.autograd.grad(pred, inputs, grad_outputs=w.reshape(pred.shape), allow_unused=True)
             if self.overlap:
                 cur.wait_stream(self.side)            # the reverse sweep ran on the stream of its forward
             self._last_hop(st)
+            if self.pins:
+                self._pin_moves(got[-2] if self.image else got[-1])
             dimg = None
             if self.image:
                 from . import unet16
@@ -286,4 +397,8 @@ class Sensitivity:
         if dimg is not None:
             for i, gr in enumerate(grads):
                 gr['image'] = dimg[i]                 # NCHW, the layout of DesignBatch.images: a view
+        if self.pins:
+            off = self.batch.node_off                 # PlacedPaths keeps the caller's numbering: a slice, no permutation
+            for i, gr in enumerate(grads):
+                gr['pin_move'] = self._pin_move[int(off[i]):int(off[i + 1])].clone()
         return out, self.endpoints, grads

@@ -1,6 +1,6 @@
 """What "which change would help" costs, in bf16 math mode at config B shapes (8 designs x 65 536 nodes, 64 levels).
 
-    python tools/bench_sensitivity.py [--designs 8] [--paths 1350] [--reps 10] [--rounds 5] [--out FILE] [--image]
+    python tools/bench_sensitivity.py [--designs 8] [--paths 1350] [--reps 10] [--rounds 5] [--out FILE] [--image | --pins]
 
 Every row is the HOST clock around the call + synchronise - what a sizing loop waits for:
   run            Sensitivity.run(objective='sum'): forward in the training form, reverse sweep, the last hop on
@@ -22,7 +22,18 @@ GPU.
                      alternating as above; run is the parent code path (nothing of it changes with image=False)
   eval_input_grad    unet16.unet_eval_input_grad alone on a tape of the batch's images (host clock), then one profiled pass:
                      every kernel of the 32 launches with its device time, and for the two kernels of
-                     include/mmft_sens_image.h the bytes they must move and the rate achieved"""
+                     include/mmft_sens_image.h the bytes they must move and the rate achieved
+
+--pins measures the discrete sensitivity to one-cell moves of a pin (include/mmft_sens_pins.h), on the placement bench's data
+(tests/place_cases.placed(config_design('B', i)): paths of up to 12 nodes on a 128 x 128 map):
+  run / run_pins     Sensitivity.run(objective='sum') of a pins=False and of a pins=True object on the same modules,
+                     alternating as above; run is the parent code path
+  pin_move_kernels   one profiled pass of the two launches alone: device time, the bytes they must move, the rate
+  estimate_vs_truth  for --sample seeded (pin, direction) pairs among the pins with a non-zero estimate: pin_move against the
+                     change of J that Predictor(placement=True).update() + predict() gives under the same weights - sign
+                     agreement and the median relative error, estimate and truth both in bf16 mode and both in fp32 mode
+                     (the head is a ReLU MLP, and in bf16 mode it rounds its input rows: information, not a test)
+--pins --trace-only runs `--reps` calls of run_pins and nothing else, for a kernel trace taken in a run of its own."""
 import argparse
 import json
 import os
@@ -103,6 +114,90 @@ def image_rows(a, emit, designs, ids, pmodel, cnn, dev):
                      gflop_per_s=r['flops'] / (r['ms'] * 1e-3) / 1e9 if r['ms'] else None)
 
 
+def pins_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    with lib.math_mode('bf16'):
+        withpins = Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids, pins=True)
+        if a.trace_only:
+            for _ in range(a.reps):
+                withpins.run(objective='sum')
+            torch.cuda.synchronize()
+            return
+        plain = Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids)
+        rows = {'run': lambda: plain.run(objective='sum'), 'run_pins': lambda: withpins.run(objective='sum')}
+        for fn in rows.values():
+            host_ms(fn, 3)
+        placed = withpins.placed
+        lens = torch.minimum(placed.lens[withpins._sel[1].long()], torch.tensor(placed.maxlen, device=dev))
+        slots = int(withpins._incidence[1].numel())
+        emit(row='shapes', designs=a.designs, nodes=int(plain.batch.N), rows=int(plain.T), maxlen=int(placed.maxlen), map=int(placed.map_x),
+             live_positions=int(lens.sum()), first_occurrence_slots=slots, pins_on_a_row=int((withpins._incidence[0].diff() > 0).sum()))
+        ms = {nm: [] for nm in rows}
+        for _ in range(a.rounds):
+            for nm, fn in rows.items():
+                ms[nm].append(host_ms(fn, a.reps))
+        for nm in rows:
+            emit(row=nm, reps=a.reps, rounds=a.rounds, ms_median=statistics.median(ms[nm]), ms_min=min(ms[nm]), ms_max=max(ms[nm]))
+        emit(row='run_pins_over_run', ratio=statistics.median(ms['run_pins']) / statistics.median(ms['run']))
+        (p0, _, g0), (p1, _, g1) = rows['run'](), rows['run_pins']()
+        pm = torch.cat([g['pin_move'] for g in g1])
+        emit(row='outputs', same_predictions=bool(torch.equal(p0, p1)),
+             same_feature_gradients=all(torch.equal(x[k], y[k]) for x, y in zip(g0, g1) for k in ('cell_feat', 'net_feat')),
+             pin_move_nonzero=int((pm != 0).sum()), pin_move_abs_max=float(pm.abs().max()))
+        # the two launches alone; the bytes they must move: per row its ids, coordinates and g, per changed cell one wT row and one
+        # feat element (counted from row_move's non-zero terms as a lower bound: 1 cell each), row_move written, then read once
+        # with the CSR for pin_move
+        Dout = int(withpins.proj_grad.shape[1])
+        changed = int((withpins.row_move != 0).sum())
+        need_rows = 4.0 * (int(lens.sum()) * 3 + withpins.T * (Dout + 3) + changed * (Dout + 1) + withpins.row_move.numel())
+        need_sum = 4.0 * (slots * 5 + pm.numel() * 2)
+        g = withpins.proj_grad
+        lib.prof_reset()
+        lib.prof_enable(True)
+        try:
+            withpins._pin_moves(g)
+            torch.cuda.synchronize()
+        finally:
+            lib.prof_enable(False)
+        for r in lib.prof_report():
+            if r['name'].startswith('pin_move'):
+                need = need_rows if 'rows' in r['name'] else need_sum
+                emit(row='pin_move_kernels', name=r['name'], launches=r['launches'], ms=r['ms'], bytes_needed_at_least=need,
+                     gb_per_s=need / (r['ms'] * 1e-3) / 1e9 if r['ms'] else None)
+    # the estimate against truth: J = sum of the predictions (objective='sum') before and after the move, in both math modes -
+    # in bf16 mode the head rounds its input rows to bf16, so the truth of a small move is itself quantised
+    rng = np.random.default_rng(7)
+    cand = torch.nonzero(pm != 0).cpu().numpy()
+    sample = cand[rng.permutation(len(cand))[:a.sample]].tolist()
+    off = withpins.batch.node_off
+    del plain, withpins
+    for mode in ('bf16', 'f32'):
+        with lib.math_mode(mode):
+            pm_m = torch.cat([g['pin_move'] for g in Sensitivity(pmodel, cnn, designs, dev, path_ids_per_design=ids, pins=True).run(objective='sum')[2]])
+            pr = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, graphed=False)
+            with torch.no_grad():
+                base = pr.predict()[0].double().clone()
+            est, true = [], []
+            for n, d in sample:
+                i = int(np.searchsorted(off, n, side='right') - 1)
+                x, y = np.array(designs[i].pin_x, dtype=np.int64), np.array(designs[i].pin_y, dtype=np.int64)
+                k = n - int(off[i])
+                x[k] += (1, -1, 0, 0)[d]
+                y[k] += (0, 0, 1, -1)[d]
+                pr.update(i, pin_x=x, pin_y=y)
+                with torch.no_grad():
+                    true.append(float((pr.predict()[0].double() - base).sum()))
+                pr.update(i, pin_x=np.asarray(designs[i].pin_x, dtype=np.int64), pin_y=np.asarray(designs[i].pin_y, dtype=np.int64))
+                est.append(float(pm_m[n, d]))
+            del pr
+        est, true = np.array(est), np.array(true)
+        moved = true != 0
+        emit(row='estimate_vs_truth', math_mode=mode, sample=int(est.size), truth_nonzero=int(moved.sum()),
+             sign_agreement=float((np.sign(est[moved]) == np.sign(true[moved])).mean()) if moved.any() else None,
+             median_rel_err=float(np.median(np.abs(est[moved] - true[moved]) / np.abs(true[moved]))) if moved.any() else None,
+             median_abs_truth=float(np.median(np.abs(true[moved]))) if moved.any() else None,
+             median_abs_estimate=float(np.median(np.abs(est))), J=float(base.sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -111,6 +206,9 @@ def main():
     ap.add_argument('--rounds', type=int, default=5)
     ap.add_argument('--out', default=None)
     ap.add_argument('--image', action='store_true', help='the gradient with respect to the layout image (see the module docstring)')
+    ap.add_argument('--pins', action='store_true', help='the change per one-cell move of a pin (see the module docstring)')
+    ap.add_argument('--sample', type=int, default=64, help='--pins: (pin, direction) pairs of the estimate-against-truth row')
+    ap.add_argument('--trace-only', action='store_true', help='--pins: only `reps` calls of run_pins (for a kernel trace)')
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
     dev = torch.device('cuda:0')
@@ -125,11 +223,17 @@ def main():
                 f.write('\n'.join(lines) + '\n')
 
     designs = [config_design('B', i) for i in range(a.designs)]
+    if a.pins:
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        from place_cases import placed
+        designs = [placed(d, seed=100 + i) for i, d in enumerate(designs)]
     rng = np.random.default_rng(6)
     ids = [np.sort(rng.permutation(d.num_paths)[:a.paths]) if a.paths else np.arange(d.num_paths) for d in designs]
     pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=9294)
     if a.image:
         return image_rows(a, emit, designs, ids, pmodel, cnn, dev)
+    if a.pins:
+        return pins_rows(a, emit, designs, ids, pmodel, cnn, dev)
     mid = (designs[0].L // 2) & ~1                                  # the middle CELL level
     cell = np.asarray(designs[0].levels[mid][:1], dtype=np.int64)
     tables = [torch.from_numpy(designs[0].cell_feat[cell] + np.float32(0.25 * (k + 1))).to(dev) for k in (0, 1)]
