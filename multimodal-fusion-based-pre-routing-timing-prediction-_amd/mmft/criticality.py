@@ -22,6 +22,8 @@ from .placement import MAX_CELLS, rasterize_host
 from .report import reference_slack
 
 FIELDS = ('node_slack', 'node_row', 'node_viol', 'node_crit', 'cell_slack', 'cell_viol', 'counts')
+SUM_FIELDS = ('node_nsum', 'cell_nsum', 'design_nsum', 'saturated', 'node_share', 'cell_share')
+_KINDS = dict(f4=torch.float32, i4=torch.int32, i8=torch.int64)
 
 
 def workspace_bytes(N, B, P):
@@ -29,39 +31,54 @@ def workspace_bytes(N, B, P):
     return lib.crit('mmft_criticality_workspace_bytes', int(N), int(B), int(P))
 
 
-class CritBuffers:
-    """The static output buffers of one criticality launch, carved out of ONE buffer of 4-byte words so that `host()` is one
-    device->host copy: node_slack fp32, node_row, node_viol int32, node_crit fp32 [N]; counts int32 [B, 2]; with cells
-    cell_slack fp32 and cell_viol int32 [B, P]."""
+class _Buffers:
+    """The static output buffers of one launch, carved out of ONE buffer of 4-byte words so that `host()` is one device->host
+    copy.  A subclass states `fields`, the order in which `tensors()` and `host()` give them (and `count`, their number in
+    words), and `layout`, the order in which they lie in the buffer: (name, f4 | i4 | i8, shape) with the shape one of N, B,
+    B2 = [B, 2] and BP = [B, P].  The cell_ fields exist only with cells."""
 
     def __init__(self, N, B, P, device, cells=True):
         self.N, self.B, self.cells = int(N), int(B), bool(cells)
         self.P = int(P) if self.cells else 0
         if self.N < 1 or self.B < 1 or (self.cells and (self.P < 64 or self.P % 64 or self.P > MAX_CELLS)):
-            raise ValueError(f'CritBuffers: need N >= 1, B >= 1 and, with cells, a map of a multiple of 64 cells up to {MAX_CELLS} '
+            raise ValueError(f'{type(self).__name__}: need N >= 1, B >= 1 and, with cells, a map of a multiple of 64 cells up to {MAX_CELLS} '
                              f'(N {N}, B {B}, P {P})')
-        bp = self.B * self.P
-        self._layout = (('node_slack', 'f4', (self.N,)), ('node_row', 'i4', (self.N,)), ('node_viol', 'i4', (self.N,)),
-                        ('node_crit', 'f4', (self.N,)), ('counts', 'i4', (self.B, 2))) + \
-            ((('cell_slack', 'f4', (self.B, self.P)), ('cell_viol', 'i4', (self.B, self.P))) if self.cells else ())
-        self.raw = torch.empty(4 * self.N + 2 * self.B + 2 * bp, dtype=torch.int32, device=device)
+        self._layout = self.shapes(self.N, self.B, self.P, self.cells)
+        self.raw = torch.empty(sum(self._words(dt, s) for _, dt, s in self._layout), dtype=torch.int32, device=device)
+
+    @classmethod
+    def shapes(cls, N, B, P, cells):
+        """`layout` with the shapes as tuples, without the cell_ fields unless `cells`."""
+        shape = dict(N=(N,), B=(B,), B2=(B, 2), BP=(B, P))
+        return tuple((name, dt, shape[s]) for name, dt, s in cls.layout if cells or not name.startswith('cell_'))
+
+    @staticmethod
+    def _words(dt, shape):
+        return int(np.prod(shape)) * int(dt[1]) // 4
 
     def _carve(self, raw, view):
-        out, pos = dict.fromkeys(FIELDS), 0
+        out, pos = dict.fromkeys(self.fields), 0
         for name, dt, shape in self._layout:
-            n = int(np.prod(shape))
+            n = self._words(dt, shape)
             out[name] = view(raw[pos:pos + n], dt, shape)
             pos += n
-        return tuple(out[k] for k in FIELDS)
+        return tuple(out[k] for k in self.fields)
 
     def tensors(self):
-        """(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts): views of the one buffer; the two cell
-        tensors are None without cells."""
-        return self._carve(self.raw, lambda t, dt, shape: (t.view(torch.float32) if dt == 'f4' else t).view(shape))
+        """`fields` as views of the one buffer; the cell_ tensors are None without cells."""
+        return self._carve(self.raw, lambda t, dt, shape: t.view(_KINDS[dt]).view(shape))
 
     def host(self):
-        """One device->host copy -> the same seven as numpy arrays (`decode` takes them)."""
+        """One device->host copy -> `fields` as numpy arrays (`decode` / `decode_sums` take them)."""
         return self._carve(self.raw.cpu().numpy(), lambda a, dt, shape: a.view(dt).reshape(shape))
+
+
+class CritBuffers(_Buffers):
+    """The seven outputs of mmft_criticality: node_slack fp32, node_row, node_viol int32, node_crit fp32 [N]; counts int32
+    [B, 2]; with cells cell_slack fp32 and cell_viol int32 [B, P]."""
+    fields, count = FIELDS, 'seven'
+    layout = (('node_slack', 'f4', 'N'), ('node_row', 'i4', 'N'), ('node_viol', 'i4', 'N'), ('node_crit', 'f4', 'N'), ('counts', 'i4', 'B2'),
+              ('cell_slack', 'f4', 'BP'), ('cell_viol', 'i4', 'BP'))
 
 
 def _vec(fn, t, name, dtype, n=None):
@@ -74,6 +91,63 @@ def _vec(fn, t, name, dtype, n=None):
     if n is not None and t.numel() != n:
         raise ValueError(f'{fn}: {name} holds {t.numel()} entries, {n} expected')
     return t
+
+
+# The host-side validation that criticality() and criticality_sums() share, in the order in which both run it: _rows, _sizes,
+# _buffers.  criticality_sums() has a check of its own after each of the first two, and the order of the refusals is part of
+# the contract, so the three stay three.
+def _rows(fn, pred, required, paths, row_design):
+    """dtype, shape and contiguity of the per-row vectors -> T."""
+    _vec(fn, pred, 'pred', torch.float32)
+    T = pred.numel()
+    _vec(fn, required, 'required', torch.float32, T)
+    _vec(fn, paths, 'paths', torch.int32, T)
+    if row_design is not None:
+        _vec(fn, row_design, 'row_design', torch.int32, T)
+    return T
+
+
+def _sizes(fn, T, placed, B, cells):
+    """The limits of T, B and N -> (N, B, P, cells), P = 0 without cells."""
+    B, cells = int(B), bool(cells)
+    N = int(placed.loc_x.numel())
+    P = int(placed.P) if cells else 0
+    if T < 1 or T > 1 << 24 or B < 1 or N < 1:
+        raise ValueError(f'{fn}: need 1 <= T <= 2^24, B >= 1, N >= 1 (T {T}, B {B}, N {N})')
+    return N, B, P, cells
+
+
+def _buffers(fn, cls, need_bytes, rows, placed, N, B, P, cells, out, workspace):
+    """The map's size, `out` (allocated from `cls` when None) field by field, one device for everything, cuda only, the
+    workspace (from lib.workspace when None) and its size -> ({field: tensor, the cell_ fields None without cells}, workspace).
+    `rows` are the tensors _rows looked at."""
+    if cells and (P % 64 or P > MAX_CELLS or P < 64):
+        raise ValueError(f'{fn}: cells=True needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {P}')
+    pred = rows[0]
+    if out is None:
+        out = cls(N, B, P, pred.device, cells=cells).tensors()
+    if len(out) != len(cls.fields):
+        raise ValueError(f'{fn}: out must be the {cls.count} tensors of {cls.__name__}.tensors()')
+    shapes = {name: (_KINDS[dt], shape) for name, dt, shape in cls.shapes(N, B, P, cells)}
+    given = [(name, t) for name, t in zip(cls.fields, out) if name in shapes]
+    for name, t in given:
+        dt, shape = shapes[name]
+        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
+            raise ValueError(f'{fn}: {name} must be a contiguous {dt} tensor of shape {shape}')
+    dev = placed.nodes.device
+    every = [t for t in rows if t is not None] + [placed.lens, placed.loc_x, placed.loc_y] + [t for _, t in given]
+    if any(t.device != dev for t in every):
+        raise ValueError(f'{fn}: every tensor must live on the device of the placement tables ({dev})')
+    if dev.type != 'cuda':
+        raise RuntimeError(f'{fn}: the mmft hot path runs on the GPU only (got {dev} tensors); there is no CPU fallback')
+    need = need_bytes(N, B, P)
+    if workspace is None:
+        workspace = lib.workspace(dev, need)
+    elif not (torch.is_tensor(workspace) and workspace.device == dev and workspace.is_contiguous()):
+        raise ValueError(f'{fn}: workspace must be a contiguous tensor on {dev}')
+    if workspace.numel() * workspace.element_size() < need:
+        raise ValueError(f'{fn}: workspace of {need} bytes needed, got {workspace.numel() * workspace.element_size()}')
+    return {**dict.fromkeys(cls.fields), **dict(given)}, workspace
 
 
 def criticality(pred, required, placed, paths, row_design, B, cells=True, out=None, workspace=None):
@@ -91,53 +165,14 @@ def criticality(pred, required, placed, paths, row_design, B, cells=True, out=No
 
     Everything is validated on the host, dtypes, shapes and contiguity first, before anything is launched."""
     fn = 'criticality'
-    _vec(fn, pred, 'pred', torch.float32)
-    T = pred.numel()
-    _vec(fn, required, 'required', torch.float32, T)
-    _vec(fn, paths, 'paths', torch.int32, T)
-    if row_design is not None:
-        _vec(fn, row_design, 'row_design', torch.int32, T)
-    B, cells = int(B), bool(cells)
-    N = int(placed.loc_x.numel())
-    P = int(placed.P) if cells else 0
-    if T < 1 or T > 1 << 24 or B < 1 or N < 1:
-        raise ValueError(f'{fn}: need 1 <= T <= 2^24, B >= 1, N >= 1 (T {T}, B {B}, N {N})')
-    if cells and (P % 64 or P > MAX_CELLS or P < 64):
-        raise ValueError(f'{fn}: cells=True needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {P}')
-    if out is None:
-        out = CritBuffers(N, B, P, pred.device, cells=cells).tensors()
-    if len(out) != 7:
-        raise ValueError(f'{fn}: out must be the seven tensors of CritBuffers.tensors()')
-    shapes = dict(node_slack=(torch.float32, (N,)), node_row=(torch.int32, (N,)), node_viol=(torch.int32, (N,)),
-                  node_crit=(torch.float32, (N,)), cell_slack=(torch.float32, (B, P)), cell_viol=(torch.int32, (B, P)),
-                  counts=(torch.int32, (B, 2)))
-    for name, t in zip(FIELDS, out):
-        if name.startswith('cell_') and not cells:
-            continue
-        dt, shape = shapes[name]
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'{fn}: {name} must be a contiguous {dt} tensor of shape {shape}')
-    dev = placed.nodes.device
-    every = [pred, required, paths, placed.lens, placed.loc_x, placed.loc_y] + ([row_design] if row_design is not None else []) + \
-        [t for name, t in zip(FIELDS, out) if cells or not name.startswith('cell_')]
-    if any(t.device != dev for t in every):
-        raise ValueError(f'{fn}: every tensor must live on the device of the placement tables ({dev})')
-    if dev.type != 'cuda':
-        raise RuntimeError(f'{fn}: the mmft hot path runs on the GPU only (got {dev} tensors); there is no CPU fallback')
-    need = workspace_bytes(N, B, P)
-    if workspace is None:
-        workspace = lib.workspace(dev, need)
-    elif not (torch.is_tensor(workspace) and workspace.device == dev and workspace.is_contiguous()):
-        raise ValueError(f'{fn}: workspace must be a contiguous tensor on {dev}')
-    if workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f'{fn}: workspace of {need} bytes needed, got {workspace.numel() * workspace.element_size()}')
-    node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, counts = out
+    T = _rows(fn, pred, required, paths, row_design)
+    N, B, P, cells = _sizes(fn, T, placed, B, cells)
+    o, workspace = _buffers(fn, CritBuffers, workspace_bytes, (pred, required, paths, row_design), placed, N, B, P, cells, out, workspace)
     lib.crit('mmft_criticality', pred, required, placed.nodes, placed.lens, placed.maxlen,
              placed.loc_x if cells else None, placed.loc_y if cells else None, placed.map_x if cells else 0, placed.map_y if cells else 0,
-             paths, row_design, T, N, B, node_slack, node_row, node_viol, node_crit,
-             cell_slack if cells else None, cell_viol if cells else None, counts,
-             workspace, workspace.numel() * workspace.element_size(), *lib.stream_args(pred))
-    return node_slack, node_row, node_viol, node_crit, (cell_slack if cells else None), (cell_viol if cells else None), counts
+             paths, row_design, T, N, B, o['node_slack'], o['node_row'], o['node_viol'], o['node_crit'], o['cell_slack'], o['cell_viol'],
+             o['counts'], workspace, workspace.numel() * workspace.element_size(), *lib.stream_args(pred))
+    return tuple(o[k] for k in FIELDS)
 
 
 def reference_criticality(pred, required, path_nodes, path_lens, pin_x, pin_y, map_x, map_y, paths, row_design, N, B,
@@ -205,7 +240,6 @@ def decode(node_slack, node_row, node_viol, node_crit, cell_slack, cell_viol, co
 # include/mmft_crit_sums.h (mmft_criticality_sums, bound by lib.csum): the seven outputs above, bitwise, and next to them how
 # much negative slack flows through every pin and every cell.  A violating row contributes q = rint(min(-slack, 2^(32 - L)) *
 # 2^L) quanta of 2^-L (L = scale_log2), an integer, so the sums are integer sums: exact, the same in every order.
-SUM_FIELDS = ('node_nsum', 'cell_nsum', 'design_nsum', 'saturated', 'node_share', 'cell_share')
 MAX_ROW_PINS = 1 << 30                             # T * maxlen: every sum is then at most 2^62
 
 
@@ -214,43 +248,15 @@ def sums_workspace_bytes(N, B, P):
     return lib.csum('mmft_criticality_sums_workspace_bytes', int(N), int(B), int(P))
 
 
-class CritSumsBuffers:
-    """The static output buffers of one mmft_criticality_sums launch, carved out of ONE buffer of 4-byte words so that `host()`
-    is one device->host copy.  The int64 fields come first - node_nsum [N], design_nsum [B], with cells cell_nsum [B, P] - so
-    that they are 8-byte aligned; then the fields of CritBuffers, saturated int32 [B], node_share fp32 [N] and, with cells,
-    cell_share fp32 [B, P]."""
-
-    def __init__(self, N, B, P, device, cells=True):
-        self.N, self.B, self.cells = int(N), int(B), bool(cells)
-        self.P = int(P) if self.cells else 0
-        if self.N < 1 or self.B < 1 or (self.cells and (self.P < 64 or self.P % 64 or self.P > MAX_CELLS)):
-            raise ValueError(f'CritSumsBuffers: need N >= 1, B >= 1 and, with cells, a map of a multiple of 64 cells up to {MAX_CELLS} '
-                             f'(N {N}, B {B}, P {P})')
-        n, b, bp = (self.N,), (self.B,), (self.B, self.P)
-        c = self.cells
-        self._layout = (('node_nsum', 'i8', n), ('design_nsum', 'i8', b)) + ((('cell_nsum', 'i8', bp),) if c else ()) + \
-            (('node_slack', 'f4', n), ('node_row', 'i4', n), ('node_viol', 'i4', n), ('node_crit', 'f4', n), ('counts', 'i4', (self.B, 2)),
-             ('saturated', 'i4', b), ('node_share', 'f4', n)) + \
-            ((('cell_slack', 'f4', bp), ('cell_viol', 'i4', bp), ('cell_share', 'f4', bp)) if c else ())
-        self.raw = torch.empty(sum(int(np.prod(s)) * int(dt[1]) // 4 for _, dt, s in self._layout), dtype=torch.int32, device=device)
-
-    def _carve(self, raw, view):
-        out, pos = dict.fromkeys(FIELDS + SUM_FIELDS), 0
-        for name, dt, shape in self._layout:
-            n = int(np.prod(shape)) * int(dt[1]) // 4
-            out[name] = view(raw[pos:pos + n], dt, shape)
-            pos += n
-        return tuple(out[k] for k in FIELDS + SUM_FIELDS)
-
-    def tensors(self):
-        """The seven of CritBuffers.tensors(), then (node_nsum, cell_nsum, design_nsum, saturated, node_share, cell_share):
-        views of the one buffer; the four cell tensors are None without cells."""
-        kinds = dict(f4=torch.float32, i4=torch.int32, i8=torch.int64)
-        return self._carve(self.raw, lambda t, dt, shape: t.view(kinds[dt]).view(shape))
-
-    def host(self):
-        """One device->host copy -> the same thirteen as numpy arrays (`decode_sums` takes them)."""
-        return self._carve(self.raw.cpu().numpy(), lambda a, dt, shape: a.view(dt).reshape(shape))
+class CritSumsBuffers(_Buffers):
+    """The thirteen outputs of mmft_criticality_sums: the seven of CritBuffers, then node_nsum, cell_nsum, design_nsum,
+    saturated, node_share, cell_share.  In the buffer the int64 fields come first - node_nsum [N], design_nsum [B], with cells
+    cell_nsum [B, P] - so that they are 8-byte aligned; then the fields of CritBuffers, saturated int32 [B], node_share fp32
+    [N] and, with cells, cell_share fp32 [B, P]."""
+    fields, count = FIELDS + SUM_FIELDS, 'thirteen'
+    layout = (('node_nsum', 'i8', 'N'), ('design_nsum', 'i8', 'B'), ('cell_nsum', 'i8', 'BP'),
+              ('node_slack', 'f4', 'N'), ('node_row', 'i4', 'N'), ('node_viol', 'i4', 'N'), ('node_crit', 'f4', 'N'), ('counts', 'i4', 'B2'),
+              ('saturated', 'i4', 'B'), ('node_share', 'f4', 'N'), ('cell_slack', 'f4', 'BP'), ('cell_viol', 'i4', 'BP'), ('cell_share', 'f4', 'BP'))
 
 
 def criticality_sums(pred, required, placed, paths, row_design, B, scale_log2=20, cells=True, out=None, workspace=None):
@@ -263,61 +269,20 @@ def criticality_sums(pred, required, placed, paths, row_design, B, scale_log2=20
 
     Everything is validated on the host, dtypes, shapes and contiguity first, before anything is launched."""
     fn = 'criticality_sums'
-    _vec(fn, pred, 'pred', torch.float32)
-    T = pred.numel()
-    _vec(fn, required, 'required', torch.float32, T)
-    _vec(fn, paths, 'paths', torch.int32, T)
-    if row_design is not None:
-        _vec(fn, row_design, 'row_design', torch.int32, T)
+    T = _rows(fn, pred, required, paths, row_design)
     if isinstance(scale_log2, bool) or not isinstance(scale_log2, (int, np.integer)) or not 0 <= scale_log2 <= 30:
         raise ValueError(f'{fn}: scale_log2 must be an integer in [0, 30], got {scale_log2!r}')
-    B, cells, scale_log2 = int(B), bool(cells), int(scale_log2)
-    N = int(placed.loc_x.numel())
-    P = int(placed.P) if cells else 0
-    if T < 1 or T > 1 << 24 or B < 1 or N < 1:
-        raise ValueError(f'{fn}: need 1 <= T <= 2^24, B >= 1, N >= 1 (T {T}, B {B}, N {N})')
+    N, B, P, cells = _sizes(fn, T, placed, B, cells)
     if T * int(placed.maxlen) > MAX_ROW_PINS:
         raise ValueError(f'{fn}: T * maxlen must be at most 2^30 for the sums to fit int64 (T {T}, maxlen {placed.maxlen})')
-    if cells and (P % 64 or P > MAX_CELLS or P < 64):
-        raise ValueError(f'{fn}: cells=True needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {P}')
-    if out is None:
-        out = CritSumsBuffers(N, B, P, pred.device, cells=cells).tensors()
-    names = FIELDS + SUM_FIELDS
-    if len(out) != len(names):
-        raise ValueError(f'{fn}: out must be the thirteen tensors of CritSumsBuffers.tensors()')
-    shapes = dict(node_slack=(torch.float32, (N,)), node_row=(torch.int32, (N,)), node_viol=(torch.int32, (N,)),
-                  node_crit=(torch.float32, (N,)), cell_slack=(torch.float32, (B, P)), cell_viol=(torch.int32, (B, P)),
-                  counts=(torch.int32, (B, 2)), node_nsum=(torch.int64, (N,)), cell_nsum=(torch.int64, (B, P)),
-                  design_nsum=(torch.int64, (B,)), saturated=(torch.int32, (B,)), node_share=(torch.float32, (N,)),
-                  cell_share=(torch.float32, (B, P)))
-    given = [(name, t) for name, t in zip(names, out) if cells or not name.startswith('cell_')]
-    for name, t in given:
-        dt, shape = shapes[name]
-        if not torch.is_tensor(t) or t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous():
-            raise ValueError(f'{fn}: {name} must be a contiguous {dt} tensor of shape {shape}')
-    dev = placed.nodes.device
-    every = [pred, required, paths, placed.lens, placed.loc_x, placed.loc_y] + ([row_design] if row_design is not None else []) + \
-        [t for _, t in given]
-    if any(t.device != dev for t in every):
-        raise ValueError(f'{fn}: every tensor must live on the device of the placement tables ({dev})')
-    if dev.type != 'cuda':
-        raise RuntimeError(f'{fn}: the mmft hot path runs on the GPU only (got {dev} tensors); there is no CPU fallback')
-    need = sums_workspace_bytes(N, B, P)
-    if workspace is None:
-        workspace = lib.workspace(dev, need)
-    elif not (torch.is_tensor(workspace) and workspace.device == dev and workspace.is_contiguous()):
-        raise ValueError(f'{fn}: workspace must be a contiguous tensor on {dev}')
-    if workspace.numel() * workspace.element_size() < need:
-        raise ValueError(f'{fn}: workspace of {need} bytes needed, got {workspace.numel() * workspace.element_size()}')
-    o = dict(zip(names, out))
-    if not cells:
-        o.update(cell_slack=None, cell_viol=None, cell_nsum=None, cell_share=None)
+    o, workspace = _buffers(fn, CritSumsBuffers, sums_workspace_bytes, (pred, required, paths, row_design), placed, N, B, P, cells, out,
+                            workspace)
     lib.csum('mmft_criticality_sums', pred, required, placed.nodes, placed.lens, placed.maxlen,
              placed.loc_x if cells else None, placed.loc_y if cells else None, placed.map_x if cells else 0, placed.map_y if cells else 0,
              paths, row_design, T, N, B, o['node_slack'], o['node_row'], o['node_viol'], o['node_crit'], o['cell_slack'], o['cell_viol'],
-             o['counts'], scale_log2, o['node_nsum'], o['cell_nsum'], o['design_nsum'], o['saturated'], o['node_share'], o['cell_share'],
+             o['counts'], int(scale_log2), o['node_nsum'], o['cell_nsum'], o['design_nsum'], o['saturated'], o['node_share'], o['cell_share'],
              workspace, workspace.numel() * workspace.element_size(), *lib.stream_args(pred))
-    return tuple(o[k] for k in names)
+    return tuple(o[k] for k in FIELDS + SUM_FIELDS)
 
 
 def reference_quanta(slack, scale_log2):

@@ -1,8 +1,8 @@
-"""ctypes binding of libmmft_hip.so (the C ABI declared in include/mmft.h; extensions beyond the reference's hot path in
-include/mmft_report.h, called through `ext`, in include/mmft_place.h, called through `place`, in include/mmft_incr.h,
-called through `incr`, in include/mmft_crit.h, called through `crit`, in include/mmft_head.h, called through `head`, in
-include/mmft_crit_sums.h, called through `csum`, in include/mmft_sens.h, called through `sens`, in include/mmft_sens_image.h, called through
-`simg`, and in include/mmft_sens_pins.h, called through `pmove`).
+"""ctypes binding of libmmft_hip.so.  include/mmft.h declares the C ABI of the hot path: `load` binds all of it and `call` /
+`query` reach it.  Everything beyond it lives in extension headers under include/, one per feature, and each of those is bound
+by one `Header` instance of this module (`ext`, `place`, ... - the list is below `Header`): calling the instance with an
+entry point's name binds that entry point from its own header on first use and refuses a name the header does not declare.
+The headers are the single source of truth for restypes and argtypes.
 
 There is NO fallback: if the shared library is missing or an entry point fails, a RuntimeError is
 raised.  PyTorch is used only for device memory, streams and torch.distributed.
@@ -18,15 +18,6 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 PKG_DIR = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get('MMFT_LIB') or os.path.join(PKG_DIR, 'lib', 'libmmft_hip.so')      # MMFT_LIB: another build of the same library (A/B runs)
 HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft.h')
-EXT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_report.h')      # extensions: not the reference's path
-PLACE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_place.h')     # masks that follow a placement
-INCR_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_incr.h')       # sweeps over the fan-out of an edit
-CRIT_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit.h')       # criticality per pin and map cell
-HEAD_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_head.h')       # the fusion head's fused MLP
-CSUM_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_crit_sums.h')  # negative-slack sums and TNS shares
-SENS_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens.h')       # gradient with respect to the features
-SIMG_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens_image.h')  # gradient with respect to the image
-PMOVE_HEADER_PATH = os.path.join(os.path.dirname(PKG_DIR), 'include', 'mmft_sens_pins.h')  # change per one-cell move of a pin
 
 _lib = None
 
@@ -67,51 +58,6 @@ def header_decls():
     return _parse_header(HEADER_PATH)
 
 
-def ext_decls():
-    """The same for include/mmft_report.h, the entry points beyond the reference's hot path (called through `ext`)."""
-    return _parse_header(EXT_HEADER_PATH)
-
-
-def place_decls():
-    """The same for include/mmft_place.h (called through `place`)."""
-    return _parse_header(PLACE_HEADER_PATH)
-
-
-def incr_decls():
-    """The same for include/mmft_incr.h (called through `incr`)."""
-    return _parse_header(INCR_HEADER_PATH)
-
-
-def crit_decls():
-    """The same for include/mmft_crit.h (called through `crit`)."""
-    return _parse_header(CRIT_HEADER_PATH)
-
-
-def head_decls():
-    """The same for include/mmft_head.h (called through `head`)."""
-    return _parse_header(HEAD_HEADER_PATH)
-
-
-def csum_decls():
-    """The same for include/mmft_crit_sums.h (called through `csum`)."""
-    return _parse_header(CSUM_HEADER_PATH)
-
-
-def sens_decls():
-    """The same for include/mmft_sens.h (called through `sens`)."""
-    return _parse_header(SENS_HEADER_PATH)
-
-
-def simg_decls():
-    """The same for include/mmft_sens_image.h (called through `simg`)."""
-    return _parse_header(SIMG_HEADER_PATH)
-
-
-def pmove_decls():
-    """The same for include/mmft_sens_pins.h (called through `pmove`)."""
-    return _parse_header(PMOVE_HEADER_PATH)
-
-
 def header_symbols():
     """Names of every function declared in include/mmft.h (used by the CPU-side symbol test)."""
     return sorted(header_decls())
@@ -130,16 +76,6 @@ def load():
             fn.restype = res
             fn.argtypes = args
     return _lib
-
-
-def _conv(a):
-    if a is None:
-        return None
-    if torch.is_tensor(a):
-        return a.data_ptr()
-    if isinstance(a, bool):
-        return int(a)
-    return a
 
 
 def stream_args(t):
@@ -171,188 +107,47 @@ def query(name, *args):
     return int(fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args]))
 
 
-_EXT = {}
+class Header:
+    """One extension header under include/ and the entry points bound from it.  `header(name, *args)` calls `name` like `call`
+    does - tensors go as their data pointers - after binding its restype and argtypes from the header on first use; a name
+    the header does not declare is refused before the library is even loaded.  An `int` entry point raises unless it returns
+    0; a `long long` query raises when its value is negative; either way the value comes back as an int."""
 
+    def __init__(self, filename):
+        self.path = os.path.join(os.path.dirname(PKG_DIR), 'include', filename)
+        self._fn = {}
 
-def ext(name, *args):
-    """Call an entry point of include/mmft_report.h; restype and argtypes are bound from that header on first use.  An `int`
-    entry point raises like `call`; a `long long` query returns its value and raises when that is negative."""
-    fn = _EXT.get(name)
-    if fn is None:
-        decls = ext_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {EXT_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _EXT[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if fn.restype is ctypes.c_int:
-        if rc != 0:
+    def decls(self):
+        """{name: (restype, [argtypes])} of every function the header declares."""
+        return _parse_header(self.path)
+
+    def __call__(self, name, *args):
+        fn = self._fn.get(name)
+        if fn is None:
+            decls = self.decls()
+            if name not in decls:
+                raise RuntimeError(f'{name} is not declared in {self.path}')
+            fn = getattr(load(), name)
+            fn.restype, fn.argtypes = decls[name]
+            self._fn[name] = fn
+        rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
+        if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
             raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-        return None
-    if rc < 0:
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
+        return int(rc)
 
 
-_PLACE = {}
-
-
-def place(name, *args):
-    """Call an `int mmft_*(...)` entry point of include/mmft_place.h, bound from that header on first use; raises like `call`
-    and returns the code (0), as `ext` returns a query's value."""
-    fn = _PLACE.get(name)
-    if fn is None:
-        decls = place_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {PLACE_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _PLACE[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_INCR = {}
-
-
-def incr(name, *args):
-    """Call an `int mmft_*(...)` entry point of include/mmft_incr.h, bound from that header on first use; raises like `call`
-    and returns the code (0), as `place` does."""
-    fn = _INCR.get(name)
-    if fn is None:
-        decls = incr_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {INCR_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _INCR[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_CRIT = {}
-
-
-def crit(name, *args):
-    """Call an entry point of include/mmft_crit.h, bound from that header on first use, exactly like `ext`: an `int` entry
-    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
-    fn = _CRIT.get(name)
-    if fn is None:
-        decls = crit_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {CRIT_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _CRIT[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_HEAD = {}
-
-
-def head(name, *args):
-    """Call an entry point of include/mmft_head.h, bound from that header on first use, exactly like `crit`: an `int` entry
-    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
-    fn = _HEAD.get(name)
-    if fn is None:
-        decls = head_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {HEAD_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _HEAD[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_CSUM = {}
-
-
-def csum(name, *args):
-    """Call an entry point of include/mmft_crit_sums.h, bound from that header on first use, exactly like `crit`: an `int` entry
-    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
-    fn = _CSUM.get(name)
-    if fn is None:
-        decls = csum_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {CSUM_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _CSUM[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_SENS = {}
-
-
-def sens(name, *args):
-    """Call an entry point of include/mmft_sens.h, bound from that header on first use, exactly like `crit`: an `int` entry
-    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
-    fn = _SENS.get(name)
-    if fn is None:
-        decls = sens_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {SENS_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _SENS[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_SIMG = {}
-
-
-def simg(name, *args):
-    """Call an entry point of include/mmft_sens_image.h, bound from that header on first use, exactly like `sens`: an `int` entry
-    point raises like `call` and returns the code (0), a `long long` query returns its value and raises when it is negative."""
-    fn = _SIMG.get(name)
-    if fn is None:
-        decls = simg_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {SIMG_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _SIMG[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc < 0 or (rc != 0 and fn.restype is ctypes.c_int):
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
-
-
-_PMOVE = {}
-
-
-def pmove(name, *args):
-    """Call an `int mmft_*(...)` entry point of include/mmft_sens_pins.h, bound from that header on first use; raises like `call`
-    and returns the code (0), as `place` does."""
-    fn = _PMOVE.get(name)
-    if fn is None:
-        decls = pmove_decls()
-        if name not in decls:
-            raise RuntimeError(f'{name} is not declared in {PMOVE_HEADER_PATH}')
-        fn = getattr(load(), name)
-        fn.restype, fn.argtypes = decls[name]
-        _PMOVE[name] = fn
-    rc = fn(*[a.data_ptr() if isinstance(a, _Tensor) else a for a in args])
-    if rc != 0:
-        raise RuntimeError(f"{name} failed ({rc}): {load().mmft_last_error().decode()}")
-    return int(rc)
+# The extension headers.  The attribute names are part of the contract: the tests' ledgers find call sites by them.
+ext = Header('mmft_report.h')           # timing report: WNS, TNS and the k worst endpoints
+place = Header('mmft_place.h')          # path masks that follow a placement
+incr = Header('mmft_incr.h')            # sweeps over the fan-out cone of an edit
+crit = Header('mmft_crit.h')            # criticality per pin and per map cell
+head = Header('mmft_head.h')            # the fusion head's fused MLP
+csum = Header('mmft_crit_sums.h')       # negative-slack sums and TNS shares
+sens = Header('mmft_sens.h')            # gradient with respect to the cell and net features
+simg = Header('mmft_sens_image.h')      # gradient with respect to the layout image
+pmove = Header('mmft_sens_pins.h')      # change per one-cell move of a pin
+ext_decls, place_decls, incr_decls, crit_decls, head_decls = ext.decls, place.decls, incr.decls, crit.decls, head.decls
+csum_decls, sens_decls, simg_decls, pmove_decls = csum.decls, sens.decls, simg.decls, pmove.decls
 
 
 _workspace = {}

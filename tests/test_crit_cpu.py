@@ -2,9 +2,7 @@
 to include/mmft_report.h), mmft.criticality's reference against a second, literal restatement of the header's words, a
 mutation check - each clause, broken in the literal form, must be noticed by the inputs test_crit_gpu.py feeds to the kernel -
 and the host-side validation of criticality() and of Predictor(criticality=...)."""
-import ast
 import ctypes
-import glob
 import math
 import os
 import re
@@ -15,14 +13,12 @@ import torch
 
 import crit_cases as C
 import place_cases as PC
+from abi_ledger import call_sites, code_only as _code_only, declared as _declared
 from mmft import criticality as K
 from mmft import lib
 from mmft import placement as PL
-from test_host_cpu import _code_only
-from test_report_cpu import _declared
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ['mmft_criticality', 'mmft_criticality_workspace_bytes']
 F = np.float32
 
@@ -81,29 +77,14 @@ def test_the_built_library_exports_both_and_refuses_bad_arguments_on_the_host():
 
 def test_every_crit_call_site_matches_the_header_and_the_kernel_test_names_the_entry_point():
     protos = _declared('mmft_crit.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, seen = 0, [], set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'crit' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name == 'mmft_version':                      # (a list built elsewhere; the refusal test above)
-                continue
-            checked += 1
-            seen.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('crit'):
+        if n is None or name == 'mmft_version':                        # (a list built elsewhere; the refusal test above)
+            continue
+        checked += 1
+        seen.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 4 and seen == set(NAMES) and not bad, bad
     src = open(os.path.join(HERE, 'test_crit_gpu.py')).read()
     assert 'pytestmark = pytest.mark.gpu' in src

@@ -3,10 +3,8 @@ test_crit_cpu.py applies to include/mmft_crit.h), the host-side refusals of the 
 reference_criticality_sums against a second, literal restatement of the header's words, a mutation check - each new clause,
 broken in the literal form, must be noticed by the inputs test_crit_sums_gpu.py feeds to the kernels - what those inputs must
 hold, and the host side: buffers, decoding, validation, the Predictor's option."""
-import ast
 import ctypes
 import functools
-import glob
 import math
 import os
 import re
@@ -18,16 +16,14 @@ import torch
 import crit_cases as C
 import crit_sums_cases as S
 import place_cases as PC
+from abi_ledger import call_sites, code_only as _code_only, declared as _declared, others
 from mmft import criticality as K
 from mmft import lib
 from test_crit_cpu import _placed_cpu
-from test_host_cpu import _code_only
-from test_report_cpu import _declared
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ['mmft_criticality_sums', 'mmft_criticality_sums_workspace_bytes']
-OTHER_HEADERS = ('mmft.h', 'mmft_report.h', 'mmft_place.h', 'mmft_incr.h', 'mmft_crit.h', 'mmft_head.h')
+OTHER_HEADERS = others('mmft_crit_sums.h')
 F = np.float32
 
 
@@ -99,29 +95,14 @@ def test_the_built_library_exports_both_and_refuses_bad_arguments_on_the_host():
 
 def test_every_csum_call_site_matches_the_header_and_the_kernel_test_names_the_entry_point():
     protos = _declared('mmft_crit_sums.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, seen = 0, [], set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'csum' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name in ('mmft_version', 'mmft_criticality'):  # (a list built elsewhere; the refusal test above)
-                continue
-            checked += 1
-            seen.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('csum'):
+        if n is None or name in ('mmft_version', 'mmft_criticality'):  # (a list built elsewhere; the refusal test above)
+            continue
+        checked += 1
+        seen.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 4 and seen == set(NAMES) and not bad, bad
     src = open(os.path.join(HERE, 'test_crit_sums_gpu.py')).read()
     assert 'pytestmark = pytest.mark.gpu' in src

@@ -1,22 +1,17 @@
 """The fused fusion-head MLP without a GPU: the ledger of include/mmft_head.h (the rules test_crit_cpu.py applies to
 include/mmft_crit.h), the host-side refusals of its two launching entry points - every one of them comes before the device is
 looked at - and the gate that decides which shapes take the fused path."""
-import ast
 import ctypes
-import glob
-import os
 
 import pytest
 import torch
 
+from abi_ledger import call_sites, declared as _declared, others
 from mmft import lib
-from test_report_cpu import _declared
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ['mmft_head_mlp_bwd', 'mmft_head_mlp_fwd', 'mmft_head_mlp_supported', 'mmft_head_mlp_workspace_bytes']
 NARGS = {'mmft_head_mlp_bwd': 21, 'mmft_head_mlp_fwd': 14, 'mmft_head_mlp_supported': 3, 'mmft_head_mlp_workspace_bytes': 1}
-OTHERS = ('mmft.h', 'mmft_report.h', 'mmft_place.h', 'mmft_incr.h', 'mmft_crit.h')
+OTHERS = others('mmft_head.h')
 
 
 def test_head_header_declares_exactly_the_new_names_and_overlaps_no_other_header():
@@ -39,29 +34,14 @@ def test_head_header_declares_exactly_the_new_names_and_overlaps_no_other_header
 
 def test_every_head_call_site_matches_the_header():
     protos = _declared('mmft_head.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, seen = 0, [], set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'head' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name == 'mmft_version':                      # (a list built elsewhere; the refusal test above)
-                continue
-            checked += 1
-            seen.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('head'):
+        if n is None or name == 'mmft_version':                        # (a list built elsewhere; the refusal test above)
+            continue
+        checked += 1
+        seen.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 6 and seen == set(NAMES) and not bad, bad
 
 

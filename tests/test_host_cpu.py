@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from abi_ledger import call_sites, declared, code_only as _code_only
 from mmft import lib
 from mmft.synth import synth_design
 from mmft.pingraph import PinGraph
@@ -367,40 +368,16 @@ def test_no_kernel_contains_a_packed_fma_with_low_half_select(tmp_path):
 def test_every_call_site_matches_the_header():
     """Static check: each `lib.call('mmft_x', ...)` / `lib.query(...)` in the package, the tools, the tests and bench.py passes
     exactly as many arguments as include/mmft.h declares for that entry point (ctypes would only notice on a GPU box)."""
-    import ast
-    import glob
-    import os
-    import re
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    hdr = open(os.path.join(root, 'include', 'mmft.h')).read()
-    protos = {}
-    for m in re.finditer(r'\b(?:int|long long|const char\*)\s+(mmft_\w+)\s*\(([^;]*?)\)\s*;', hdr, re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ('', 'void') else len(args.split(','))
-    files = glob.glob(os.path.join(root, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(root, 'tests', '*.py')) + glob.glob(os.path.join(root, 'tools', '*.py')) + [os.path.join(root, 'bench.py')]
+    protos = declared('mmft.h')
     checked, bad = 0, []
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in ('call', 'query') and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2                                  # (device, stream)
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown:
-                continue
-            checked += 1
-            if name not in protos:
-                bad.append((name, 'not declared', f, node.lineno))
-            elif protos[name] != n:
-                bad.append((name, protos[name], n, f, node.lineno))
+    for name, n, f, lineno in call_sites(('call', 'query'), bench=True):
+        if n is None:
+            continue
+        checked += 1
+        if name not in protos:
+            bad.append((name, 'not declared', f, lineno))
+        elif protos[name] != n:
+            bad.append((name, protos[name], n, f, lineno))
     assert checked > 100 and not bad, bad
 
 
@@ -548,24 +525,6 @@ ABI_CALLED_THROUGH_WRAPPER = {
     'mmft_minmax_normalize': ('test_prep_gpu.py', 'prep.py', 'minmax_normalize_'),
     'mmft_u16_pack_weights': ('test_unet16_gpu.py', 'unet16.py', 'pack_run'),
 }
-
-
-def _code_only(src):
-    """Python source without comments and docstrings: what is left are names and the string literals that code uses."""
-    import ast
-    import io
-    import tokenize
-    doc = set()
-    for node in ast.walk(ast.parse(src)):
-        if isinstance(node, (ast.Module, ast.FunctionDef, ast.ClassDef)) and node.body and isinstance(node.body[0], ast.Expr) and \
-                isinstance(node.body[0].value, ast.Constant) and isinstance(node.body[0].value.value, str):
-            doc.add(node.body[0].lineno)
-    out = []
-    for tok in tokenize.generate_tokens(io.StringIO(src).readline):
-        if tok.type == tokenize.COMMENT or (tok.type == tokenize.STRING and tok.start[0] in doc):
-            continue
-        out.append(tok.string)
-    return ' '.join(out)
 
 
 def test_every_abi_entry_point_has_a_kernel_level_test():

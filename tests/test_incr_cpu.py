@@ -1,7 +1,5 @@
 """Incremental re-prediction without a GPU: the numpy cone test_incr_gpu.py checks the device against is a closure, the ledger of
 include/mmft_incr.h (the rules test_place_cpu.py applies to include/mmft_place.h), and the host validation of update(rows=)."""
-import ast
-import glob
 import os
 import re
 
@@ -10,13 +8,11 @@ import pytest
 import torch
 
 import incr_cases as C
+from abi_ledger import call_sites, code_only as _code_only, declared as _declared
 from mmft import lib
 from mmft.infer import check_rows
-from test_host_cpu import _code_only
-from test_report_cpu import _declared
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ['mmft_fanout_cone_step', 'mmft_mlp2_feat_fwd_bf16_masked', 'mmft_update_rows_diff']
 
 
@@ -129,29 +125,14 @@ def test_the_built_library_exports_the_three_symbols_and_refuses_bad_arguments_o
 
 def test_every_incr_call_site_matches_the_header_and_the_kernel_test_names_the_entry_points():
     protos = _declared('mmft_incr.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, seen = 0, [], set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'incr' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name == 'mmft_version':                      # (the refusal test above)
-                continue
-            checked += 1
-            seen.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('incr'):
+        if n is None or name == 'mmft_version':                        # (the refusal test above)
+            continue
+        checked += 1
+        seen.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 6 and seen == set(NAMES) and not bad, bad
     src = open(os.path.join(HERE, 'test_incr_gpu.py')).read()
     assert 'pytestmark = pytest.mark.gpu' in src

@@ -2,26 +2,21 @@
 tests/pin_move_oracle.py on every case, the conditions under which the cases bite, the ledger of include/mmft_sens_pins.h (the
 rules test_sens_cpu.py applies to include/mmft_sens.h) with the host-side refusals of its two entry points, and the refusals of
 Sensitivity(pins=True) that need no device."""
-import ast
 import ctypes
-import glob
 import os
 
 import numpy as np
 import pytest
 import torch
 
+from abi_ledger import call_sites, declared as _declared, others
 from mmft import lib, placement as PL
 from pin_move_cases import CASES, DOUTS, HAND, PinCase, operands
 from pin_move_oracle import FLAGS, geometry, oracle
-from test_report_cpu import _declared
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 NAMES = ['mmft_pin_move_rows', 'mmft_pin_move_sum']
 NARGS = {'mmft_pin_move_rows': 18, 'mmft_pin_move_sum': 9}
-OTHER_HEADERS = ('mmft.h', 'mmft_report.h', 'mmft_place.h', 'mmft_incr.h', 'mmft_crit.h', 'mmft_head.h', 'mmft_crit_sums.h', 'mmft_sens.h',
-                 'mmft_sens_image.h')
+OTHER_HEADERS = others('mmft_sens_pins.h')
 
 
 # ------------------------------------------------------------------------------------------------ host form vs the definition
@@ -123,30 +118,15 @@ def test_pins_header_declares_exactly_the_two_names_and_overlaps_no_other_header
 
 def test_every_pmove_call_site_matches_the_header():
     protos = _declared('mmft_sens_pins.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, product = 0, [], set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'pmove' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name not in protos:                       # (a list built elsewhere; the refusal test above)
-                continue
-            checked += 1
-            if os.sep + 'mmft' + os.sep in f:
-                product.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('pmove'):
+        if n is None or name not in protos:                         # (a list built elsewhere; the refusal test above)
+            continue
+        checked += 1
+        if os.sep + 'mmft' + os.sep in f:
+            product.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name), n, f, lineno))
     assert checked >= 2 and product == set(NAMES) and not bad, bad
 
 

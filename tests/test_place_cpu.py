@@ -2,9 +2,7 @@
 include/mmft_report.h), mmft.placement's host side (rasterize_host, runs_host, attach_placement, the record round trip,
 PlacedPaths' batching) against the oracle's mask rule, fusion._runs_from_csr and a literal restatement, and a mutation check:
 each clause of the rule, broken in the literal form, must be noticed by the cases test_place_gpu.py feeds to the kernel."""
-import ast
 import copy
-import glob
 import os
 import re
 
@@ -13,14 +11,12 @@ import pytest
 import torch
 
 import place_cases as C
+from abi_ledger import call_sites, code_only as _code_only, declared as _declared
 from mmft import fusion, lib
 from mmft import placement as PL
 from oracle.prep_restatement import path_mask_rows
-from test_host_cpu import _code_only
-from test_report_cpu import _declared
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 
 
 # ------------------------------------------------------------------------------------------------ the header's ledger
@@ -43,28 +39,13 @@ def test_place_header_is_exported_and_the_other_headers_are_what_they_were():
 
 def test_every_place_call_site_matches_the_header_and_the_kernel_test_names_the_entry_point():
     protos = _declared('mmft_place.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad = 0, []
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'place' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name == 'mmft_version':                      # (the refusal test above)
-                continue
-            checked += 1
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('place'):
+        if n is None or name == 'mmft_version':                        # (the refusal test above)
+            continue
+        checked += 1
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 3 and not bad, bad
     src = open(os.path.join(HERE, 'test_place_gpu.py')).read()
     assert 'pytestmark = pytest.mark.gpu' in src

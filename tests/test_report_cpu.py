@@ -4,7 +4,6 @@ against a second, literal restatement of the contract, and a mutation check: eac
 noticed on the inputs that test_report_gpu.py feeds to the kernel."""
 import ast
 import functools
-import glob
 import os
 import re
 
@@ -12,21 +11,12 @@ import numpy as np
 import pytest
 
 import report_cases as C
+from abi_ledger import call_sites, code_only as _code_only, declared as _declared
 from mmft import lib
 from mmft import report as R
-from test_host_cpu import _code_only
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-
-
-def _declared(header):
-    hdr = re.sub(r'/\*.*?\*/', '', open(os.path.join(ROOT, 'include', header)).read(), flags=re.S)
-    protos = {}
-    for m in re.finditer(r'\b(?:int|long long|const char\*)\s+(mmft_[a-z0-9_]+)\s*\(([^;]*?)\)\s*;', hdr, re.S):
-        args = m.group(2).strip()
-        protos[m.group(1)] = 0 if args in ('', 'void') else len(args.split(','))
-    return protos
 
 
 # ------------------------------------------------------------------------------------------------ the extension ledger
@@ -61,28 +51,13 @@ def test_every_extension_entry_point_has_a_kernel_level_test():
 
 def test_every_ext_call_site_matches_the_extension_header():
     protos = _declared('mmft_report.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad = 0, []
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'ext' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str)):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown:
-                continue
-            checked += 1
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name, 'not declared'), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('ext'):
+        if n is None:
+            continue
+        checked += 1
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name, 'not declared'), n, f, lineno))
     assert checked >= 3 and not bad, bad
 
 

@@ -3,9 +3,7 @@ applies to include/mmft_sens.h), the host-side refusals of its two entry points 
 is looked at - the plain oracle of tests/sens_image_oracle.py against the fixtures the REFERENCE's module produced
 (tests/golden/make_golden_eval_grad.py) and against central differences of the eval forward, and the refusals of
 Sensitivity(image=True) that need no device."""
-import ast
 import ctypes
-import glob
 import os
 import types
 
@@ -13,19 +11,18 @@ import numpy as np
 import pytest
 import torch
 
+from abi_ledger import call_sites, declared as _declared, others
 from conftest import rel_err
 from mmft import lib
 from mmft.detrand import det_uniform, det_state_dict
 import sens_image_oracle as SI
 import unet_eval_oracle as E
-from test_report_cpu import _declared
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-ROOT = os.path.dirname(HERE)
 GOLD = os.path.join(HERE, 'golden')
 NAMES = ['mmft_u16_conv3x3_dgrad_image', 'mmft_u16_frozen_bwd']
 NARGS = {'mmft_u16_frozen_bwd': 16, 'mmft_u16_conv3x3_dgrad_image': 8}
-OTHER_HEADERS = ('mmft.h', 'mmft_report.h', 'mmft_place.h', 'mmft_incr.h', 'mmft_crit.h', 'mmft_head.h', 'mmft_crit_sums.h', 'mmft_sens.h')
+OTHER_HEADERS = others('mmft_sens_image.h')
 FIXTURES = [('max', 8, 32, 2), ('avg', 16, 64, 1)]
 
 
@@ -52,31 +49,16 @@ def test_image_header_declares_exactly_the_two_names_and_overlaps_no_other_heade
 
 def test_every_simg_call_site_matches_the_header():
     protos = _declared('mmft_sens_image.h')
-    files = glob.glob(os.path.join(ROOT, 'multimodal-fusion-based-pre-routing-timing-prediction-_amd', '**', '*.py'), recursive=True)
-    files += glob.glob(os.path.join(ROOT, 'tests', '*.py')) + glob.glob(os.path.join(ROOT, 'tools', '*.py'))
     checked, bad, seen, product = 0, [], set(), set()
-    for f in files:
-        for node in ast.walk(ast.parse(open(f).read())):
-            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr == 'simg' and node.args
-                    and isinstance(node.args[0], ast.Constant) and isinstance(node.args[0].value, str) and node.args[0].value.startswith('mmft_')):
-                continue
-            name, n, unknown = node.args[0].value, 0, False
-            for a in node.args[1:]:
-                if isinstance(a, ast.Starred):
-                    if isinstance(a.value, ast.Call) and getattr(a.value.func, 'attr', '') == 'stream_args':
-                        n += 2
-                    else:
-                        unknown = True
-                else:
-                    n += 1
-            if unknown or name not in protos:                       # (a list built elsewhere; the refusal test above)
-                continue
-            checked += 1
-            seen.add(name)
-            if os.sep + 'mmft' + os.sep in f:
-                product.add(name)
-            if protos.get(name) != n:
-                bad.append((name, protos.get(name), n, f, node.lineno))
+    for name, n, f, lineno in call_sites('simg'):
+        if n is None or name not in protos:                         # (a list built elsewhere; the refusal test above)
+            continue
+        checked += 1
+        seen.add(name)
+        if os.sep + 'mmft' + os.sep in f:
+            product.add(name)
+        if protos.get(name) != n:
+            bad.append((name, protos.get(name), n, f, lineno))
     assert checked >= 2 and seen == set(NAMES) and product == set(NAMES) and not bad, bad
 
 
