@@ -151,12 +151,27 @@ __global__ void __launch_bounds__(256) bcast_row_kernel(const float* __restrict_
 // ---- backward of the run form --------------------------------------------------------------------------------
 // One workgroup per (design, block of S cells), 256 threads = J entry lanes x GROUPS channel groups.
 // Stage 1: D[c] = sum of gout over the batch rows whose path has a run ENDING at cell c, minus those with a run STARTING
-// at c + 1 inside the block (`code` >= 0: path id, run end; < 0: path id = -code - 1, run start).  Entry lane j owns the
-// cells [j S/J, (j+1) S/J) and walks their boundary lists with four index -> batch-row -> gradient-row chains in flight;
+// at c + 1 inside the block (`code` >= 0: path id, run end; < 0: path id = -code - 1, run start).  A block's boundary
+// entries are one contiguous range of bcode.  Resolve: all threads turn it, coalesced, into one (batch row | -1 = path not
+// sampled, flags) pair per entry in LDS - the code -> first -> next hops are walked once per workgroup, not once per lane and
+// round.  Gather: entry lane j owns the cells [j S/J, (j+1) S/J), whose resolved entries are contiguous too, and walks them as
+// ONE list, MFB_DEPTH gradient rows in flight per round and one dependent global load per round (entries of unsampled paths
+// issue none; `next` is followed only where the flag says the path occurs twice in the batch); the sum of a cell is closed
+// where the walk crosses the cell's end, so it is formed in entry order exactly as by the direct walk.  A block whose list
+// exceeds MFB_CAP entries (decided per workgroup from its own pointers) takes the direct walk: four index -> batch-row ->
+// gradient-row chains in flight per cell.  Both give the same bits: an entry contributes gout[first] + (the rest of its chain
+// in batch order) as one term, and skipping an unsampled entry equals adding its zeros (a sum that starts at +0 never is -0).
 // D stays in LDS.  Stage 2 (every lane: local suffix sums of its cells + the later lanes' totals): suffix sums of D give
 // dg[c] = d loss / d(f[c] wT[c]); emit the design's dwT slab (f dg) and df[c] = <dg, wT[c]> (wave-shuffle reduction over the
 // GROUPS lanes).  Fixed orders.
 constexpr int MFB_THREADS = 512;      // 16 entry lanes x 32 channel groups at Dout = 128: 4 cells per lane (256: 246 us, 512: 192 us, 1024: 231 us)
+constexpr int MFB_CAP = 2048;         // resolved entries kept in LDS: config B has 1 020 per block, 1 277 at most over the eight designs
+constexpr int MFB_DEPTH = 4;          // gradient rows in flight per entry lane (66 VGPRs: three workgroups per CU; with the slab reduction 2: 119 us, 4: 106, 5: 105, 6: 122, 8: 121)
+static_assert(MFB_CAP * 8 >= MFB_THREADS * 16, "stage 2's lane totals reuse the resolved list's LDS");
+// dynamic LDS: D [S][Dout] floats | the block's S + 1 list pointers (relative) | MFB_CAP (+ MFB_DEPTH of padding) resolved entries (stage 2: the lane totals)
+__host__ __device__ static inline int mfb_ptr_words(int S) { return (S + 4) & ~3; }      // S + 1, rounded up to 16 bytes
+static inline size_t mfb_lds_bytes(int S, int Dout) { return ((size_t)S * Dout + mfb_ptr_words(S)) * 4 + (size_t)(MFB_CAP + MFB_DEPTH) * 8; }
+
 template <int GROUPS>
 __global__ void __launch_bounds__(MFB_THREADS) masked_fc_bwd_runs_kernel(const int* __restrict__ bptr, const int* __restrict__ bcode,
                                                                  const int* __restrict__ first, const int* __restrict__ next,
@@ -165,6 +180,9 @@ __global__ void __launch_bounds__(MFB_THREADS) masked_fc_bwd_runs_kernel(const i
                                                                  float* __restrict__ df, int P, int S) {
   constexpr int Dout = GROUPS * 4, J = MFB_THREADS / GROUPS;
   extern __shared__ __attribute__((aligned(16))) float dl[];            // [S][Dout]
+  int* const lp = reinterpret_cast<int*>(dl + S * Dout);
+  int2* const res = reinterpret_cast<int2*>(lp + mfb_ptr_words(S));
+  f32x4* const tot = reinterpret_cast<f32x4*>(res);
   const int b = blockIdx.y, blk = blockIdx.x;
   const int j = threadIdx.x / GROUPS, c4 = threadIdx.x % GROUPS;
   const long long cell0 = (long long)b * P + (long long)blk * S;
@@ -175,49 +193,112 @@ __global__ void __launch_bounds__(MFB_THREADS) masked_fc_bwd_runs_kernel(const i
     return sum;
   };
   const int cpl = S / J;
-  // the boundary-list pointers of the lane's cells in one go (they are consecutive): the cells' chains start together
-  int eb[9];
+  const int le0 = bptr[cell0], ln = bptr[cell0 + S] - le0;
+  if (ln <= MFB_CAP) {                              // the same for every thread of the workgroup
+    for (int i = threadIdx.x; i <= S; i += MFB_THREADS) lp[i] = bptr[cell0 + i] - le0;
+    for (int i0 = threadIdx.x; i0 < ln; i0 += 4 * MFB_THREADS) {      // four entries per thread: their three hops overlap
+      // every load unconditional (a branch around a load makes the compiler wait for it there): a thread past the list's end
+      // re-reads the last entry, an unsampled path re-reads its `first` word in place of a `next` word
+      int code[4], path[4], t[4], nx[4];
 #pragma unroll
-  for (int i = 0; i < 9; ++i) eb[i] = (cpl <= 8 && i <= cpl) ? bptr[cell0 + j * cpl + i] : 0;
-  for (int y = j * cpl; y < (j + 1) * cpl; ++y) {
+      for (int k = 0; k < 4; ++k) {
+        code[k] = bcode[le0 + min(i0 + k * MFB_THREADS, ln - 1)];
+        path[k] = code[k] >= 0 ? code[k] : -code[k] - 1;
+      }
+#pragma unroll
+      for (int k = 0; k < 4; ++k) t[k] = first[path[k]];
+#pragma unroll
+      for (int k = 0; k < 4; ++k) nx[k] = *(t[k] >= 0 ? next + t[k] : first + path[k]);
+#pragma unroll
+      for (int k = 0; k < 4; ++k)                   // flags: bit 0 subtract, bit 1 the path occurs again in the batch
+        if (i0 + k * MFB_THREADS < ln)
+          res[i0 + k * MFB_THREADS] = make_int2(t[k], (code[k] < 0 ? 1 : 0) | (t[k] >= 0 && nx[k] >= 0 ? 2 : 0));
+    }
+    __syncthreads();
+    int y = j * cpl;
+    const int yend = y + cpl, iend = lp[yend];
+    int cend = lp[y + 1];
     f32x4 acc = z;
-    int e, e1;
-    if (cpl <= 8) {
-      e = e1 = 0;
+    for (int i = lp[y]; i < iend; i += MFB_DEPTH) {
+      int2 w[MFB_DEPTH];
+      f32x4 r[MFB_DEPTH];
+      int dup = 0;
 #pragma unroll
-      for (int i = 0; i < 8; ++i)
-        if (i == y - j * cpl) { e = eb[i]; e1 = eb[i + 1]; }
-    } else {
-      e = bptr[cell0 + y];
-      e1 = bptr[cell0 + y + 1];
+      for (int k = 0; k < MFB_DEPTH; ++k) {         // read past the lane's end (the list is padded), then mask: no branch per read
+        w[k] = res[i + k];
+        if (i + k >= iend) w[k] = make_int2(-1, 0);
+        dup |= w[k].y;
+      }
+#pragma unroll
+      for (int k = 0; k < MFB_DEPTH; ++k)
+        r[k] = w[k].x >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)w[k].x * ldg + c4 * 4) : z;
+      if (dup & 2) {
+#pragma unroll
+        for (int k = 0; k < MFB_DEPTH; ++k)
+          if (w[k].y & 2) r[k] += rowsum(next[w[k].x]);
+      }
+#pragma unroll
+      for (int k = 0; k < MFB_DEPTH; ++k)
+        if (w[k].x >= 0) {
+          while (i + k >= cend && y + 1 < yend) {   // the walk left cell y: its sum is complete
+            *reinterpret_cast<f32x4*>(dl + y * Dout + c4 * 4) = acc;
+            acc = z;
+            cend = lp[++y + 1];
+          }
+          acc = (w[k].y & 1) ? acc - r[k] : acc + r[k];
+        }
     }
-    for (; e + 4 <= e1; e += 4) {
-      int k0 = bcode[e], k1 = bcode[e + 1], k2 = bcode[e + 2], k3 = bcode[e + 3];
-      int t0 = first[k0 >= 0 ? k0 : -k0 - 1], t1 = first[k1 >= 0 ? k1 : -k1 - 1];
-      int t2 = first[k2 >= 0 ? k2 : -k2 - 1], t3 = first[k3 >= 0 ? k3 : -k3 - 1];
-      f32x4 r0 = t0 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t0 * ldg + c4 * 4) : z;
-      f32x4 r1 = t1 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t1 * ldg + c4 * 4) : z;
-      f32x4 r2 = t2 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t2 * ldg + c4 * 4) : z;
-      f32x4 r3 = t3 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t3 * ldg + c4 * 4) : z;
-      if (t0 >= 0) r0 += rowsum(next[t0]);
-      if (t1 >= 0) r1 += rowsum(next[t1]);
-      if (t2 >= 0) r2 += rowsum(next[t2]);
-      if (t3 >= 0) r3 += rowsum(next[t3]);
-      acc = k0 >= 0 ? acc + r0 : acc - r0;
-      acc = k1 >= 0 ? acc + r1 : acc - r1;
-      acc = k2 >= 0 ? acc + r2 : acc - r2;
-      acc = k3 >= 0 ? acc + r3 : acc - r3;
+    for (; y < yend; ++y) {
+      *reinterpret_cast<f32x4*>(dl + y * Dout + c4 * 4) = acc;
+      acc = z;
     }
-    for (; e < e1; ++e) {
-      int code = bcode[e];
-      f32x4 sum = rowsum(first[code >= 0 ? code : -code - 1]);
-      acc = code >= 0 ? acc + sum : acc - sum;
+    __syncthreads();                                // the resolved list is read no more: stage 2 puts the lane totals there
+  } else {
+    // the boundary-list pointers of the lane's cells in one go (they are consecutive): the cells' chains start together
+    int eb[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) eb[i] = (cpl <= 8 && i <= cpl) ? bptr[cell0 + j * cpl + i] : 0;
+    for (int y = j * cpl; y < (j + 1) * cpl; ++y) {
+      f32x4 acc = z;
+      int e, e1;
+      if (cpl <= 8) {
+        e = e1 = 0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i)
+          if (i == y - j * cpl) { e = eb[i]; e1 = eb[i + 1]; }
+      } else {
+        e = bptr[cell0 + y];
+        e1 = bptr[cell0 + y + 1];
+      }
+      for (; e + 4 <= e1; e += 4) {
+        int k0 = bcode[e], k1 = bcode[e + 1], k2 = bcode[e + 2], k3 = bcode[e + 3];
+        int t0 = first[k0 >= 0 ? k0 : -k0 - 1], t1 = first[k1 >= 0 ? k1 : -k1 - 1];
+        int t2 = first[k2 >= 0 ? k2 : -k2 - 1], t3 = first[k3 >= 0 ? k3 : -k3 - 1];
+        f32x4 r0 = t0 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t0 * ldg + c4 * 4) : z;
+        f32x4 r1 = t1 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t1 * ldg + c4 * 4) : z;
+        f32x4 r2 = t2 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t2 * ldg + c4 * 4) : z;
+        f32x4 r3 = t3 >= 0 ? *reinterpret_cast<const f32x4*>(gout + (long long)t3 * ldg + c4 * 4) : z;
+        if (t0 >= 0) r0 += rowsum(next[t0]);
+        if (t1 >= 0) r1 += rowsum(next[t1]);
+        if (t2 >= 0) r2 += rowsum(next[t2]);
+        if (t3 >= 0) r3 += rowsum(next[t3]);
+        acc = k0 >= 0 ? acc + r0 : acc - r0;
+        acc = k1 >= 0 ? acc + r1 : acc - r1;
+        acc = k2 >= 0 ? acc + r2 : acc - r2;
+        acc = k3 >= 0 ? acc + r3 : acc - r3;
+      }
+      for (; e < e1; ++e) {
+        int code = bcode[e];
+        int t = first[code >= 0 ? code : -code - 1];
+        f32x4 sum = z;
+        if (t >= 0) sum = *reinterpret_cast<const f32x4*>(gout + (long long)t * ldg + c4 * 4) + rowsum(next[t]);
+        acc = code >= 0 ? acc + sum : acc - sum;
+      }
+      *reinterpret_cast<f32x4*>(dl + y * Dout + c4 * 4) = acc;
     }
-    *reinterpret_cast<f32x4*>(dl + y * Dout + c4 * 4) = acc;
   }
   // Stage 2: suffix sums over the block's cells, all entry lanes at work: lane j turns its own cells into local suffix sums,
   // the lanes' totals are added from the block's end (fixed order), and every lane finishes its cells.
-  __shared__ f32x4 tot[MFB_THREADS];
   f32x4 run = z;
   for (int y = (j + 1) * cpl - 1; y >= j * cpl; --y) {
     run += *reinterpret_cast<const f32x4*>(dl + y * Dout + c4 * 4);
@@ -683,8 +764,13 @@ int mmft_masked_fc_bwd_runs(const int* bnd_ptr, const int* bnd_code, const int* 
   hipStream_t st = (hipStream_t)stream;
   float* slabs = B > 1 ? workspace : dwT;
   const dim3 grid(P / S, B);
-  const size_t lds = (size_t)S * Dout * 4;
+  const size_t lds = mfb_lds_bytes(S, Dout);
+  static DynLdsOnce once[7];
+  int arc = MMFT_OK;
 #define MMFT_RUNS(G)                                                                                                   \
+  arc = ensure_dyn_lds(once[__builtin_ctz(G)], (const void*)masked_fc_bwd_runs_kernel<G>, (int)mfb_lds_bytes(16384 / (G * 4), G * 4), \
+                       "masked_fc_bwd_runs");                                                                          \
+  if (arc) return arc;                                                                                                 \
   MMFT_LAUNCH_LDS("masked_fc_bwd_runs_kernel", 0.0, 0.0, masked_fc_bwd_runs_kernel<G>, grid, dim3(MFB_THREADS), lds, st, bnd_ptr, \
                   bnd_code, first, next, gout, ldg, f, wT, slabs, df, P, S)
   switch (groups) {
