@@ -133,7 +133,11 @@ def fanout_cone_mask(in_csrs, level_nodes, seed, within=None, out=None):
 
 
 def trace_critical_paths(in_csrs, level, endpoints, stop=None, maxlen=None):
-    """paths int32[P, maxlen] (-1 padded, endpoint first) and lens int32[P]; `stop`: optional uint8 flags per node."""
+    """paths int32[P, maxlen] (-1 padded, endpoint first) and lens int32[P]; `stop`: optional uint8 flags per node
+    (the reference's "'clk' in name.lower()").  Predecessors are visited in CSR order, which must be edge insertion order
+    (networkx's predecessors()).  With two CSRs all of the first one's predecessors of a node come before the second's;
+    that equals the reference's order only where a node's in-edges are all of one kind, as for a netlist pin (driven
+    through one net, or by the arcs of one cell)."""
     p = _csr_pair(in_csrs)
     ops._chk(level, 'level', torch.int32); ops._chk(endpoints, 'endpoints', torch.int32)
     if stop is not None:

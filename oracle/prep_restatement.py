@@ -6,10 +6,19 @@ imports this).  Plain Python over adjacency lists, following the reference state
     path masks            src/verilog_parser_asap7.py:1302-1369   (masking == 'critical')
     minMax_scalar / norm  src/train.py:309-318
 
-Pinning: the reference functions need networkx graphs built by its Verilog parser (pyverilog and the raw EDA data are
-absent here), so they cannot be run; the reference holds no fixture for them either -> **parity unpinned** for this
-file.  The restatement is checked instead against properties (every node's level = longest path from a primary
-input, brute force) in tests/test_prep_cpu.py.
+Pinning: tests/golden/make_golden_prep.py runs the reference's own code on hand-built and random pin graphs and writes
+tests/golden/prep_*.npz (prep_edges, prep_random_600, prep_norm).  The parser module itself does not import without
+pyverilog and dgl, so the generator takes cal_topo_level and find_critical_path out of its syntax tree and runs them
+against a namespace holding a networkx.DiGraph and node2level, which is all they touch; minMax_scalar / norm likewise.
+The mask loop is no function: it is the inline slice of parse_netlist from `self.path_masks = th.zeros(...)` through
+`self.path_masks = mask_2`, executed as it stands.  The generator asserts that every function below equals the reference
+on every fixture (levels and paths equal, mask rows as sorted sets, norm bitwise with NaNs in place), and
+tests/test_prep_golden_cpu.py repeats that from the fixtures alone.  tests/test_prep_cpu.py adds property checks (every
+node's level = longest path from a primary input, brute force).
+
+find_critical_path skips predecessors without a level: the reference has removed them from its graph by then.  Where a
+node at level >= 2 has no predecessor one level below and none named clk, the reference's loop does not end; that cannot
+happen with levels from cal_topo_level, and this restatement (like the kernel) stops there.
 """
 import numpy as np
 import torch

@@ -1,6 +1,6 @@
-"""The preprocessing restatement (oracle/prep_restatement.py) has no reference fixture to pin it (parity unpinned,
-see its header); these checks tie it to the definitions instead: longest-path levels by brute force, path validity,
-mask rows as explicit unions of rectangles."""
+"""The preprocessing restatement (oracle/prep_restatement.py) is pinned to the reference's own functions by the fixtures
+of tests/test_prep_golden_cpu.py; these checks tie it to the definitions as well: longest-path levels by brute force, path
+validity, mask rows as explicit unions of rectangles."""
 import numpy as np
 import torch
 

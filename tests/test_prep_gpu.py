@@ -1,5 +1,6 @@
-"""GPU preprocessing kernels (mmft.prep) against the CPU restatement: integer outputs bit-exact, min-max scaling
-bit-exact in fp32; plus the size-independent property at BASELINE sizes that levelizing a synthetic design from its
+"""GPU preprocessing kernels (mmft.prep): against the CPU restatement on random graphs, and against the fixtures that the
+reference's own functions produced (tests/golden/prep_*.npz) at the edges listed there - integer outputs bit-exact, min-max
+scaling bit-exact in fp32; plus the size-independent property at BASELINE sizes that levelizing a synthetic design from its
 level-0 nodes reproduces the generator's levels."""
 import numpy as np
 import pytest
@@ -7,6 +8,7 @@ import torch
 
 from oracle import prep_restatement as PR
 from test_prep_cpu import random_dag
+from test_prep_golden_cpu import GRAPHS, MAP_SIZES, fixture, norm_fixture, same_bits
 from conftest import rel_err
 
 pytestmark = pytest.mark.gpu
@@ -105,6 +107,76 @@ def test_minmax_normalize_bit_exact(dev):
     g[1, 2] = float('nan')
     w2, g2 = PR.norm(g, 0), prep.minmax_normalize_(g.to(dev).clone(), 0).cpu()
     assert torch.equal(torch.isnan(w2), torch.isnan(g2)) and torch.equal(torch.nan_to_num(w2), torch.nan_to_num(g2))
+
+
+# ---- against what the reference's own functions computed (tests/golden/prep_*.npz, tests/golden/make_golden_prep.py):
+# integer and bitwise comparisons only, the restatement is not involved
+
+def _csr_forms(fx, rows, cols, dev):
+    """The merged CSR and the two CSRs split by edge kind (net, cell), as PinGraph keeps them."""
+    net = fx.kind == 0
+    return {'merged': [csr(fx.n, rows, cols, dev)],
+            'split': [csr(fx.n, rows[net], cols[net], dev), csr(fx.n, rows[~net], cols[~net], dev)]}
+
+
+@pytest.mark.parametrize('form', ['merged', 'split'])
+@pytest.mark.parametrize('name', GRAPHS)
+def test_levelize_vs_reference_fixture(dev, name, form):
+    """mmft_levelize: primary inputs below other primary inputs, a primary input without successors, removed nodes,
+    duplicated edges, a node in three frontiers; 600 nodes reach the kernels' second block."""
+    from mmft import prep
+    fx = fixture(name)
+    level, nl = prep.levelize(_csr_forms(fx, fx.src, fx.dst, dev)[form], fx.n, torch.from_numpy(fx.pis.astype(np.int32)).to(dev))
+    assert nl == fx.nl and np.array_equal(level.cpu().numpy(), fx.level)
+    assert [t.cpu().tolist() for t in prep.level_lists(level, nl)] == fx.level_sets()
+
+
+@pytest.mark.parametrize('form', ['merged', 'split'])
+@pytest.mark.parametrize('name', GRAPHS)
+def test_trace_critical_paths_vs_reference_fixture(dev, name, form):
+    """mmft_trace_critical_paths with the stop flags the reference derives from the names ('clk' in name.lower()): a clk
+    predecessor before / after the matching one, an upper-case CLK, removed predecessors ahead of the others."""
+    from mmft import prep
+    fx = fixture(name)
+    level = torch.from_numpy(fx.level.astype(np.int32)).to(dev)
+    paths, lens = prep.trace_critical_paths(_csr_forms(fx, fx.dst, fx.src, dev)[form], level,
+                                            torch.from_numpy(fx.ends.astype(np.int32)).to(dev),
+                                            stop=torch.from_numpy(fx.stop.astype(np.uint8)).to(dev))
+    want, want_lens = fx.path_table()
+    assert lens.cpu().tolist() == want_lens.tolist()
+    assert np.array_equal(paths.cpu().numpy(), want)                     # -1 after each path
+
+
+@pytest.mark.parametrize('size', MAP_SIZES, ids=lambda s: f'{s[0]}x{s[1]}')
+@pytest.mark.parametrize('name', GRAPHS)
+def test_rasterize_path_masks_vs_reference_fixture(dev, name, size):
+    """mmft_path_mask_count + mmft_path_mask_fill on the recorded paths: a partial last word (5 x 7, 37 x 45), two and
+    eight words per thread in the emission (96 x 96, 256 x 256), whole words inside a row range, boxes of one cell, of
+    full rows, of the full map, ending on the last cell, starting on bit 0 and on bit 31 of a word."""
+    from mmft import prep
+    fx = fixture(name)
+    tab, lens = fx.path_table(fx.mask_paths)
+    px, py = fx.pins[size]
+    ip, cols = prep.rasterize_path_masks(torch.from_numpy(tab).to(dev), torch.from_numpy(lens).to(dev),
+                                         torch.from_numpy(px.astype(np.int32)).to(dev),
+                                         torch.from_numpy(py.astype(np.int32)).to(dev), *size)
+    wip, wcols = fx.row_csr(size)
+    assert np.array_equal(ip.cpu().numpy(), wip) and np.array_equal(cols.cpu().numpy(), wcols)
+
+
+@pytest.mark.parametrize('pitch', [7, 12])
+def test_minmax_normalize_vs_reference_fixture(dev, pitch):
+    """mmft_minmax_normalize on the matrix the reference's norm scaled: constant, NaN, +inf and subnormal-range columns, one
+    row in the second strip; contiguous and as a view of a wider allocation."""
+    from mmft import prep
+    feat, out, start = norm_fixture()
+    buf = torch.full((feat.shape[0], pitch), 7.0, device=dev)
+    view = buf[:, :feat.shape[1]]
+    view.copy_(feat.to(dev))
+    assert view.stride(0) == pitch
+    got = prep.minmax_normalize_(view, start)
+    assert got is view and same_bits(got.cpu(), out)
+    assert bool((buf[:, feat.shape[1]:] == 7.0).all())                   # the padding is not touched
 
 
 @pytest.mark.parametrize('cfg', ['B', 'E'])
