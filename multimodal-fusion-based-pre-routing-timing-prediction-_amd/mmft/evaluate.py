@@ -127,7 +127,7 @@ def validate(train_step, path_ids_per_design=None, per_level=False, frozen_stats
     if not per_level:
         return metrics_from_sums(eval_sums(hats, arrival, required, label).cpu().tolist())
     both = torch.cat([eval_sums(hats, arrival, required, label).reshape(1, 10),
-                      eval_sums_by_level(hats, arrival, required, label, sel[5].contiguous(), b.L)], 0).cpu().tolist()
+                      eval_sums_by_level(hats, arrival, required, label, sel.levels.contiguous(), b.L)], 0).cpu().tolist()
     m = metrics_from_sums(both[0])
     m['levels'] = level_metrics_from_sums(both[1:])
     return m
@@ -137,14 +137,13 @@ def _validate_per_design(b, sel, hats, arrival, required, label, per_level):
     """The 'reg' tail of validate(per_design=True): pooled sums [1], per-level sums [L] (per_level), per-design sums [B],
     per-design-and-level sums [B * L] (per_level) - one concatenation, one device->host copy."""
     B, L = b.B, b.L
-    # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
-    design = torch.div(sel[2], b.P, rounding_mode='floor').to(torch.int32).contiguous()
+    design = torch.div(sel.feat_off, b.P, rounding_mode='floor').to(torch.int32).contiguous()      # on the device: no upload
     parts = [eval_sums(hats, arrival, required, label).reshape(1, 10)]
     if per_level:
-        parts.append(eval_sums_by_level(hats, arrival, required, label, sel[5].contiguous(), L))
+        parts.append(eval_sums_by_level(hats, arrival, required, label, sel.levels.contiguous(), L))
     parts.append(eval_sums_by_level(hats, arrival, required, label, design, B))
     if per_level:
-        parts.append(eval_sums_by_level(hats, arrival, required, label, (design * L + sel[5]).contiguous(), B * L))
+        parts.append(eval_sums_by_level(hats, arrival, required, label, (design * L + sel.levels).contiguous(), B * L))
     rows = torch.cat(parts, 0).cpu().tolist()
     m = metrics_from_sums(rows[0])
     pos = 1
@@ -181,16 +180,13 @@ def timing_report(train_step, path_ids_per_design=None, k=32, hist=None, frozen_
     sel = b.select(path_ids_per_design)
     with frozen_statistics(train_step.cnn, frozen_stats):
         hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
-    idx, T = ends_d.long(), ends_d.numel()
-    arrival = b.arrival[idx].reshape(T).contiguous()
-    required = b.required[idx].reshape(T).contiguous()
-    # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
-    design = np.zeros(T, dtype=np.int64) if b.B == 1 else sel[2].cpu().numpy().astype(np.int64) // b.P
-    ptr, rows = (torch.from_numpy(a).to(hats.device) for a in R.group_rows(design, b.B))
+    arrival = b.arrival[ends_d.long()].reshape(sel.T).contiguous()
+    required = sel.required_times(b)
+    ptr, rows = (torch.from_numpy(a).to(hats.device) for a in R.group_rows(sel.design, b.B))
     bufs = R.ReportBuffers(b.B, k, hist, hats.device, reports=2)
     R.timing_report(hats.contiguous(), required, ptr, rows, k, hist, out=bufs.tensors(0))
     R.timing_report(arrival, required, ptr, rows, k, hist, out=bufs.tensors(1))
-    predicted, actual = (R.decode(*h, endpoints=np.asarray(sel[4])) for h in bufs.host())
+    predicted, actual = (R.decode(*h, endpoints=np.asarray(sel.endpoints)) for h in bufs.host())
     out = []
     for p, a in zip(predicted, actual):
         m = min(int(k), p['n'], a['n'])

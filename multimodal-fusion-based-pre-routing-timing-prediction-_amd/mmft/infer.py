@@ -1,7 +1,8 @@
 """Inference on resident designs: `Predictor` holds a batch of designs on the device, returns the predicted arrival time of
 their endpoints and lets the caller push new features / layout images (a placement that keeps changing under one netlist).
 
-The arithmetic is TrainStep.forward's whole-sweep form under torch.no_grad(): the netlist sweep in its forward-only form
+The arithmetic is TrainStep.forward's whole-sweep form (train.forward_to_head, the one place that orders its launches) under
+torch.no_grad(): the netlist sweep in its forward-only form
 (mmft.sweep.FORWARD_ONLY: nothing kept for a reverse sweep), the U-Net from its running statistics
 (evaluate.frozen_statistics; 19 launches in bf16 mode), masked projection, fusion head.  Nothing of the model is written: no
 statistic, no counter, no gradient, no module mode.  In bf16 mode the whole call is captured once and replayed.
@@ -13,8 +14,7 @@ import torch
 
 from . import gradsink, lib, ops
 from .evaluate import frozen_statistics
-from .fusion import MaskedPathMap
-from .train import DesignBatch
+from .train import DesignBatch, forward_to_head
 
 
 def design_permutations(old_of_new, node_off):
@@ -90,7 +90,62 @@ def update_design(batch, perm, i, cell_feat=None, net_feat=None, image=None, row
         batch.images[i].copy_(img)
 
 
-class Predictor:
+class ResidentDesigns:
+    """What the front ends that keep a batch of designs on the device share (Predictor, sensitivity.Sensitivity): the
+    DesignBatch, ONE Selection of paths made here (static_selection: its packed indices live in `_static_idx`, at addresses
+    a replayed graph may keep) with the rows' slack inputs - `required` (fp32 [T] on the device) and `row_design` (host int64
+    [T]) -, h, the per-design row permutations, and the module modes of a call."""
+
+    def __init__(self, who, pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap, static_selection=False):
+        self.pmodel, self.cnn = pmodel, cnn
+        self.device = torch.device(device)
+        self.frozen_stats = bool(frozen_stats)
+        self.overlap = bool(overlap) and pmodel.gnn is not None
+        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
+        b = self.batch = DesignBatch(designs, device, pmodel.gnn.out_feat_dim if pmodel.gnn is not None else 128)
+        if path_ids_per_design is None:
+            path_ids_per_design = [np.arange(d.num_paths) for d in designs]
+        self.T = int(sum(len(p) for p in path_ids_per_design))
+        if self.T == 0:
+            raise ValueError(f'{who}: no path selected')
+        self._static_idx = None
+        if static_selection:
+            self._static_idx = torch.zeros(6 * self.T + b.path2level.shape[0], dtype=torch.int32, device=self.device)
+        self._sel = b.select(path_ids_per_design, static=self._static_idx)
+        self.endpoints = np.asarray(self._sel.endpoints)    # the caller's numbering: node_off[design] + the design's own node id
+        self.required, self.row_design = self._sel.required_times(b), self._sel.design
+        self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
+        self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
+        self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
+        self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
+
+    @contextlib.contextmanager
+    def _modes_kept(self):
+        """Module modes and the U-Net's statistics-per-image switch (set for the call, as TrainStep sets it for good: with it
+        a train-mode U-Net treats every design's image as the batch of one the reference feeds) back as found, also on an
+        exception."""
+        modes = [(m, m.training) for m in self._modules]
+        per = [(m, m.per_sample_stats) for m in self._per_sample]
+        try:
+            for m in self._per_sample:
+                m.per_sample_stats = True
+            yield
+        finally:
+            for m, was in per:
+                m.per_sample_stats = was
+            for m, was in modes:
+                m.training = was
+
+    def _check_design(self, i, what):
+        if not 0 <= i < self.batch.B:
+            raise IndexError(f'{what}: design {i} of {self.batch.B}')
+
+    def _update_design(self, i, cell_feat, net_feat, image, rows, **kw):
+        self._check_design(i, 'update')
+        update_design(self.batch, self._perm[i], i, cell_feat, net_feat, image, rows=rows, **kw)
+
+
+class Predictor(ResidentDesigns):
     """Predictor(pmodel, cnn, designs, device).predict() -> (predictions, endpoint ids).
 
     path_ids_per_design   per design the paths whose endpoints are predicted (None: every path of every design); fixed for
@@ -148,26 +203,10 @@ class Predictor:
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
                  cone=False, report=None, placement=False, incremental=False, criticality=None):
         criticality = self._criticality_spec(criticality)
-        self.pmodel, self.cnn = pmodel, cnn
-        self.device = torch.device(device)
-        self.frozen_stats, self.graphed, self.cone = bool(frozen_stats), bool(graphed), bool(cone)
-        self.overlap = bool(overlap) and pmodel.gnn is not None
-        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
-        b = self.batch = DesignBatch(designs, device, pmodel.gnn.out_feat_dim if pmodel.gnn is not None else 128)
-        if path_ids_per_design is None:
-            path_ids_per_design = [np.arange(d.num_paths) for d in designs]
-        T = int(sum(len(p) for p in path_ids_per_design))
-        if T == 0:
-            raise ValueError('Predictor: no path selected')
-        self._static_idx = torch.zeros(6 * T + b.path2level.shape[0], dtype=torch.int32, device=self.device)
-        self._sel = b.select(path_ids_per_design, static=self._static_idx)
-        self._links, self._end_order = b.links, b.end_order
-        self.endpoints = np.asarray(self._sel[4])           # the caller's numbering: node_off[design] + the design's own node id
-        self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
-        self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
+        super().__init__('Predictor', pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap, static_selection=True)
+        self.graphed, self.cone = bool(graphed), bool(cone)
+        b = self.batch
         self._perm32 = None                                # incremental=True: the same as int32, what update_rows_diff indexes by
-        self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
-        self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
         self._tensors = [t for root in (pmodel, cnn) if root is not None for t in list(root.parameters()) + list(root.buffers())]
         self._replay = self._sig = self._out = None
         # incremental sweeps: which feature rows changed since the last predict() / which rows that predict() swept (static
@@ -179,7 +218,6 @@ class Predictor:
         self._trusted, self._trust_sig, self._incr_ok = False, None, {}
         if self.incremental:
             self._perm32 = [q.to(torch.int32) for q in self._perm]
-        self._slack = None
         self._report = self._make_report(report) if report is not None else None
         self._placed = self._make_placed(designs) if placement else None
         self._crit = self._make_criticality(criticality, designs) if criticality is not None else None
@@ -190,38 +228,15 @@ class Predictor:
         from . import placement as PL
         if self.pmodel.fcn is None or self.cnn is None:
             raise ValueError('Predictor: placement=True needs the masked projection (pmodel.fcn and a CNN)')
-        for i, d in enumerate(designs):
-            if not PL.has_placement(d):
-                raise ValueError(f'Predictor: placement=True, but design {i} carries no placement data '
-                                 f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
-        b = self.batch
-        if not b.masks.run_block or b.P > PL.MAX_CELLS:
-            raise ValueError(f'Predictor: placement=True needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; it has {b.P}')
-        placed = PL.PlacedPaths(designs, b.node_off, self.device)
-        ip, cols = (t.cpu().numpy().astype(np.int64) for t in placed.csr())
-        for i in range(b.B):
-            q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
-            if not (np.array_equal(ip[q0:q1 + 1], b.masks.host_indptr[q0:q1 + 1]) and
-                    np.array_equal(cols[ip[q0]:ip[q1]], b.masks.host_cols[ip[q0]:ip[q1]])):
-                raise ValueError(f'Predictor: the stored masks of design {i} are not the masks of its pins '
-                                 '(placement.attach_placement rebuilds them)')
-        return placed
+        return PL.batch_tables(designs, self.batch, self.device, 'Predictor(placement=True)')
 
-    def _slack_rows(self, option):
-        """What slack needs, from the static selection: (required fp32 [T] on the device, design of each batch row as a host
-        int64 array).  Made once and shared by the options that form slacks (report=, criticality=); refuses a model whose
-        head is not the regression head."""
+    def _slacks_of(self, option):
+        """(required, row_design) for the options that form slacks (report=, criticality=); refuses a model whose head is not
+        the regression head."""
         nlabels = self.pmodel.mlp_fuse.layers[-1].out_features
         if nlabels != 1:
             raise ValueError(f'Predictor: {option} needs the regression head (nlabels = 1), the model has {nlabels} labels')
-        if self._slack is None:
-            b = self.batch
-            T = self._sel[0].numel()
-            required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
-            # sel[2] is each row's offset into the batched feature map, design index * P (DesignBatch.select)
-            design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
-            self._slack = (required, design)
-        return self._slack
+        return self.required, self.row_design
 
     @staticmethod
     def _criticality_spec(spec):
@@ -248,16 +263,15 @@ class Predictor:
         keyed-word workspace - static addresses, kept alive with the replay."""
         from . import criticality as K, placement as PL
         cells, sums, scale_log2 = bool(spec.get('cells', True)), bool(spec.get('sums', False)), int(spec.get('scale_log2', 20))
-        required, design = self._slack_rows('criticality=')
-        for i, d in enumerate(designs):
-            if not PL.has_placement(d):
-                raise ValueError(f'Predictor: criticality= needs the paths\' nodes, but design {i} carries no placement data '
-                                 f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
+        required, design = self._slacks_of('criticality=')
         b, dev = self.batch, self.device
         if cells and (b.P % 64 or b.P > PL.MAX_CELLS):
             raise ValueError(f'Predictor: criticality=dict(cells=True) needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; '
                              f'it has {b.P}')
-        placed = self._placed if self._placed is not None else PL.PlacedPaths(designs, b.node_off, dev)
+        # tables of its own feed no projection: the paths' nodes are all it reads, so neither the run form nor masks that
+        # match the stored ones are asked for
+        placed = self._placed if self._placed is not None else PL.batch_tables(designs, b, dev, 'Predictor(criticality=)',
+                                                                               projection=False)
         row_design = torch.from_numpy(design.astype(np.int32)).to(dev) if b.B > 1 else None
         N = int(b.node_off[-1])
         if sums and required.numel() * int(placed.maxlen) > K.MAX_ROW_PINS:
@@ -278,29 +292,13 @@ class Predictor:
             raise ValueError(f'Predictor: report= takes k and hist, got {sorted(unknown)}')
         b, dev = self.batch, self.device
         k, hist = int(spec.get('k', 32)), spec.get('hist')
-        required, design = self._slack_rows('report=')
+        required, design = self._slacks_of('report=')
         T = required.numel()
         ptr, rows = R.group_rows(design, b.B)
         bufs = R.ReportBuffers(b.B, k, hist, dev)
         scratch = torch.empty((R.workspace_bytes(T, b.B, k, hist) + 7) // 8, dtype=torch.int64, device=dev)
         return dict(k=k, hist=hist, required=required, design_ptr=torch.from_numpy(ptr).to(dev), design_rows=torch.from_numpy(rows).to(dev),
                     bufs=bufs, scratch=scratch, ready=False)
-    @contextlib.contextmanager
-    def _modes_kept(self):
-        """Module modes and the U-Net's statistics-per-image switch (set for the call, as TrainStep sets it for good: with it
-        a train-mode U-Net treats every design's image as the batch of one the reference feeds) back as found, also on an
-        exception."""
-        modes = [(m, m.training) for m in self._modules]
-        per = [(m, m.per_sample_stats) for m in self._per_sample]
-        try:
-            for m in self._per_sample:
-                m.per_sample_stats = True
-            yield
-        finally:
-            for m, was in per:
-                m.per_sample_stats = was
-            for m, was in modes:
-                m.training = was
 
     def _unet_is_fused_eval(self):
         """Inside frozen_statistics: the U-Net call is unet16's eval forward (19 launches, nothing written)."""
@@ -312,41 +310,27 @@ class Predictor:
         return bool(bns) and hasattr(cnn, 'inc') and all(C.bn_uses_running_stats(bn) for bn in bns) and \
             unet16.supported(cnn, self.batch.images, frozen_stats=True)
 
+    def _run_sweep(self, run):
+        """The sweep of a call (train.forward_to_head's sweep=)."""
+        if not self.incremental_active:
+            return run()
+        # dirty = fan-out of the seeds, the sweep over the dirty rows, then the seeds are spent - in this order on one
+        # stream, so a seed set by an update() after this predict() survives until the next one
+        out = run(incremental=(self.seed, self.dirty))
+        self.seed.zero_()
+        return out
+
+    def _placed_fc(self, pmap, feat):
+        """h_cnn from the pins as they are now (train.forward_to_head's project=, placement=True)."""
+        from .placement import placed_fc
+        b, fcn = self.batch, self.pmodel.fcn
+        return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks)
+
     def _launches(self):
-        from . import sweep as _sweep
-        b, g, pm_ = self.batch, self.batch.graph, self.pmodel
-        ends_d, paths_d, foff_d, _, _, lv_d = self._sel
-        g.ndata['h'] = self.h
-        cur = torch.cuda.current_stream(self.device)
-        h_gnn = None
-        if pm_.gnn is not None:
-            def sweep():
-                if not self.incremental_active:
-                    return _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone)
-                # dirty = fan-out of the seeds, the sweep over the dirty rows, then the seeds are spent - in this order on one
-                # stream, so a seed set by an update() after this predict() survives until the next one
-                out = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order, cone=self.cone,
-                                               incremental=(self.seed, self.dirty))
-                self.seed.zero_()
-                return out
-            if self.overlap:
-                self.side.wait_stream(cur)
-                with torch.cuda.stream(self.side):
-                    h_gnn = sweep()
-            else:
-                h_gnn = sweep()
-        feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
-        pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
-        if h_gnn is not None and self.overlap:
-            # joined BEFORE the masked projection, as TrainStep.forward does
-            cur.wait_stream(self.side)
-            h_gnn.record_stream(cur)
-        if self._placed is not None:
-            from .placement import placed_fc
-            h_cnn = placed_fc(self._placed, paths_d, foff_d if b.B > 1 else None, feat, pm_.fcn.weight, pm_.fcn.bias, b.masks)
-        else:
-            h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
-        pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+        b, pm_, paths_d = self.batch, self.pmodel, self._sel.paths
+        h_gnn, _, pmap, h_cnn = forward_to_head(pm_, self.cnn, b, self._sel, self.h, side=self.side, cone=self.cone, sweep=self._run_sweep,
+                                                project=self._placed_fc if self._placed is not None else None)
+        pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn)
         if self._report is not None:
             from . import report as R
             r = self._report
@@ -429,8 +413,8 @@ class Predictor:
         copy here, nothing in predict()."""
         if not self.incremental:
             raise RuntimeError('Predictor.dirty_mask(): built without incremental=True')
-        if i is not None and not 0 <= i < self.batch.B:
-            raise IndexError(f'dirty_mask: design {i} of {self.batch.B}')
+        if i is not None:
+            self._check_design(i, 'dirty_mask')
         d = self.dirty.cpu().numpy() if self.incremental_active else np.ones(self.batch.N, dtype=np.uint8)
         return d if i is None else d[self._perm[i].cpu().numpy()]
 
@@ -455,8 +439,8 @@ class Predictor:
             raise RuntimeError('Predictor.criticality(): no criticality was requested (criticality=True or dict(cells=...))')
         if not self._crit['ready']:
             raise RuntimeError('Predictor.criticality(): predict() has not run yet')
-        if i is not None and not 0 <= i < self.batch.B:
-            raise IndexError(f'criticality: design {i} of {self.batch.B}')
+        if i is not None:
+            self._check_design(i, 'criticality')
         placed = self._crit['placed']
         if self._crit['sums']:
             out = K.decode_sums(*self._crit['bufs'].host(), node_off=self.batch.node_off, scale_log2=self._crit['scale_log2'],
@@ -475,8 +459,7 @@ class Predictor:
         With incremental=True the features - whole tables as well - are written by a kernel that flags every row whose bits
         changed: the next predict() sweeps the fan-out of exactly those rows.  Images and pins flag nothing (the U-Net and the
         projection run in full anyway)."""
-        if not 0 <= i < self.batch.B:
-            raise IndexError(f'update: design {i} of {self.batch.B}')
+        self._check_design(i, 'update')
         pins = None
         if pin_x is not None or pin_y is not None:
             if self._placed is None:
@@ -484,8 +467,8 @@ class Predictor:
             if pin_x is None or pin_y is None:
                 raise ValueError('update: pin_x and pin_y go together')
             pins = self._placed.check_pins(i, pin_x, pin_y)
-        update_design(self.batch, self._perm[i], i, cell_feat, net_feat, image, rows=rows, seed=self.seed,
-                      perm32=self._perm32[i] if self._perm32 is not None else None)
+        self._update_design(i, cell_feat, net_feat, image, rows, seed=self.seed,
+                            perm32=self._perm32[i] if self._perm32 is not None else None)
         if pins is not None:
             self._placed.set_pins(i, *pins)
 
@@ -493,8 +476,7 @@ class Predictor:
         """Host (indptr, cols) int64 of design i's current path masks: rasterised from the pins as they are now with
         placement=True (synchronises), the design's stored masks otherwise."""
         b = self.batch
-        if not 0 <= i < b.B:
-            raise IndexError(f'masks: design {i} of {b.B}')
+        self._check_design(i, 'masks')
         q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
         if self._placed is not None:
             ip, cols = (t.cpu().numpy().astype(np.int64) for t in self._placed.csr())

@@ -8,6 +8,7 @@ that placement data - `path_nodes` [num_paths, maxlen] (-1 padded, the layout pr
     rasterize_host / runs_host   the mask rule and its run form in numpy (host side: attach_placement, tests, tools)
     attach_placement             validates the four arrays, sets them on a design and rebuilds its masks from them
     PlacedPaths                  the device tables of a batch of such designs; set_pins() moves a design's pins in place
+    batch_tables                 the PlacedPaths of a resident batch, with the refusals every front end makes before it uses them
     placed_fc                    the masked projection computed from those tables by mmft_placed_fc_fwd: bitwise what
                                  fusion.masked_fc gives on masks rasterised from the same pins, with nothing to rebuild
 """
@@ -22,6 +23,13 @@ MAX_CELLS = 65536          # the kernel's LDS bitmap (mmft_place.h)
 
 def has_placement(design):
     return all(getattr(design, k, None) is not None for k in FIELDS)
+
+
+def require_placement(designs, who):
+    """ValueError, prefixed with `who`, for the first design that carries no placement data.  Host only."""
+    for i, d in enumerate(designs):
+        if not has_placement(d):
+            raise ValueError(f'{who}: design {i} carries no placement data ({", ".join(FIELDS)}: placement.attach_placement)')
 
 
 def _bitmaps(path_nodes, path_lens, pin_x, pin_y, map_x, map_y):
@@ -135,9 +143,7 @@ class PlacedPaths:
     Rows follow the designs' paths one after another, as PathMasks.batch numbers them."""
 
     def __init__(self, designs, node_off, device):
-        missing = [i for i, d in enumerate(designs) if not has_placement(d)]
-        if missing:
-            raise ValueError(f'PlacedPaths: design {missing[0]} carries no placement data (placement.attach_placement)')
+        require_placement(designs, 'PlacedPaths')
         self.node_off = np.asarray(node_off, dtype=np.int64)
         if self.node_off.shape != (len(designs) + 1,) or any(int(self.node_off[i + 1] - self.node_off[i]) != int(d.N) for i, d in enumerate(designs)):
             raise ValueError('PlacedPaths: node_off must hold the designs\' node offsets')
@@ -191,6 +197,27 @@ class PlacedPaths:
         prep.rasterize_path_masks (inspection, saving; synchronises)."""
         from . import prep
         return prep.rasterize_path_masks(self.nodes, self.lens, self.loc_x, self.loc_y, self.map_x, self.map_y)
+
+
+def batch_tables(designs, batch, device, who, projection=True):
+    """The PlacedPaths of a resident batch (train.DesignBatch), or a ValueError prefixed with `who`: a design without
+    placement data; and, with projection=True - the tables then stand in for the stored masks in the masked projection
+    (placed_fc) - a map the run form does not take, and stored masks that are not the masks of the pins (the results would
+    change before a pin has moved).  projection=False: for a caller that walks the paths' nodes only (criticality)."""
+    require_placement(designs, who)
+    if projection and (not batch.masks.run_block or batch.P > MAX_CELLS):
+        raise ValueError(f'{who} needs a map of a multiple of 64 cells, at most {MAX_CELLS}; it has {batch.P}')
+    placed = PlacedPaths(designs, batch.node_off, device)
+    if projection:
+        ip, cols = (t.cpu().numpy().astype(np.int64) for t in placed.csr())
+        m = batch.masks
+        for i in range(batch.B):
+            q0, q1 = int(batch.path_off[i]), int(batch.path_off[i + 1])
+            if not (np.array_equal(ip[q0:q1 + 1], m.host_indptr[q0:q1 + 1]) and
+                    np.array_equal(cols[ip[q0]:ip[q1]], m.host_cols[ip[q0]:ip[q1]])):
+                raise ValueError(f'{who}: the stored masks of design {i} are not the masks of its pins '
+                                 '(placement.attach_placement rebuilds them)')
+    return placed
 
 
 def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None):

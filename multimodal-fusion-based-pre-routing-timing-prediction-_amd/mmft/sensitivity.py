@@ -5,8 +5,8 @@
 
 with respect to every row of cell_feat and net_feat, handed out per design in the design's own node order.
 
-What runs.  The U-Net, the masked projection and h_cnn run under no_grad exactly as in Predictor._launches: they do not
-depend on the features.  The netlist sweep runs in its training form (sweep.SweepFn keeps A / LSE / the hidden rows) and the
+What runs.  The launches and their order are train.forward_to_head's, as for Predictor.  The U-Net, the masked projection and
+h_cnn run under no_grad: they do not depend on the features.  The netlist sweep runs in its training form (sweep.SweepFn keeps A / LSE / the hidden rows) and the
 fusion head on top of it; torch.autograd.grad seeds the existing reverse sweep with w as the gradient of the predictions.
 After it the sweep's G holds, for every cell and net row, the gradient at the output of fc_cell_self / fc_net_self - the rows
 mlp2_feat_bwd_kernel reads for the weight gradients.  The last hop, through the two feature MLPs to their inputs, is
@@ -35,16 +35,13 @@ buffer, no .grad (torch.autograd.grad, not .backward()), no requires_grad flag, 
 gradient sinks (mmft.gradsink: a trainer with the fused optimizer owns it) is refused: the reverse sweep would deliver its
 weight gradients into that trainer's flat gradient buffer.
 """
-import contextlib
-
 import numpy as np
 import torch
 
 from . import gradsink, lib, ops
 from .evaluate import frozen_statistics
-from .fusion import MaskedPathMap
-from .infer import design_permutations, update_design
-from .train import DesignBatch
+from .infer import ResidentDesigns
+from .train import forward_to_head
 
 OBJECTIVES = ('tns', 'sum')
 
@@ -88,10 +85,7 @@ def check_pins_model(pmodel, cnn, designs):
     if getattr(pmodel, 'fcn', None) is None:
         raise ValueError('Sensitivity(pins=True): the model has no masked projection (pmodel.fcn is None): the predictions '
                          'do not depend on the pins\' coordinates')
-    for i, d in enumerate(designs):
-        if not PL.has_placement(d):
-            raise ValueError(f'Sensitivity(pins=True): design {i} carries no placement data '
-                             f'({", ".join(PL.FIELDS)}: placement.attach_placement)')
+    PL.require_placement(designs, 'Sensitivity(pins=True)')
 
 
 def check_pin_update(pins, image, pin_x, pin_y):
@@ -150,7 +144,7 @@ def check_weights(weights, T):
     return w
 
 
-class Sensitivity:
+class Sensitivity(ResidentDesigns):
     """Sensitivity(pmodel, cnn, designs, device).run() -> (pred, endpoints, grads).
 
     path_ids_per_design   per design the paths that are predicted and weighted (None: every path of every design); one static
@@ -182,27 +176,8 @@ class Sensitivity:
         if pins:
             check_pins_model(pmodel, cnn, designs)
         self.image, self.pins = bool(image), bool(pins)
-        self.pmodel, self.cnn = pmodel, cnn
-        self.device = torch.device(device)
-        self.frozen_stats, self.overlap = bool(frozen_stats), bool(overlap)
-        self.side = torch.cuda.Stream(device=self.device) if self.overlap else None
-        b = self.batch = DesignBatch(designs, device, pmodel.gnn.out_feat_dim)
-        if path_ids_per_design is None:
-            path_ids_per_design = [np.arange(d.num_paths) for d in designs]
-        T = int(sum(len(p) for p in path_ids_per_design))
-        if T == 0:
-            raise ValueError('Sensitivity: no path selected')
-        self.T = T
-        self._sel = b.select(path_ids_per_design)
-        self._links, self._end_order = b.links, b.end_order
-        self.endpoints = np.asarray(self._sel[4])
-        self.required = b.required[self._sel[0].long()].reshape(T).to(torch.float32).contiguous()
-        self.row_design = np.zeros(T, dtype=np.int64) if b.B == 1 else self._sel[2].cpu().numpy().astype(np.int64) // b.P
-        self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
-        self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
-        self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
-        self._per_sample = [m for m in self._modules if hasattr(m, 'per_sample_stats')]
-        nd = b.graph.ndata
+        super().__init__('Sensitivity', pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap)
+        nd = self.batch.graph.ndata
         # rows outside the (even / odd) levels are never written: zero for the life of the object
         self._dx = {k: torch.zeros_like(nd[k]) for k in ('cell_feat', 'net_feat')}
         self.feat_map = self.last_hop = self.feat_grad = None
@@ -216,38 +191,13 @@ class Sensitivity:
         kernels do not take and designs whose stored masks are not the masks of their pins (pred would then differ from
         pins=False) - what Predictor(placement=True) refuses."""
         from . import placement as PL
-        b = self.batch
-        if not b.masks.run_block or b.P > PL.MAX_CELLS:
-            raise ValueError(f'Sensitivity(pins=True) needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; it has {b.P}')
-        placed = PL.PlacedPaths(designs, b.node_off, self.device)
+        placed = PL.batch_tables(designs, self.batch, self.device, 'Sensitivity(pins=True)')
         if placed.maxlen > ops.PIN_MOVE_MAX_LEN:
             raise ValueError(f'Sensitivity(pins=True): paths of up to {ops.PIN_MOVE_MAX_LEN} nodes, the designs\' rows hold {placed.maxlen}')
-        ip, cols = (t.cpu().numpy().astype(np.int64) for t in placed.csr())
-        for i in range(b.B):
-            q0, q1 = int(b.path_off[i]), int(b.path_off[i + 1])
-            if not (np.array_equal(ip[q0:q1 + 1], b.masks.host_indptr[q0:q1 + 1]) and
-                    np.array_equal(cols[ip[q0]:ip[q1]], b.masks.host_cols[ip[q0]:ip[q1]])):
-                raise ValueError(f'Sensitivity(pins=True): the stored masks of design {i} are not the masks of its pins '
-                                 '(placement.attach_placement rebuilds them)')
         self.placed = placed
-        self._incidence = PL.pin_incidence(placed, self._sel[1])
+        self._incidence = PL.pin_incidence(placed, self._sel.paths)
         self.row_move = torch.zeros((self.T, placed.maxlen, 4), dtype=torch.float32, device=self.device)
-        self._pin_move = torch.zeros((int(b.node_off[-1]), 4), dtype=torch.float32, device=self.device)
-
-    @contextlib.contextmanager
-    def _modes_kept(self):
-        """Module modes and the U-Net's statistics-per-image switch back as found, also on an exception (Predictor._modes_kept)."""
-        modes = [(m, m.training) for m in self._modules]
-        per = [(m, m.per_sample_stats) for m in self._per_sample]
-        try:
-            for m in self._per_sample:
-                m.per_sample_stats = True
-            yield
-        finally:
-            for m, was in per:
-                m.per_sample_stats = was
-            for m, was in modes:
-                m.training = was
+        self._pin_move = torch.zeros((self.batch.N, 4), dtype=torch.float32, device=self.device)
 
     def update(self, i, cell_feat=None, net_feat=None, image=None, rows=None, pin_x=None, pin_y=None):
         """New features / a new layout image of design i, as Predictor.update (infer.update_design): the next run() sees them.
@@ -257,54 +207,46 @@ class Sensitivity:
         xy = None
         if check_pin_update(self.pins, self.image, pin_x, pin_y):
             xy = self.placed.check_pins(i, pin_x, pin_y)
-        update_design(self.batch, self._perm[i] if 0 <= i < self.batch.B else None, i, cell_feat, net_feat, image, rows=rows)
+        self._update_design(i, cell_feat, net_feat, image, rows)
         if xy is not None:
             self.placed.set_pins(i, *xy)
 
     def _forward(self):
         """pred [T] with the sweep and the head on the autograd tape; everything in front of them under no_grad - but for
         image=True: the feature map is then a leaf and the masked projection runs on the tape too."""
-        from . import sweep as _sweep
-        b, g, pm_ = self.batch, self.batch.graph, self.pmodel
-        ends_d, paths_d, foff_d, _, _, lv_d = self._sel
-        g.ndata['h'] = self.h
-        cur = torch.cuda.current_stream(self.device)
-        sweep = lambda: _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=self._end_order)
-        with torch.enable_grad():
-            if self.overlap:
-                self.side.wait_stream(cur)
-                with torch.cuda.stream(self.side):
-                    h_gnn = sweep()
-            else:
-                h_gnn = sweep()
-        st = g._sweep
+        b, pm_, sel = self.batch, self.pmodel, self._sel
         self._tape = None
-        with torch.set_grad_enabled(self.image):
-            if self.image:
+
+        def sweep(run):
+            with torch.enable_grad():
+                return run()
+
+        def features():
+            with torch.set_grad_enabled(self.image):
+                if not self.image:
+                    return self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
                 from . import unet16
                 with torch.no_grad():
                     out, self._tape = unet16.unet_forward_eval_taped(self.cnn, b.images)
-                feat = out.reshape(b.B, -1).requires_grad_(True)
-            else:
-                feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
-            pmap = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *self._links) if feat is not None else None
-            if self.overlap:
-                # joined BEFORE the masked projection, as TrainStep.forward does (DESIGN 3.7)
-                cur.wait_stream(self.side)
-                h_gnn.record_stream(cur)
-            if self.pins and not self.image:
+                return out.reshape(b.B, -1).requires_grad_(True)
+
+        def project(pmap, feat):
+            with torch.set_grad_enabled(self.image):
+                if not self.pins or self.image:
+                    return pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
                 # the masks of the pins as they are now: bitwise masked_fc on masks rasterised from them (placement.placed_fc)
                 from .placement import placed_fc
-                h_cnn = placed_fc(self.placed, paths_d, foff_d if b.B > 1 else None, feat, pm_.fcn.weight, pm_.fcn.bias, b.masks)
-            else:
-                h_cnn = pm_._fcn(pmap) if (pmap is not None and pm_.fcn is not None) else None
-        if self.pins and not self.image:
-            h_cnn.requires_grad_(True)                    # a leaf of the tape: autograd.grad hands back the gradient at it
+                h_cnn = placed_fc(self.placed, sel.paths, sel.feat_off if b.B > 1 else None, feat, pm_.fcn.weight, pm_.fcn.bias, b.masks)
+            return h_cnn.requires_grad_(True)             # a leaf of the tape: autograd.grad hands back the gradient at it
+
+        h_gnn, feat, pmap, h_cnn = forward_to_head(pm_, self.cnn, b, sel, self.h, side=self.side, sweep=sweep, features=features,
+                                                   project=project)
+        st = b.graph._sweep
         self._proj = h_cnn if self.pins else None
         self.feat_map = feat.detach() if self.image else feat
         self._feat_leaf = feat if self.image else None
         with torch.enable_grad():
-            pred = pm_.fuse_heads(h_gnn, pmap, lv_d, b.L, h_cnn=h_cnn)
+            pred = pm_.fuse_heads(h_gnn, pmap, sel.levels, b.L, h_cnn=h_cnn)
         return pred, st
 
     def _last_hop(self, st):
@@ -334,7 +276,7 @@ class Sensitivity:
         """proj_grad -> row_move -> pin_move (include/mmft_sens_pins.h): two launches on the current stream."""
         from . import fusion
         b, placed = self.batch, self.placed
-        _, paths_d, foff_d = self._sel[:3]
+        paths_d, foff_d = self._sel.paths, self._sel.feat_off
         self._proj = None
         if g is None:
             raise RuntimeError('Sensitivity(pins=True): the predictions do not depend on the masked projection')

@@ -58,7 +58,34 @@ def parameter_buckets(pmodel, cnn):
     return [('head', head), ('gnn+cnn', rest)]
 
 
-_JOIN_LATE = os.environ.get('MMFT_JOIN_LATE') == '1'      # see TrainStep.forward
+_JOIN_LATE = os.environ.get('MMFT_JOIN_LATE') == '1'      # see forward_to_head
+
+
+class Selection:
+    """The sampled paths of one mini-batch, bucketed by level (DesignBatch.select); nothing about it is kept on the batch.
+    On the device, int32 views of ONE packed buffer (select(static=): the caller's, at fixed offsets): per row `ends` (the
+    endpoint's renumbered node id), `paths` (global path id), `feat_off` (design * P, the offset into the batched feature
+    map) and `levels`; `links` = (first [num_paths], next [T]), fusion.batch_links of paths; `end_order`, the rows grouped by
+    endpoint (deterministic gradient scatter).  On the host: `counts` (rows per level), `endpoints` (caller's numbering),
+    `design` (int64 [T]), `ends_unique` (no endpoint sampled twice), `T`.
+    Iterating or indexing [0..5] yields (ends, paths, feat_off, counts, endpoints, levels), the tuple select() used to return."""
+    __slots__ = ('ends', 'paths', 'feat_off', 'counts', 'endpoints', 'levels', 'links', 'end_order', 'ends_unique', 'T', 'design')
+
+    def __init__(self, dev, T, counts, endpoints, design, ends_unique):
+        self.ends, self.paths, self.feat_off, self.levels = dev[0:T], dev[T:2 * T], dev[2 * T:3 * T], dev[3 * T:4 * T]
+        self.links, self.end_order = (dev[6 * T:], dev[4 * T:5 * T]), dev[5 * T:6 * T]
+        self.counts, self.endpoints, self.design, self.ends_unique, self.T = counts, endpoints, design, ends_unique, T
+
+    def __iter__(self):
+        return iter((self.ends, self.paths, self.feat_off, self.counts, self.endpoints, self.levels))
+
+    def __getitem__(self, i):
+        return tuple(self)[i]
+
+    def required_times(self, batch):
+        """The rows' required times from batch.required: contiguous fp32 [T] on the device (one gather)."""
+        return batch.required[self.ends.long()].reshape(self.T).to(torch.float32).contiguous()
+
 
 class DesignBatch:
     """B designs resident on the device, merged block-diagonally."""
@@ -134,7 +161,8 @@ class DesignBatch:
 
     def select(self, path_ids_per_design, static=None):
         """Bucket the sampled paths by level (src/train.py:476-484); order inside a level = design, then
-        order of appearance.  One host->device copy for the whole step."""
+        order of appearance.  One host->device copy for the whole step (static: into that int32 device buffer of 6 * T +
+        num_paths elements, where a replayed graph reads it), nothing else launched; the batch stays as it was."""
         gp = np.concatenate([np.asarray(p, dtype=np.int64) + self.path_off[i]
                              for i, p in enumerate(path_ids_per_design)])
         lv = self.path2level[gp]
@@ -145,8 +173,9 @@ class DesignBatch:
         first, nxt = batch_links(gp, self.path2level.shape[0])
         T = gp.shape[0]
         eorder = np.argsort(ends, kind='stable')       # batch rows grouped by endpoint: deterministic gradient scatter
-        self.ends_unique = bool(T < 2 or (np.diff(ends[eorder]) != 0).all())
-        packed = np.concatenate([ends, gp, self.path2design[gp] * self.P, lv, nxt, eorder, first]).astype(np.int32)
+        ends_unique = bool(T < 2 or (np.diff(ends[eorder]) != 0).all())
+        design = self.path2design[gp]
+        packed = np.concatenate([ends, gp, design * self.P, lv, nxt, eorder, first]).astype(np.int32)
         if static is not None:
             if static.numel() != packed.shape[0]:
                 raise ValueError('graph replay needs a constant number of sampled paths per step')
@@ -155,9 +184,7 @@ class DesignBatch:
             dev = static
         else:
             dev = torch.from_numpy(packed).to(self.device)
-        self.links = (dev[6 * T:], dev[4 * T:5 * T])
-        self.end_order = dev[5 * T:6 * T]
-        return dev[0:T], dev[T:2 * T], dev[2 * T:3 * T], counts, self.old_of_new[ends], dev[3 * T:4 * T]
+        return Selection(dev, T, counts, self.old_of_new[ends], design, ends_unique)
 
     STAGING_SLOTS = 4
 
@@ -185,6 +212,57 @@ class DesignBatch:
         ev.record(torch.cuda.current_stream(self.device))
         st['events'][k] = ev
         st['i'] += 1
+
+
+def forward_to_head(pmodel, cnn, batch, sel, h, side=None, cone=False, join_late=False, sweep=None, features=None, project=None):
+    """A resident batch from a Selection up to the fusion head: (h_gnn, feat, pmap, h_cnn); the caller calls
+    pmodel.fuse_heads(h_gnn, pmap, sel.levels, batch.L, h_cnn=h_cnn) itself.  THE one place that orders these launches:
+    TrainStep.forward (sweep mode), Predictor.predict and Sensitivity.run come through here; GraphedTrainStep's pieces=True
+    capture cuts the same sequence at its two tape boundaries (_capture_pieces).
+    side: the HIP stream the sweep runs on underneath the U-Net (None: the current one); cone: for sweep_forward_all;
+    join_late: MMFT_JOIN_LATE, honoured only for the caller that passes it (TrainStep, which tools/packed_fma_repro.py
+    drives) - Predictor and Sensitivity always join first.  What differs between the callers, each defaulting to TrainStep's:
+    sweep(run) -> h_gnn, called on the sweep's stream, run(**kw) being the sweep_forward_all call of this selection;
+    features() -> the feature map [B, P] or None; project(pmap, feat) -> h_cnn."""
+    from . import sweep as _sweep
+    b, g = batch, batch.graph
+    # (whole-sweep entry: the *_self MLPs store every level node's row before anything reads it - no 268 MB fill)
+    g.ndata['h'] = h
+    # The netlist sweep and the U-Net are independent until the fusion head: the level-serial sweep
+    # (many small, latency-bound launches) runs on a side HIP stream underneath the CNN's large kernels.
+    cur = torch.cuda.current_stream(b.device)
+    h_gnn = None
+    if pmodel.gnn is not None:
+        run = lambda **kw: _sweep.sweep_forward_all(pmodel.gnn, g, b.level_nodes, sel.ends, target_order=sel.end_order,
+                                                    cone=cone, **kw)
+        if side is not None:
+            side.wait_stream(cur)
+        with torch.cuda.stream(side):                # (None: a no-op)
+            h_gnn = run() if sweep is None else sweep(run)
+    if features is not None:
+        feat = features()
+    else:
+        feat = cnn(b.images).reshape(b.B, -1) if cnn is not None else None
+    pmap = MaskedPathMap(b.masks, sel.paths, feat, sel.feat_off if b.B > 1 else None, *sel.links) if feat is not None else None
+    # The sweep stream is joined BEFORE the masked projection.  Issued ahead of the join (it needs only the CNN output)
+    # the projection's kernels ran beside the sweep's last launches, and in a replayed graph its prefix kernel then lost
+    # one term in ~5 % of the launches - a wrong result of one packed-fma form under that co-residency, not a data race
+    # (csrc/common.h MMFT_NO_PACKED_F32, DESIGN 3.7).  The kernel no longer contains the form; the join stays first
+    # because it is free: the sweep finishes before the U-Net anyway (tools/step_timeline.py).  MMFT_JOIN_LATE=1
+    # restores the old order for tools/packed_fma_repro.py.
+    def join():
+        if h_gnn is not None and side is not None:
+            cur.wait_stream(side)
+            h_gnn.record_stream(cur)
+    if not join_late:
+        join()
+    if project is not None:
+        h_cnn = project(pmap, feat)
+    else:
+        h_cnn = pmodel._fcn(pmap) if (pmap is not None and pmodel.fcn is not None) else None
+    if join_late:
+        join()
+    return h_gnn, feat, pmap, h_cnn
 
 
 class TrainStep:
@@ -255,45 +333,16 @@ class TrainStep:
     # ---------------------------------------------------------------- forward of one mini-batch
     def forward(self, path_ids_per_design, _sel=None):
         b, g = self.batch, self.batch.graph
-        ends_d, paths_d, foff_d, counts, ends_h, lv_d = _sel if _sel is not None else b.select(path_ids_per_design)
-        if self.mode != 'sweep':
-            self.h.zero_()                                                                # src/train.py:342,559
-        # (whole-sweep entry: the *_self MLPs store every level node's row before anything reads it - no 268 MB fill)
-        g.ndata['h'] = self.h
+        sel = _sel if _sel is not None else b.select(path_ids_per_design)
         if self.mode == 'sweep':
-            # The netlist sweep and the U-Net are independent until the fusion head: the level-serial sweep
-            # (many small, latency-bound launches) runs on a side HIP stream underneath the CNN's large kernels.
-            from . import sweep as _sweep
-            cur = torch.cuda.current_stream(self.device)
-            h_gnn = None
-            if self.pmodel.gnn is not None:
-                if self.overlap:
-                    self.side.wait_stream(cur)
-                    with torch.cuda.stream(self.side):
-                        h_gnn = _sweep.sweep_forward_all(self.pmodel.gnn, g, b.level_nodes, ends_d,
-                                                         target_order=b.end_order, cone=self.cone)
-                else:
-                    h_gnn = _sweep.sweep_forward_all(self.pmodel.gnn, g, b.level_nodes, ends_d, target_order=b.end_order,
-                                                     cone=self.cone)
-            feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None
-            pm = MaskedPathMap(b.masks, paths_d, feat, foff_d if b.B > 1 else None, *b.links) \
-                if feat is not None else None
-            # The sweep stream is joined BEFORE the masked projection.  Issued ahead of the join (it needs only the CNN output)
-            # the projection's kernels ran beside the sweep's last launches, and in a replayed graph its prefix kernel then lost
-            # one term in ~5 % of the launches - a wrong result of one packed-fma form under that co-residency, not a data race
-            # (csrc/common.h MMFT_NO_PACKED_F32).  The kernel no longer contains the form; the join stays first
-            # because it is free: the sweep finishes before the U-Net anyway (tools/step_timeline.py).  MMFT_JOIN_LATE=1
-            # restores the old order for tools/packed_fma_repro.py.
-            if h_gnn is not None and self.overlap and not _JOIN_LATE:
-                cur.wait_stream(self.side)
-                h_gnn.record_stream(cur)
-            h_cnn = self.pmodel._fcn(pm) if (pm is not None and self.pmodel.fcn is not None) else None
-            if h_gnn is not None and self.overlap and _JOIN_LATE:
-                cur.wait_stream(self.side)
-                h_gnn.record_stream(cur)
-            return self.pmodel.fuse_heads(h_gnn, pm, lv_d, b.L, h_cnn=h_cnn), ends_d, ends_h
+            h_gnn, _, pm, h_cnn = forward_to_head(self.pmodel, self.cnn, b, sel, self.h, side=self.side, cone=self.cone,
+                                                  join_late=_JOIN_LATE)
+            return self.pmodel.fuse_heads(h_gnn, pm, sel.levels, b.L, h_cnn=h_cnn), sel.ends, sel.endpoints
+        ends_d, paths_d, foff_d, counts = sel.ends, sel.paths, sel.feat_off, sel.counts
+        self.h.zero_()                                                                    # src/train.py:342,559
+        g.ndata['h'] = self.h
         feat = self.cnn(b.images).reshape(b.B, -1) if self.cnn is not None else None      # src/train.py:465,562
-        g.targets_unique = b.ends_unique      # host knowledge: no repeated endpoint -> one exact atomic add per element
+        g.targets_unique = sel.ends_unique    # host knowledge: no repeated endpoint -> one exact atomic add per element
         hats, pos = [], 0
         for level_id in range(b.L):                                                       # src/train.py:490-511
             k = int(counts[level_id])
@@ -309,12 +358,12 @@ class TrainStep:
                 path_map = MaskedPathMap(b.masks, paths_d[pos:pos + k], feat, foff_d[pos:pos + k] if b.B > 1 else None)
                 # the step's link lists (all levels, in level order) for the deferred head, which differentiates all levels
                 # as one batch: without them it derives the lists from a device-to-host copy of the rows
-                path_map.batch_links, path_map.batch_rows = b.links, (pos, paths_d.numel())
+                path_map.batch_links, path_map.batch_rows = sel.links, (pos, paths_d.numel())
             cur = self.pmodel(g, b.level_nodes[level_id], None, targets, level_id, b.level_th[level_id], path_map)
             pos += k
             if cur is not None:
                 hats.append(cur)
-        return torch.cat(hats, 0), ends_d, ends_h
+        return torch.cat(hats, 0), ends_d, sel.endpoints
 
     def _sparse_masks(self):
         """path_masks as the reference stores them: sparse COO (num_paths, P) with int64 ones
@@ -415,8 +464,7 @@ class GraphedTrainStep:
         import gc
         gc.collect()
         torch.cuda.synchronize()
-        sel = b.select(example_path_ids)
-        T = sel[0].numel()
+        T = int(sum(len(p) for p in example_path_ids))
         self.static_idx = torch.zeros(6 * T + b.path2level.shape[0], dtype=torch.int32, device=ts.device)
         self.T = T
         sel = b.select(example_path_ids, static=self.static_idx)
@@ -446,7 +494,6 @@ class GraphedTrainStep:
         from . import sweep as _sweep
         ts, b = self.ts, self.ts.batch
         pm_, cnn, g = ts.pmodel, ts.cnn, ts.batch.graph
-        ends_d, paths_d, foff_d, counts, ends_h, lv_d = sel
         skip = ('gnn.fc_net_drive.', 'gnn.fc_attn2.')
         named = [(n, p) for n, p in pm_.named_parameters() if not n.startswith(skip)]
         head_params = [p for n, p in named if not n.startswith(('gnn.', 'cnn.'))]
@@ -458,15 +505,15 @@ class GraphedTrainStep:
         kw = dict(pool=pool, capture_error_mode='thread_local')
         g.ndata['h'] = ts.h
         with torch.cuda.graph(self.gA, stream=ts.side, **kw):                       # A: netlist sweep forward
-            h_out = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, ends_d, target_order=b.end_order, cone=ts.cone)
+            h_out = _sweep.sweep_forward_all(pm_.gnn, g, b.level_nodes, sel.ends, target_order=sel.end_order, cone=ts.cone)
             h_leaf = h_out.detach().requires_grad_(True)
         with torch.cuda.graph(self.gB, **kw):                                       # B: U-Net forward
             feat_out = cnn(b.images).reshape(b.B, -1)
             feat_leaf = feat_out.detach().requires_grad_(True)
         with torch.cuda.graph(self.gH, **kw):                                       # H: head forward, loss, head backward
-            pmap = MaskedPathMap(b.masks, paths_d, feat_leaf, foff_d if b.B > 1 else None, *b.links)
-            hats = pm_.fuse_heads(h_leaf, pmap, lv_d, b.L, h_cnn=pm_._fcn(pmap))
-            loss = ts.loss(hats, ends_d)
+            pmap = MaskedPathMap(b.masks, sel.paths, feat_leaf, sel.feat_off if b.B > 1 else None, *sel.links)
+            hats = pm_.fuse_heads(h_leaf, pmap, sel.levels, b.L, h_cnn=pm_._fcn(pmap))
+            loss = ts.loss(hats, sel.ends)
             ts.optim.zero_grad()
             torch.autograd.backward(loss, inputs=head_params + [h_leaf, feat_leaf])
             self.loss, self.hats = loss.detach(), hats.detach()
@@ -482,14 +529,14 @@ class GraphedTrainStep:
         host synchronisation: the host may run ahead of the device (the staging slots bound it)."""
         ts, b = self.ts, self.ts.batch
         sel = b.select(path_ids_per_design, static=self.static_idx)
-        ts.last_ends = sel[0]
+        ts.last_ends = sel.ends
         if not self.pieces:
             self.graph.replay()
             if ts.reducer is not None:
                 ts.reducer.after_replay()        # per bucket: all-reduce + Adam on the communication stream
             else:
                 ts.optim.note_replay()
-            return self.loss, self.hats, sel[4].tolist()
+            return self.loss, self.hats, sel.endpoints.tolist()
         main, side = torch.cuda.current_stream(ts.device), ts.side
         e0, eA, eH, ebA = self._ev[:4]
         e0.record(main)                          # the endpoint indices are in place (and the previous step's Adam is done)
@@ -513,7 +560,7 @@ class GraphedTrainStep:
             ts.reducer.reduce_rest_and_join(main)
         else:
             ts.optim.step()
-        return self.loss, self.hats, sel[4].tolist()
+        return self.loss, self.hats, sel.endpoints.tolist()
 
     def time_pieces(self, reps=10):
         """Diagnostic: every piece replayed ALONE on the stream it is assigned to (ms each), plus A | B and bA | bB

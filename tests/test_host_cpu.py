@@ -164,7 +164,7 @@ def test_design_batch_select_order():
     assert ends.tolist() == [int(ds[i].path2endpoint[p] + b.node_off[i]) for (_, i, _, p) in exp]
     assert foff.tolist() == [i * b.P for (_, i, _, _) in exp] and lv.tolist() == [l for (l, _, _, _) in exp]
     assert counts.sum() == 6 and len(b.level_nodes) == 8
-    first, nxt = b.links
+    first, nxt = b.select(ids).links
     assert first.numel() == b.path_off[-1] and nxt.numel() == 6
     # the renumbering is internal: ids handed back are unchanged
     r = DesignBatch(ds, 'cpu', renumber=True)
@@ -178,6 +178,39 @@ def test_design_batch_select_order():
     assert torch.equal(r.graph.ndata['cell_feat'], b.graph.ndata['cell_feat'][torch.from_numpy(r.old_of_new)])
     src, dst = r.graph._coo['net']
     assert sorted(zip(r.old_of_new[src].tolist(), r.old_of_new[dst].tolist())) == sorted(zip(*[a.tolist() for a in b.graph._coo['net']]))
+
+
+def test_selection_carries_its_own_state_and_outlives_the_next_select():
+    """DesignBatch.select returns a Selection: the six legacy items under names, the rows' design on the host, and the link
+    lists / endpoint order / uniqueness flag that used to live on the batch - a later select() on the same batch leaves them."""
+    from mmft.train import DesignBatch, Selection
+    ds = [synth_design(N=512, L=8, tile=16, seed=10 + i, end_frac=0.5) for i in range(2)]
+    b = DesignBatch(ds, 'cpu')
+    ids = [[5, 0, 7, 0], [1, 3]]
+    sel = b.select(ids)
+    assert isinstance(sel, Selection) and sel.T == 6 and len(list(sel)) == 6
+    ends, paths, foff, counts, ends_h, lv = sel
+    for named, legacy, k in ((sel.ends, ends, 0), (sel.paths, paths, 1), (sel.feat_off, foff, 2), (sel.counts, counts, 3),
+                             (sel.endpoints, ends_h, 4), (sel.levels, lv, 5)):
+        assert named is legacy and np.array_equal(np.asarray(sel[k]), np.asarray(legacy))
+    assert isinstance(sel.design, np.ndarray) and sel.design.dtype == np.int64
+    assert sel.design.tolist() == (sel.feat_off.numpy().astype(np.int64) // b.P).tolist() and set(sel.design.tolist()) == {0, 1}
+    assert sel.ends_unique is False and b.select([[5, 0, 7], [1, 3]]).ends_unique is True
+    req = sel.required_times(b)
+    assert req.dtype == torch.float32 and req.is_contiguous() and tuple(req.shape) == (6,)
+    assert torch.equal(req, b.required[sel.ends.long()].reshape(6))
+    one = DesignBatch(ds[:1], 'cpu').select([[5, 0, 7, 0]])
+    assert one.design.tolist() == [0, 0, 0, 0] and one.design.dtype == np.int64
+    # a second selection of other paths on the same batch: the first one's state stays, element for element
+    kept = (sel.links[0].clone(), sel.links[1].clone(), sel.end_order.clone(), sel.ends_unique)
+    other = b.select([[2, 4, 6, 9], [0, 8]])
+    assert not torch.equal(other.links[0], kept[0])
+    assert torch.equal(sel.links[0], kept[0]) and torch.equal(sel.links[1], kept[1]) and torch.equal(sel.end_order, kept[2])
+    assert sel.ends_unique is kept[3] is False
+    assert sel.links[0].tolist() == batch_links(sel.paths.tolist(), int(b.path_off[-1]))[0].tolist()
+    assert sel.links[1].tolist() == batch_links(sel.paths.tolist(), int(b.path_off[-1]))[1].tolist()
+    assert sel.end_order.tolist() == np.argsort(sel.ends.numpy(), kind='stable').tolist()
+    assert not hasattr(b, 'links') and not hasattr(b, 'end_order') and not hasattr(b, 'ends_unique')
 
 
 def test_design_record_roundtrip_and_reference_tuple_converter(tmp_path):

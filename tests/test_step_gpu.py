@@ -453,6 +453,49 @@ def test_cone_pruning_inside_the_training_step(dev):
     assert tl == res[True][5] and rel_err(res[True][0], h_o) < 1e-4
 
 
+@pytest.mark.parametrize('mode', ['sweep', 'dropin'])
+@pytest.mark.parametrize('math', ['bf16', 'f32'])
+def test_a_selection_is_not_disturbed_by_a_later_select_on_its_batch(dev, mode, math):
+    """forward(None, _sel=sel_a) takes everything from sel_a - rows, link lists, endpoint order, the uniqueness flag - also
+    when the batch has selected other paths since: predictions and every parameter gradient are bitwise those of the run
+    without the second select().  ids_a holds one path twice (a repeated endpoint: the ordered scatter and, in drop-in mode,
+    targets_unique matter); ids_b holds as many paths per design, so that a stale index would still be in range.
+    Before Selection the link lists, the endpoint order and the flag lived on the batch and the LAST select() won: only the
+    backward passes read them, so the predictions agreed and, in sweep mode, 63 parameter gradients did not (both math modes;
+    the drop-in cases passed there too: profiles/resident_forward_config_b.txt)."""
+    from mmft import lib
+    from mmft.synth import synth_design
+    from mmft.train import build_models, TrainStep
+    designs = [synth_design(N=2048, L=12, tile=32, seed=640 + i, end_frac=0.25) for i in range(2)]
+    rng = np.random.default_rng(21)
+    perms = [rng.permutation(d.num_paths) for d in designs]
+    n = 24
+    ids_a = [p[:n].copy() for p in perms]
+    ids_a[0][n - 1] = ids_a[0][0]                                   # one path twice
+    ids_b = [p[n:2 * n] for p in perms]                             # other paths, the same number per design
+    assert all(len(a) == len(b) == n and not set(a) & set(b) for a, b in zip(ids_a, ids_b))
+
+    def run(select_between):
+        pmodel, cnn = build_models(map_size=designs[0].map_size, device=dev, seed=11)
+        ts = TrainStep(pmodel, cnn, designs, dev, mode=mode, overlap=False, with_optimizer=False)
+        sel_a = ts.batch.select(ids_a)
+        assert len(set(sel_a[0].tolist())) == 2 * n - 1             # a repeated endpoint ...
+        if select_between:
+            assert len(set(ts.batch.select(ids_b)[0].tolist())) == 2 * n        # ... and none in the selection made after it
+        hats, ends_d, _ = ts.forward(None, _sel=sel_a)
+        ts.loss(hats, ends_d).backward()
+        torch.cuda.synchronize()
+        grads = {f'{root}.{k}': p.grad.clone() for root, m in (('pmodel', pmodel), ('cnn', cnn)) for k, p in m.named_parameters()
+                 if p.grad is not None}
+        return hats.detach().clone(), grads
+
+    with lib.math_mode(math):
+        (hats_a, grads_a), (hats_b, grads_b) = run(False), run(True)
+    assert len(grads_a) > 50 and sorted(grads_a) == sorted(grads_b)
+    assert torch.equal(hats_a, hats_b)
+    assert [k for k in grads_a if not torch.equal(grads_a[k], grads_b[k])] == []
+
+
 @pytest.mark.parametrize('graphed', [False, True])
 def test_adam_clearing_consumed_gradients_equals_zero_grad(dev, graphed):
     """TrainStep(keep_grads=False) - the bench's setting: the fused Adam launch clears the gradients it consumed instead of a
