@@ -243,14 +243,13 @@ __global__ void __launch_bounds__(256) bn_eval_kernel(const float* __restrict__ 
                                                       float eps, int C, long long total, int relu) {
   const long long stride = (long long)gridDim.x * blockDim.x * VEC;
   long long i = ((long long)blockIdx.x * blockDim.x + threadIdx.x) * VEC;
-  auto invstd_of = [&](int c) { return __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(running_var[c], eps))); };
   if (VEC == 4 && stride % C == 0) {
     if (i >= total) return;
     const int c = (int)(i % C);
     float mu[4], is[4], ga[4], be[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      mu[j] = running_mean[c + j]; is[j] = invstd_of(c + j); ga[j] = gamma[c + j]; be[j] = beta[c + j];
+      mu[j] = running_mean[c + j]; is[j] = bn_frozen_invstd(running_var[c + j], eps); ga[j] = gamma[c + j]; be[j] = beta[c + j];
     }
     for (; i + stride < total; i += 2 * stride) {                // two independent 16-byte streams per thread
       f32x4 v0 = *reinterpret_cast<const f32x4*>(x + i), v1 = *reinterpret_cast<const f32x4*>(x + i + stride);
@@ -280,12 +279,12 @@ __global__ void __launch_bounds__(256) bn_eval_kernel(const float* __restrict__ 
       f32x4 v = *reinterpret_cast<const f32x4*>(x + i);
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        const float t = bn_affine(v[j], running_mean[c + j], invstd_of(c + j), gamma[c + j], beta[c + j]);
+        const float t = bn_affine(v[j], running_mean[c + j], bn_frozen_invstd(running_var[c + j], eps), gamma[c + j], beta[c + j]);
         v[j] = (relu && !(t > 0.f)) ? 0.f : t;
       }
       *reinterpret_cast<f32x4*>(y + i) = v;
     } else {
-      const float t = bn_affine(x[i], running_mean[c], invstd_of(c), gamma[c], beta[c]);
+      const float t = bn_affine(x[i], running_mean[c], bn_frozen_invstd(running_var[c], eps), gamma[c], beta[c]);
       y[i] = (relu && !(t > 0.f)) ? 0.f : t;
     }
   }

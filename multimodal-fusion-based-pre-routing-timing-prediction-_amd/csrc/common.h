@@ -127,6 +127,10 @@ inline int ew_grid(long long work_items, int block = 256) {
   return (int)g;
 }
 
+// 1 / sqrt(running_var + eps) of a BatchNorm in eval mode: every step rounded to fp32 (add, square root, division), the ONE
+// sequence of the eval forwards (cnn.hip, unet16_conv.hip) and of the backward that must form the forward's bits again
+__device__ __forceinline__ float bn_frozen_invstd(float rvar, float eps) { return __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(rvar, eps))); }
+
 // slab reductions (linear.hip): partial results written by the workgroups of a split kernel, added in a fixed order
 struct SlabSeg {
   const float* slabs;

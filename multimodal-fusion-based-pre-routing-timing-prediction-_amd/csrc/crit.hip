@@ -9,10 +9,9 @@
 // Three launches on one stream:
 //   crit_init_kernel     the keyed words (workspace) to "none", the counts (outputs) to zero
 //   crit_scatter_kernel  one workgroup of 256 threads per batch row: slack, the pins of the path (<= maxlen 8-byte atomics),
-//                        and - with the cell outputs - the row's mask as a bitmap in LDS
-//                        (the box loop of placed_fc_fwd_kernel, place.hip, restated here: ~35 lines duplicated, so that that
-//                        kernel stays byte for byte what it is), then one atomic per set bit, a wave on the 64 consecutive
-//                        cells of one bitmap block at a time, empty blocks skipped
+//                        and - with the cell outputs - the row's mask as a bitmap in LDS (mask_raster_path, mask_rule.h: the
+//                        function placed_fc_fwd_kernel, place.hip, builds its bitmap with), then one atomic per set bit, a
+//                        wave on the 64 consecutive cells of one bitmap block at a time, empty blocks skipped
 //                        The designs' minima and row counts come from the first T / 1024 workgroups, each for 1024 rows,
 //                        combined in LDS (crit_design_words)
 //   crit_decode_kernel   keyed words -> node_slack / node_row / node_crit, cell_slack
@@ -23,6 +22,7 @@
 // same walk over the pins and the same bitmap - and sums the quanta and the saturated rows per design through the LDS
 // combine of crit_design_words; its decode kernel forms the shares in one fp64 division each.
 #include "common.h"
+#include "mask_rule.h"
 #include "slack_key.h"
 #include "../../include/mmft_crit.h"
 #include "../../include/mmft_crit_sums.h"
@@ -32,7 +32,6 @@ namespace mmft {
 typedef unsigned long long crit_u64;
 
 constexpr int CRIT_THREADS = 256;
-constexpr int CRIT_MAX_CELLS = 65536;         // bitmap 8 KB in LDS: the limit of mmft_placed_fc_fwd
 constexpr int CRIT_ROWS = 1024;               // rows whose per-design words one workgroup combines in LDS
 constexpr int CRIT_LDS_DESIGNS = 256;         // ... for the designs below this
 constexpr int CRIT_MAX_GRID = 8192;           // the init and decode kernels stride over their elements
@@ -183,9 +182,9 @@ __device__ void crit_design_words(const CritArgs& a, unsigned* lds) {
 
 template <bool SUMS>
 __global__ void __launch_bounds__(CRIT_THREADS) crit_scatter_kernel(CritArgs a) {
-  __shared__ __attribute__((aligned(8))) unsigned bits[CRIT_MAX_CELLS / 32];
-  static_assert(6 * CRIT_LDS_DESIGNS <= CRIT_MAX_CELLS / 32, "the per-design words borrow the bitmap");
-  __shared__ int pin_x[256], pin_y[256];
+  __shared__ __attribute__((aligned(8))) unsigned bits[MASK_MAX_CELLS / 32];
+  static_assert(6 * CRIT_LDS_DESIGNS <= MASK_MAX_CELLS / 32, "the per-design words borrow the bitmap");
+  __shared__ int pin_x[CRIT_THREADS], pin_y[CRIT_THREADS];
   const int t = blockIdx.x, tid = threadIdx.x;
   // the first T / CRIT_ROWS (rounded up) workgroups also carry a slice of the per-design words (the grid has T workgroups)
   if ((long long)blockIdx.x * CRIT_ROWS < a.T) crit_design_words<SUMS>(a, bits);
@@ -215,44 +214,11 @@ __global__ void __launch_bounds__(CRIT_THREADS) crit_scatter_kernel(CritArgs a) 
     }
   }
   if (a.P == 0) return;
-  // ---- the mask: the union of boxes as placed_fc_fwd_kernel (place.hip) builds it - THE MASK RULE of mmft_place.h
-  const int map_x = a.map_x, map_y = a.map_y, words = a.P >> 5, nblk = a.P >> 6;
+  // ---- the mask: THE MASK RULE of mmft_place.h, staged (mask_rule.h); a node id outside the contract is never read through
+  const int words = a.P >> 5, nblk = a.P >> 6;
   if (len < 2) return;                                                     // an empty mask
   for (int w = tid; w < words; w += CRIT_THREADS) bits[w] = 0u;
-  for (int j0 = 0; j0 + 1 < len; j0 += 255) {                              // chunks overlap by the node two boxes share
-    const int n = len - j0 < 256 ? len - j0 : 256;
-    __syncthreads();                                                       // bitmap zeroed / the previous chunk's boxes read
-    if (tid < n) {
-      int p = path[j0 + tid];
-      p = p < 0 ? 0 : (p >= a.N ? a.N - 1 : p);                            // outside the contract; never read through
-      pin_x[tid] = a.loc_x[p];
-      pin_y[tid] = a.loc_y[p];
-    }
-    __syncthreads();
-    for (int j = 0; j + 1 < n; ++j) {
-      int xa = pin_x[j], ya = pin_y[j], xb = pin_x[j + 1], yb = pin_y[j + 1];
-      int x1 = xa < xb ? xa : xb, x2 = xa < xb ? xb : xa;
-      int y1 = ya < yb ? ya : yb, y2 = ya < yb ? yb : ya;
-      x1 = x1 < 0 ? 0 : x1;
-      y1 = y1 < 0 ? 0 : y1;
-      x2 = x2 >= map_x ? map_x - 1 : x2;
-      y2 = y2 >= map_y ? map_y - 1 : y2;
-      int w = y2 - y1 + 1, hgt = x2 - x1 + 1;
-      if (w <= 0 || hgt <= 0) continue;
-      // a box row is the contiguous bit range [x * map_y + y1, x * map_y + y2]: whole-word masks, not one atomic per cell
-      const int wpr = ((w + 30) >> 5) + 1;                                 // words a row's range can touch
-      for (int c = tid; c < hgt * wpr; c += CRIT_THREADS) {
-        int row = c / wpr, k = c - row * wpr;
-        int lo = (x1 + row) * map_y + y1, hi = lo + w - 1;                 // inclusive bit range, inside [0, P) after the clamps
-        int wd = (lo >> 5) + k;
-        if (wd > (hi >> 5)) continue;
-        int b0 = wd == (lo >> 5) ? (lo & 31) : 0;
-        int b1 = wd == (hi >> 5) ? (hi & 31) : 31;
-        unsigned mask = (b1 == 31 ? 0xffffffffu : ((1u << (b1 + 1)) - 1u)) & ~((1u << b0) - 1u);
-        atomicOr(&bits[wd], mask);
-      }
-    }
-  }
+  mask_raster_path<CRIT_THREADS, true>(bits, pin_x, pin_y, path, len, a.loc_x, a.loc_y, a.N, a.map_x, a.map_y, tid);
   __syncthreads();
   // ---- the cells: wave w takes the blocks w, w + 4, ... of 64 consecutive cells, lane l the cell l of the block
   const int lane = tid & 63, wave = tid >> 6;
@@ -314,7 +280,7 @@ __global__ void __launch_bounds__(CRIT_THREADS) crit_decode_kernel(CritArgs a) {
 
 inline long long crit_align8(long long v) { return (v + 7) & ~7ll; }
 inline bool crit_sizes_ok(int N, int B, int P) {
-  return N >= 1 && B >= 1 && (P == 0 || (P > 0 && P % 64 == 0 && P <= CRIT_MAX_CELLS));
+  return N >= 1 && B >= 1 && (P == 0 || mask_map_ok(P, 1));    // (the cell count alone: a map of P x 1)
 }
 inline long long crit_workspace_bytes(int N, int B, int P) { return 8ll * N + crit_align8(4ll * B) + 4ll * B * P; }
 
@@ -332,8 +298,8 @@ int crit_run(const char* fn, CritArgs a, const float* pred, const float* require
   MMFT_REQUIRE(pred && required && path_nodes && path_lens && paths && node_slack && node_row && node_viol && node_crit && counts &&
                    (!cells || (loc_x && loc_y)),
                "%s: null pointer", fn);
-  MMFT_REQUIRE(!cells || (map_x > 0 && map_y > 0 && (long long)map_x * map_y <= CRIT_MAX_CELLS && ((long long)map_x * map_y) % 64 == 0),
-               "%s: with the cell outputs the map must hold a multiple of 64 cells, at most %d (got %d x %d)", fn, CRIT_MAX_CELLS,
+  MMFT_REQUIRE(!cells || mask_map_ok(map_x, map_y),
+               "%s: with the cell outputs the map must hold a multiple of 64 cells, at most %d (got %d x %d)", fn, MASK_MAX_CELLS,
                map_x, map_y);
   const int P = cells ? map_x * map_y : 0;
   if constexpr (SUMS) {
@@ -386,7 +352,7 @@ extern "C" {
 long long mmft_criticality_workspace_bytes(int N, int B, int P) {
   if (!crit_sizes_ok(N, B, P)) {
     set_error("criticality_workspace_bytes: need N >= 1, B >= 1, P == 0 or a multiple of 64 up to %d (got N %d, B %d, P %d)",
-              CRIT_MAX_CELLS, N, B, P);
+              MASK_MAX_CELLS, N, B, P);
     return -1;
   }
   return crit_workspace_bytes(N, B, P);
@@ -405,7 +371,7 @@ int mmft_criticality(const float* pred, const float* required, const int* path_n
 long long mmft_criticality_sums_workspace_bytes(int N, int B, int P) {
   if (!crit_sizes_ok(N, B, P)) {
     set_error("criticality_sums_workspace_bytes: need N >= 1, B >= 1, P == 0 or a multiple of 64 up to %d (got N %d, B %d, P %d)",
-              CRIT_MAX_CELLS, N, B, P);
+              MASK_MAX_CELLS, N, B, P);
     return -1;
   }
   return crit_workspace_bytes(N, B, P);

@@ -1,33 +1,25 @@
 // Discrete pin sensitivity (include/mmft_sens_pins.h): per batch row and (first-occurrence position, direction) the change of
 // g[t] . h_cnn[t] when that pin moves one map cell, from the line segments its adjacent boxes gain and lose - no bitmap - and
-// the per-pin sums of those rows over a static incidence CSR.  The box arithmetic is the mask rule of include/mmft_place.h as
-// place.hip / prep.hip apply it (min / max of the two pins, lower corner clamped to 0, upper to map - 1, empty boxes skipped).
+// the per-pin sums of those rows over a static incidence CSR.  The box arithmetic is the mask rule of include/mmft_place.h,
+// per axis mask_axis_range (mask_rule.h) - the function the bitmap kernels build their boxes from.
 #include "common.h"
+#include "mask_rule.h"
 #include "../../include/mmft_sens_pins.h"
 
 namespace mmft {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
-constexpr int PMOVE_MAX_CELLS = 65536;      // as mmft_place.h
 constexpr int PMOVE_MAX_LEN = 1024;         // nodes of a row staged in LDS: 3 x 4 KB ints + 1 KB flags, next to 4 KB of g
-
-// [lo, hi] of the mask rule along one axis for two pins at u and v on an axis of `lim` cells; empty when lo > hi
-__device__ inline void pm_range(int u, int v, int lim, int& lo, int& hi) {
-  lo = u < v ? u : v;
-  hi = u < v ? v : u;
-  lo = lo < 0 ? 0 : lo;
-  hi = hi >= lim ? lim - 1 : hi;
-}
 
 // Is the cell at (pm, pf) - moving axis, fixed axis - inside the box of the node pair (k, k + 1), pin n displaced by delta along
 // the moving axis (delta == 0: the box as it is)?
 __device__ inline bool pm_in_box(const int* cm, const int* cf, const int* node, int k, int n, int delta, int lim_m, int lim_f,
                                  int pm, int pf) {
   int lo, hi;
-  pm_range(cm[k] + (node[k] == n ? delta : 0), cm[k + 1] + (node[k + 1] == n ? delta : 0), lim_m, lo, hi);
+  mask_axis_range(cm[k] + (node[k] == n ? delta : 0), cm[k + 1] + (node[k + 1] == n ? delta : 0), lim_m, lo, hi);
   if (pm < lo || pm > hi) return false;
-  pm_range(cf[k], cf[k + 1], lim_f, lo, hi);
+  mask_axis_range(cf[k], cf[k + 1], lim_f, lo, hi);
   return pf >= lo && pf <= hi;
 }
 
@@ -53,10 +45,10 @@ __device__ inline void pin_move_items(const int* sx, const int* sy, const int* s
       const bool mk = snode[k] == n, mk1 = snode[k + 1] == n;
       if (!mk && !mk1) continue;                                       // a box the pin does not touch
       int f1, f2, a1, a2, b1, b2;
-      pm_range(cf[k], cf[k + 1], lim_f, f1, f2);
+      mask_axis_range(cf[k], cf[k + 1], lim_f, f1, f2);
       if (f1 > f2) continue;                                           // empty before and after
-      pm_range(cm[k], cm[k + 1], lim_m, a1, a2);                       // as it is
-      pm_range(cm[k] + (mk ? delta : 0), cm[k + 1] + (mk1 ? delta : 0), lim_m, b1, b2);      // moved
+      mask_axis_range(cm[k], cm[k + 1], lim_m, a1, a2);                       // as it is
+      mask_axis_range(cm[k] + (mk ? delta : 0), cm[k + 1] + (mk1 ? delta : 0), lim_m, b1, b2);      // moved
       const int L = f2 - f1 + 1;
       // the two ranges differ by at most one line at each end: gained lines are among {b1, b2}, lost ones among {a1, a2}
       for (int s = 0; s < 4; ++s) {
@@ -183,8 +175,7 @@ extern "C" {
 int mmft_pin_move_rows(const int* path_nodes, const int* path_lens, int maxlen, const int* loc_x, const int* loc_y, int map_x,
                        int map_y, const int* paths, const int* f_off, int T, const float* feat, const float* wT, int Dout,
                        const float* g, long long ldg, float* row_move, int device, void* stream) {
-  MMFT_REQUIRE(map_x > 0 && map_y > 0 && (long long)map_x * map_y <= PMOVE_MAX_CELLS && ((long long)map_x * map_y) % 64 == 0,
-               "pin_move_rows: the map must hold a multiple of 64 cells, at most 65536");
+  MMFT_REQUIRE(mask_map_ok(map_x, map_y), "pin_move_rows: the map must hold a multiple of 64 cells, at most 65536");
   MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && maxlen >= 1 && maxlen <= PMOVE_MAX_LEN && T >= 0 && ldg >= Dout &&
                    ldg % 4 == 0,
                "pin_move_rows: bad sizes (Dout a multiple of 4 in [4, 1024], maxlen in [1, 1024], T >= 0, ldg >= Dout and a "

@@ -2,21 +2,33 @@
 // LDS bitmap from (path nodes, pin coordinates) and projected through the block-prefix table of fc_prefix_kernel, run by
 // run, in the order and with the arithmetic of masked_fc_fwd_runs_kernel (fusion.hip) - no CSR and no run table in device memory.
 #include "common.h"
+#include "mask_rule.h"
 #include "../../include/mmft_place.h"
 
 namespace mmft {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned long long place_u64;
 
-constexpr int PLACE_MAX_CELLS = 65536;      // bitmap 8 KB, block counts 4 KB
 constexpr int PLACE_LIST = 1024;            // masks of up to this many runs (box masks have tens) get a run list in LDS, 4 KB
 
 // Dynamic LDS only (a static array in front of it would move its base off 16 bytes):
 //   part [256] f32x4 | list [PLACE_LIST] unsigned | cnt [nblk + 1] int, padded to 16 bytes | red [8] int | pin [2][256] int |
-//   bits [P / 32] unsigned
+//   bits [P / 32] unsigned                 (at MASK_MAX_CELLS: bitmap 8 KB, block counts 4 KB)
 __host__ __device__ inline int place_cnt_slots(int nblk) { return (nblk + 1 + 3) & ~3; }
 inline size_t place_lds_bytes(int P) {
   return 256 * sizeof(f32x4) + (size_t)(PLACE_LIST + place_cnt_slots(P >> 6) + 8 + 512) * 4 + (size_t)(P >> 5) * 4;
+}
+
+// the 64 cells of a block as one word (from its two bitmap words, read by the caller), and the word's run starts: bit i is set
+// where a run starts at cell i of the block
+__device__ inline place_u64 place_block(unsigned lo, unsigned hi) { return (place_u64)lo | ((place_u64)hi << 32); }
+__device__ inline place_u64 place_starts(place_u64 v) { return v & ~(v << 1); }
+// the lowest run among `starts` (not empty) of block word v: its first cell i and its length
+__device__ inline void place_first_run(place_u64 v, place_u64 starts, int& i, int& len) {
+  i = __ffsll((long long)starts) - 1;
+  const place_u64 past = ~(v >> i);                     // its first set bit: the run's length (none: the run fills 64 bits)
+  len = past ? __ffsll((long long)past) - 1 : 64;
 }
 
 // [s, e] (cells of the design's map) of run r; b is the lane's block cursor, it only moves forward (r ascends per lane).
@@ -28,12 +40,11 @@ __device__ inline void place_locate(const int* cnt, const unsigned* bits, int nb
     if (cnt[mid] <= r) lo = mid; else hi = mid - 1;
   }
   b = lo;
-  unsigned long long v = (unsigned long long)bits[2 * b] | ((unsigned long long)bits[2 * b + 1] << 32);
-  unsigned long long starts = v & ~(v << 1);            // bit i: a run starts at cell i of the block
+  const place_u64 v = place_block(bits[2 * b], bits[2 * b + 1]);
+  place_u64 starts = place_starts(v);
   for (int k = r - cnt[b]; k > 0; --k) starts &= starts - 1;
-  int i = __ffsll((long long)starts) - 1;
-  unsigned long long past = ~(v >> i);                  // its first set bit: the run's length (none: the run fills 64 bits)
-  int len = past ? __ffsll((long long)past) - 1 : 64;
+  int i, len;
+  place_first_run(v, starts, i, len);
   s = (b << 6) + i;
   e = s + len - 1;
 }
@@ -68,51 +79,18 @@ __global__ void __launch_bounds__(256) placed_fc_fwd_kernel(const int* __restric
   unsigned* bits = reinterpret_cast<unsigned*>(pin_y + 256);
   const int t = blockIdx.x, tid = threadIdx.x;
   for (int w = tid; w < words; w += 256) bits[w] = 0u;
-  // ---- the union of boxes, as path_mask_kernel (prep.hip) builds it; the node -> coordinate loads of (up to) 256 nodes are
-  // issued by as many threads at once instead of one dependent pair of loads per box
+  // ---- the union of boxes: THE MASK RULE, staged (mask_rule.h); node ids are not checked here (mmft_place.h)
   const int q = paths[t];
   const int* path = path_nodes + (long long)q * maxlen;
-  const int len = path_lens[q] < maxlen ? path_lens[q] : maxlen;        // the same for every thread: the barriers below are uniform
-  for (int j0 = 0; j0 + 1 < len; j0 += 255) {                           // chunks overlap by the node two boxes share
-    const int n = len - j0 < 256 ? len - j0 : 256;
-    __syncthreads();                                                    // bitmap zeroed / the previous chunk's boxes read
-    if (tid < n) {
-      int a = path[j0 + tid];
-      pin_x[tid] = loc_x[a];
-      pin_y[tid] = loc_y[a];
-    }
-    __syncthreads();
-    for (int j = 0; j + 1 < n; ++j) {
-      int xa = pin_x[j], ya = pin_y[j], xb = pin_x[j + 1], yb = pin_y[j + 1];
-      int x1 = xa < xb ? xa : xb, x2 = xa < xb ? xb : xa;
-      int y1 = ya < yb ? ya : yb, y2 = ya < yb ? yb : ya;
-      x1 = x1 < 0 ? 0 : x1;
-      y1 = y1 < 0 ? 0 : y1;
-      x2 = x2 >= map_x ? map_x - 1 : x2;
-      y2 = y2 >= map_y ? map_y - 1 : y2;
-      int w = y2 - y1 + 1, hgt = x2 - x1 + 1;
-      if (w <= 0 || hgt <= 0) continue;
-      // a box row is the contiguous bit range [x * map_y + y1, x * map_y + y2]: whole-word masks, not one atomic per cell
-      const int wpr = ((w + 30) >> 5) + 1;                      // words a row's range can touch
-      for (int c = tid; c < hgt * wpr; c += 256) {
-        int row = c / wpr, k = c - row * wpr;
-        int lo = (x1 + row) * map_y + y1, hi = lo + w - 1;      // inclusive bit range, inside [0, P) after the clamps
-        int word = (lo >> 5) + k;
-        if (word > (hi >> 5)) continue;
-        int b0 = word == (lo >> 5) ? (lo & 31) : 0;
-        int b1 = word == (hi >> 5) ? (hi & 31) : 31;
-        unsigned mask = (b1 == 31 ? 0xffffffffu : ((1u << (b1 + 1)) - 1u)) & ~((1u << b0) - 1u);
-        atomicOr(&bits[word], mask);
-      }
-    }
-  }
+  const int len = path_lens[q] < maxlen ? path_lens[q] : maxlen;        // the same for every thread
+  mask_raster_path<256, false>(bits, pin_x, pin_y, path, len, loc_x, loc_y, 0, map_x, map_y, tid);
   __syncthreads();
   // ---- number the runs: per-block counts, exclusive scan over the blocks (thread tid owns `per` consecutive blocks)
   const int per = (nblk + 255) >> 8;
   int mine = 0, cells = 0;
   for (int b = tid * per; b < (tid + 1) * per && b < nblk; ++b) {
-    unsigned long long v = (unsigned long long)bits[2 * b] | ((unsigned long long)bits[2 * b + 1] << 32);
-    mine += __popcll(v & ~(v << 1));
+    const place_u64 v = place_block(bits[2 * b], bits[2 * b + 1]);
+    mine += __popcll(place_starts(v));
     cells += __popcll(v);
   }
   const int lane = tid & 63, wave = tid >> 6;
@@ -132,14 +110,13 @@ __global__ void __launch_bounds__(256) placed_fc_fwd_kernel(const int* __restric
   {
     int run = base + incl - mine;
     for (int b = tid * per; b < (tid + 1) * per && b < nblk; ++b) {
-      unsigned long long v = (unsigned long long)bits[2 * b] | ((unsigned long long)bits[2 * b + 1] << 32);
+      const place_u64 v = place_block(bits[2 * b], bits[2 * b + 1]);
       cnt[b] = run;
-      unsigned long long starts = v & ~(v << 1);
+      const place_u64 starts = place_starts(v);
       if (listed) {                                     // every thread lists the runs of its own blocks, ascending
-        for (unsigned long long st = starts; st; st &= st - 1) {
-          int i = __ffsll((long long)st) - 1;
-          unsigned long long past = ~(v >> i);
-          int len = past ? __ffsll((long long)past) - 1 : 64;
+        for (place_u64 st = starts; st; st &= st - 1) {
+          int i, len;
+          place_first_run(v, st, i, len);
           list[run++] = (unsigned)((b << 6) + i) | ((unsigned)(len - 1) << 16);
         }
       } else {
@@ -202,8 +179,7 @@ int mmft_placed_fc_fwd(const int* path_nodes, const int* path_lens, int maxlen, 
                        int map_y, const int* paths, const int* f_off, int T, const float* GP, const float* bias, float* out,
                        long long ldo, int Dout, int S, int* stats, int device, void* stream) {
   MMFT_REQUIRE(S == 64, "placed_fc_fwd: the prefix block must be 64 cells (one bitmap word per block)");
-  MMFT_REQUIRE(map_x > 0 && map_y > 0 && (long long)map_x * map_y <= PLACE_MAX_CELLS && ((long long)map_x * map_y) % 64 == 0,
-               "placed_fc_fwd: the map must hold a multiple of 64 cells, at most 65536");
+  MMFT_REQUIRE(mask_map_ok(map_x, map_y), "placed_fc_fwd: the map must hold a multiple of 64 cells, at most 65536");
   MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && maxlen >= 1 && T >= 0 && ldo >= Dout && ldo % 4 == 0,
                "placed_fc_fwd: bad sizes (Dout a multiple of 4 in [4, 1024], maxlen >= 1, T >= 0, ldo >= Dout and a multiple of 4)");
   MMFT_REQUIRE(path_nodes && path_lens && loc_x && loc_y && paths && GP && out, "placed_fc_fwd: null pointer");
@@ -212,7 +188,7 @@ int mmft_placed_fc_fwd(const int* path_nodes, const int* path_lens, int maxlen, 
   DeviceGuard dg(device);
   const int P = map_x * map_y;
   static DynLdsOnce once;
-  int arc = ensure_dyn_lds(once, (const void*)placed_fc_fwd_kernel, (int)place_lds_bytes(PLACE_MAX_CELLS), "placed_fc_fwd");
+  int arc = ensure_dyn_lds(once, (const void*)placed_fc_fwd_kernel, (int)place_lds_bytes(MASK_MAX_CELLS), "placed_fc_fwd");
   if (arc) return arc;
   MMFT_LAUNCH_LDS("placed_fc_fwd_kernel", 0.0, 0.0, placed_fc_fwd_kernel, dim3(T), dim3(256), place_lds_bytes(P), (hipStream_t)stream,
                   path_nodes, path_lens, maxlen, loc_x, loc_y, map_x, map_y, paths, f_off, GP, bias, out, ldo, Dout, stats);

@@ -9,6 +9,7 @@
 //                       (:1302-1369, masking == 'critical')
 //   minmax_normalize    per-column (a - min) / (max - min)           (src/train.py:309-318)
 #include "common.h"
+#include "mask_rule.h"
 #include <math.h>
 
 namespace mmft {
@@ -143,28 +144,7 @@ __global__ void __launch_bounds__(256) path_mask_kernel(const int* __restrict__ 
   int len = lens[t] < maxlen ? lens[t] : maxlen;
   for (int j = 0; j + 1 < len; ++j) {
     int a = path[j], b = path[j + 1];
-    int xa = loc_x[a], ya = loc_y[a], xb = loc_x[b], yb = loc_y[b];
-    int x1 = xa < xb ? xa : xb, x2 = xa < xb ? xb : xa;
-    int y1 = ya < yb ? ya : yb, y2 = ya < yb ? yb : ya;
-    x1 = x1 < 0 ? 0 : x1;
-    y1 = y1 < 0 ? 0 : y1;
-    x2 = x2 >= map_x ? map_x - 1 : x2;
-    y2 = y2 >= map_y ? map_y - 1 : y2;
-    int w = y2 - y1 + 1, hgt = x2 - x1 + 1;
-    if (w <= 0 || hgt <= 0) continue;
-    // a box row is the contiguous bit range [x * map_y + y1, x * map_y + y2]: OR whole-word masks instead of one
-    // LDS atomic per cell (boxes of long nets cover thousands of cells)
-    const int wpr = ((w + 30) >> 5) + 1;                      // words a row's range can touch
-    for (int c = tid; c < hgt * wpr; c += 256) {
-      int row = c / wpr, k = c - row * wpr;
-      int lo = (x1 + row) * map_y + y1, hi = lo + w - 1;      // inclusive bit range
-      int word = (lo >> 5) + k;
-      if (word > (hi >> 5)) continue;
-      int b0 = word == (lo >> 5) ? (lo & 31) : 0;
-      int b1 = word == (hi >> 5) ? (hi & 31) : 31;
-      unsigned mask = (b1 == 31 ? 0xffffffffu : ((1u << (b1 + 1)) - 1u)) & ~((1u << b0) - 1u);
-      atomicOr(&bits[word], mask);
-    }
+    mask_or_box<256>(bits, loc_x[a], loc_y[a], loc_x[b], loc_y[b], map_x, map_y, tid);       // THE MASK RULE (mask_rule.h)
   }
   __syncthreads();
   // ordered emission: per-thread popcount over a contiguous run of words, then an exclusive scan over the block

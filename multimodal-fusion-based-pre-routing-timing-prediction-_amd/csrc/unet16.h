@@ -53,4 +53,27 @@ __device__ __forceinline__ u32x2 as_u32x2(s16x4 v) { return __builtin_bit_cast(u
 // the ReLU mask from z with the SAME expression (t > 0), so forward and backward agree on every element.
 __device__ __forceinline__ float bn_pre(float z, float scale, float shift) { return __fmaf_rn(z, scale, shift); }
 
+// the scale of the eval epilogue (unet16_conv.hip), gamma / sqrt(running_var + eps) with every step rounded to fp32; its
+// backward (unet16_eval_bwd.hip) multiplies by the same bits
+__device__ __forceinline__ float bn_frozen_scale(float gamma, float rvar, float eps) {
+  return __fmul_rn(gamma, bn_frozen_invstd(rvar, eps));
+}
+
+// 2x2 max pooling backward (u16_pool_bwd_kernel, unet16_ew.hip; u16_frozen_bwd_pool_kernel, unet16_eval_bwd.hip):
+// arg[j] = the pixel (0 .. 3, scan order) of the window that receives the pooled gradient of channel j: torch's argmax, the
+// first maximum in scan order - a later element wins when it is greater - and a NaN wins
+__device__ __forceinline__ void u16_pool_argmax(const float av[4][8], int arg[8]) {
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    float m = av[0][j];
+    arg[j] = 0;
+#pragma unroll
+    for (int k = 1; k < 4; ++k)
+      if (av[k][j] > m || av[k][j] != av[k][j]) {
+        m = av[k][j];
+        arg[j] = k;
+      }
+  }
+}
+
 }  // namespace mmft

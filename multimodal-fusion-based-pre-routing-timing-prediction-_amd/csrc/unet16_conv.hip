@@ -198,8 +198,8 @@ __global__ void __launch_bounds__(256) u16_conv3x3_kernel(U16ConvArgs a) {
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const int c = co0 + m * 16 + 4 * q + j;
-        const float invstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(a.rvar[c], a.eps)));
-        sc[m][j] = __fmul_rn(a.gamma[c], invstd);
+        const float rv = a.rvar[c];
+        sc[m][j] = bn_frozen_scale(a.gamma[c], rv, a.eps);
         sh[m][j] = __fmaf_rn(-a.rmean[c], sc[m][j], a.beta[c]);
       }
   }

@@ -2,8 +2,8 @@
 // walk of mmft.unet16.unet_eval_input_grad does not find among the training kernels.
 //   u16_frozen_bwd*_kernel        backward of the eval epilogue of unet16_conv.hip, a = bf16(relu(fmaf(acc, scale, shift))),
 //                                 with the ReLU mask read from the STORED activation; the pooled form also routes the pooled
-//                                 tensor's gradient (the rule of u16_pool_bwd_kernel, unet16_ew.hip) and adds the skip
-//                                 connection's in the same pass - one rounding, no round trip of g
+//                                 tensor's gradient (to u16_pool_argmax of unet16.h, as u16_pool_bwd_kernel of unet16_ew.hip
+//                                 does) and adds the skip connection's in the same pass - one rounding, no round trip of g
 //   u16_conv3x3_dgrad_image_kernel  input gradient of the 3 -> 16 convolution, fp32 NCHW, from an LDS-resident halo tile
 //                                 on the MFMA (the 3 input channels padded to 16 rows)
 // No weight gradient, no BatchNorm parameter gradient, no workspace, no atomics: same inputs, same bits.
@@ -12,14 +12,10 @@
 
 namespace mmft {
 
-// scale of 8 consecutive channels, by the sequence of the eval epilogue (unet16_conv.hip: invstd = 1 / sqrtf(rv + eps);
-// scale = gamma * invstd), restated here: that file's device code stays as it is
+// scale of 8 consecutive channels: bn_frozen_scale (unet16.h), the function the eval epilogue of unet16_conv.hip forms it with
 __device__ __forceinline__ void frozen_scale8(const float* __restrict__ gamma, const float* __restrict__ rvar, float eps, int c0, float sc[8]) {
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const float invstd = __fdiv_rn(1.f, __fsqrt_rn(__fadd_rn(rvar[c0 + j], eps)));
-    sc[j] = __fmul_rn(gamma[c0 + j], invstd);
-  }
+  for (int j = 0; j < 8; ++j) sc[j] = bn_frozen_scale(gamma[c0 + j], rvar[c0 + j], eps);
 }
 
 struct U16FrozenBwdArgs {
@@ -72,17 +68,7 @@ __global__ void __launch_bounds__(256) u16_frozen_bwd_pool_kernel(U16FrozenBwdAr
     for (int k = 0; k < 4; ++k)
       unpack8(*reinterpret_cast<const u32x4*>(p.a + (p00 + (k >> 1) * p.W + (k & 1)) * p.lda + cg * 8), av[k]);
     int arg[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float m = av[0][j];
-      arg[j] = 0;
-#pragma unroll
-      for (int k = 1; k < 4; ++k)
-        if (av[k][j] > m || av[k][j] != av[k][j]) {
-          m = av[k][j];
-          arg[j] = k;
-        }
-    }
+    u16_pool_argmax(av, arg);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const long long pix = p00 + (k >> 1) * p.W + (k & 1);

@@ -283,8 +283,8 @@ __global__ void __launch_bounds__(256) u16_bn_bwd_apply_kernel(const u16* __rest
 }
 
 // ---------------------------------------------------------------------------------------------- pooling backward + skip add
-// g[pixel] = gskip[pixel] + (the window's pooled gradient routed to torch's argmax: first maximum in scan order, NaN wins
-// / a quarter of it for average pooling).  a: the stored activation (a slice of the concatenation buffer, pitch lda);
+// g[pixel] = gskip[pixel] + (the window's pooled gradient routed to torch's argmax - u16_pool_argmax, unet16.h - / a quarter
+// of it for average pooling).  a: the stored activation (a slice of the concatenation buffer, pitch lda);
 // gskip: the skip half of the concatenation's gradient (pitch ldg), may be null; item = (window, group of 8 channels).
 struct U16PoolBwdArgs {
   const u16* a;
@@ -311,17 +311,7 @@ __global__ void __launch_bounds__(256) u16_pool_bwd_kernel(U16PoolBwdArgs p) {
     for (int k = 0; k < 4; ++k)
       unpack8(*reinterpret_cast<const u32x4*>(p.a + (p00 + (k >> 1) * p.W + (k & 1)) * p.lda + cg * 8), av[k]);
     int arg[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-      float m = av[0][j];
-      arg[j] = 0;
-#pragma unroll
-      for (int k = 1; k < 4; ++k)
-        if (av[k][j] > m || av[k][j] != av[k][j]) {
-          m = av[k][j];
-          arg[j] = k;
-        }
-    }
+    u16_pool_argmax(av, arg);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       const long long pix = p00 + (k >> 1) * p.W + (k & 1);
