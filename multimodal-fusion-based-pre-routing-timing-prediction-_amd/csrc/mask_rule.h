@@ -1,7 +1,8 @@
 // THE MASK RULE of include/mmft_place.h as device code, stated once: the box of two pins (min / max per axis, lower corner
 // clamped to 0, upper to map - 1, empty boxes skipped) ORed into an LDS bitmap, cell (x, y) = bit x * map_y + y.
-// path_mask_kernel (prep.hip), placed_fc_fwd_kernel (place.hip) and crit_scatter_kernel (crit.hip) build their bitmaps with
-// it, pin_move.hip takes the axis arithmetic: the tests compare these kernels bitwise, and the rule they share is here.
+// path_mask_kernel (prep.hip), placed_fc_fwd_kernel (place.hip), crit_scatter_kernel (crit.hip) and trial_rows_kernel
+// (trial.hip, under a candidate's overrides) build their bitmaps with it, pin_move.hip takes the axis arithmetic: the tests
+// compare these kernels bitwise, and the rule they share is here.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -61,6 +62,35 @@ __device__ __forceinline__ void mask_raster_path(unsigned* bits, int* pin_x, int
       if constexpr (CLAMP) a = a < 0 ? 0 : (a >= n_nodes ? n_nodes - 1 : a);
       pin_x[tid] = loc_x[a];
       pin_y[tid] = loc_y[a];
+    }
+    __syncthreads();
+    for (int j = 0; j + 1 < n; ++j) mask_or_box<THREADS>(bits, pin_x[j], pin_y[j], pin_x[j + 1], pin_y[j + 1], map_x, map_y, tid);
+  }
+}
+
+// mask_raster_path under a trial move: the nodes mv_node[0 .. n_mv) (LDS, distinct, written by the caller before the call:
+// the first barrier below orders those writes) take the coordinates (mv_x[m], mv_y[m]) at EVERY occurrence in the path, every
+// other node its own from loc_x / loc_y, which are not written.  The override is applied where a node's coordinates are
+// staged, so the boxes go through the same mask_or_box in the same order: with n_mv == 0, or with no moved node on the path,
+// the bitmap is mask_raster_path's.
+template <int THREADS>
+__device__ __forceinline__ void mask_raster_path_moved(unsigned* bits, int* pin_x, int* pin_y, const int* path, int len,
+                                                       const int* loc_x, const int* loc_y, const int* mv_node, const int* mv_x,
+                                                       const int* mv_y, int n_mv, int map_x, int map_y, int tid) {
+  for (int j0 = 0; j0 + 1 < len; j0 += THREADS - 1) {
+    const int n = len - j0 < THREADS ? len - j0 : THREADS;
+    __syncthreads();                                          // bitmap zeroed, overrides staged / the previous chunk's boxes read
+    if (tid < n) {
+      const int a = path[j0 + tid];
+      int x = loc_x[a], y = loc_y[a];
+      for (int m = 0; m < n_mv; ++m) {
+        if (mv_node[m] == a) {
+          x = mv_x[m];
+          y = mv_y[m];
+        }
+      }
+      pin_x[tid] = x;
+      pin_y[tid] = y;
     }
     __syncthreads();
     for (int j = 0; j + 1 < n; ++j) mask_or_box<THREADS>(bits, pin_x[j], pin_y[j], pin_x[j + 1], pin_y[j + 1], map_x, map_y, tid);

@@ -197,12 +197,19 @@ class Predictor(ResidentDesigns):
                           (scale_log2 in [0, 30], refused without sums), every pin's and cell's share of its design's TNS and
                           the rows that hit the cap; criticality() then also returns node_tns, cell_tns, tns, node_share,
                           cell_share and saturated (mmft.criticality.decode_sums).  Without sums nothing about the call changes
+    trials                True (needs placement=True): every predict() keeps the head's input rows, the prefix table of the
+                          masked projection and its predictions, and trial_moves(i, pins, pin_x, pin_y, cand_ptr) returns the
+                          exact predictions and WNS / TNS of design i under a batch of candidate pin moves, each taken alone,
+                          without writing the placement (mmft.trial, include/mmft_trial.h).  bf16 math mode with the fused
+                          regression head.  Left at False, nothing about the object, its launches or its results changes
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
-                 cone=False, report=None, placement=False, incremental=False, criticality=None):
+                 cone=False, report=None, placement=False, incremental=False, criticality=None, trials=False):
         criticality = self._criticality_spec(criticality)
+        if trials and not placement:
+            raise ValueError('Predictor: trials=True needs placement=True (a trial move moves pins of the placement tables)')
         super().__init__('Predictor', pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap, static_selection=True)
         self.graphed, self.cone = bool(graphed), bool(cone)
         b = self.batch
@@ -221,6 +228,10 @@ class Predictor(ResidentDesigns):
         self._report = self._make_report(report) if report is not None else None
         self._placed = self._make_placed(designs) if placement else None
         self._crit = self._make_criticality(criticality, designs) if criticality is not None else None
+        self._trial = None                                 # trials=True: what trial_moves needs from the last predict() (mmft.trial)
+        if trials:
+            from .trial import TrialState
+            self._trial = TrialState(self)
 
     def _make_placed(self, designs):
         """The batch's placement tables; refuses designs without placement data and designs whose stored masks are not the
@@ -324,13 +335,22 @@ class Predictor(ResidentDesigns):
         """h_cnn from the pins as they are now (train.forward_to_head's project=, placement=True)."""
         from .placement import placed_fc
         b, fcn = self.batch, self.pmodel.fcn
+        if self._trial is not None:                          # ... and the prefix table it projected through is kept for trial_moves
+            return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks,
+                             keep=self._trial.kept)
         return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks)
 
     def _launches(self):
         b, pm_, paths_d = self.batch, self.pmodel, self._sel.paths
         h_gnn, _, pmap, h_cnn = forward_to_head(pm_, self.cnn, b, self._sel, self.h, side=self.side, cone=self.cone, sweep=self._run_sweep,
                                                 project=self._placed_fc if self._placed is not None else None)
-        pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn)
+        if self._trial is not None:
+            # the references of the latest eager or capturing call: a replay rewrites those same buffers
+            kept = self._trial.kept
+            pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn, keep=kept)
+            kept['pred'], kept['mode'] = pred, lib.get_math_mode()
+        else:
+            pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn)
         if self._report is not None:
             from . import report as R
             r = self._report
@@ -363,6 +383,7 @@ class Predictor(ResidentDesigns):
             if not replay:
                 out = self._launches()
                 self._trusted = self.incremental_active
+                self._trial_fresh()
                 return out, self.endpoints
             # the graph bakes in where the model lives and which modes it ran in
             sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
@@ -371,12 +392,38 @@ class Predictor(ResidentDesigns):
             if self._replay is None or sig != self._sig:
                 self._sig = sig
                 self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed,
-                                                     self.seed, self.dirty, self._crit))
+                                                     self.seed, self.dirty, self._crit) +
+                                               ((self._trial,) if self._trial is not None else ()))
             out = self._replay.run(self._launches)
             self._trusted = self.incremental_active
+            self._trial_fresh()
             if out is not None:                                  # an eager or the capturing call
                 self._out = out
             return self._out, self.endpoints
+
+    def _trial_fresh(self):
+        """A predict() has completed: what trial_moves keeps is that of the resident designs again."""
+        if self._trial is not None:
+            self._trial.ready, self._trial.stale = True, False
+
+    def trial_moves(self, i, pins, pin_x, pin_y, cand_ptr=None):
+        """Exact predictions of design i under K candidate pin moves, each taken ALONE, from the last predict()
+        (trials=True; mmft.trial, include/mmft_trial.h).  pins: int64 [M] node ids in design i's own numbering; pin_x / pin_y:
+        int32 / int64 [M], the pins' NEW absolute map-cell coordinates (any 32-bit int: the mask rule clamps them, as for
+        update); cand_ptr: int64 [K + 1], CSR over the moves - non-decreasing, from 0 to M -, None: every move is a candidate
+        of its own.  A candidate is a set of at most 64 distinct pins that move together.  Everything is validated on the
+        host before anything is launched.
+
+        Returns host data (one device -> host copy): pair_ptr [K + 1] and rows [n_pairs] - per candidate the rows of `pred`
+        whose path holds one of its pins, ascending: the only rows it can change -, pred fp32 [n_pairs] - that row under that
+        candidate -, per candidate wns, tns (float64), wns_row, violations, n_nan, n (the slack rule of mmft_report.h over
+        design i's rows) and `base`, the same figures on the pins as they are.  A candidate without pairs has the base's.
+
+        Writes nothing another call reads - not loc_x / loc_y, h, the model or predict()'s static output.  Eager: refused
+        under an outer stream capture.  RuntimeError without trials=True, before the first predict() and after an update() that
+        no predict() has followed; ValueError outside bf16 math mode with the fused regression head."""
+        from . import trial
+        return trial.trial_moves(self, i, pins, pin_x, pin_y, cand_ptr)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is
@@ -469,6 +516,8 @@ class Predictor(ResidentDesigns):
             pins = self._placed.check_pins(i, pin_x, pin_y)
         self._update_design(i, cell_feat, net_feat, image, rows, seed=self.seed,
                             perm32=self._perm32[i] if self._perm32 is not None else None)
+        if self._trial is not None:
+            self._trial.stale = True                         # until the next predict(): trial_moves refuses in between
         if pins is not None:
             self._placed.set_pins(i, *pins)
 

@@ -220,13 +220,14 @@ def batch_tables(designs, batch, device, who, projection=True):
     return placed
 
 
-def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None):
+def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None, keep=None):
     """fcn(mask rows * feat_map) with the mask of every batch row taken from `placed`'s current pins.
 
     paths int32 [T] (rows of placed.nodes), f_off int32 [T] or None (one design), feat_map [B, P], w [Dout, P], b [Dout] or
     None; `masks` is the batch's PathMasks and only says how the prefix table is laid out (B, P, run_block): the table comes
     from fusion.masked_fc_prefix - same cache, same launches as fusion.masked_fc.  stats: optional int32 [T, 2], filled with
-    (cells, runs) of each row's mask.  Forward only."""
+    (cells, runs) of each row's mask.  keep: a dict that receives the prefix table this call projected through as keep['GP']
+    (mmft.trial projects trial rows through the same table); absent, nothing else happens.  Forward only."""
     if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (feat_map, w, b)):
         raise RuntimeError('placed_fc is forward only: call it under torch.no_grad() (moving masks have no backward)')
     if masks.P != placed.P or masks.B != placed.B:
@@ -242,6 +243,8 @@ def placed_fc(placed, paths, f_off, feat_map, w, b, masks, stats=None):
     if GP is None:
         raise ValueError('placed_fc: the masks have no run form (the map must hold a multiple of fusion.RUN_BLOCK cells, '
                          'fusion.USE_RUNS on, contiguous feat_map and weight)')
+    if keep is not None:
+        keep['GP'] = GP
     T, Dout = paths.numel(), w.shape[0]
     if stats is not None and (stats.dtype != torch.int32 or tuple(stats.shape) != (T, 2) or not stats.is_contiguous()):
         raise ValueError('placed_fc: stats must be a contiguous int32 [T, 2] tensor')

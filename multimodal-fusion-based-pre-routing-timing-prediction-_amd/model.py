@@ -328,12 +328,13 @@ class PathModel(nn.Module):
         # an outside caller's endpoints need not be ordered by level: the order-free gradient of the level gather
         return self.fuse_heads(h_gnn, path_map, target_levels, len(level_nodes), levels_ascending=False)
 
-    def fuse_heads(self, h_gnn, path_map, target_levels, num_levels, h_cnn=None, levels_ascending=True):
+    def fuse_heads(self, h_gnn, path_map, target_levels, num_levels, h_cnn=None, levels_ascending=True, keep=None):
         """Fusion head over all T endpoints at once: fcn(path_map), mlp_alpha(level of each endpoint), mlp_fuse
         (src/model.py:271-292 with the level-invariant work hoisted).  `h_cnn` may be passed pre-computed
         (= self._fcn(path_map)) so that the caller can overlap it with the tail of the sweep.  levels_ascending: the caller
         guarantees non-decreasing `target_levels` (DesignBatch.select sorts them); unchecked, the gradient into mlp_alpha
-        is wrong without it."""
+        is wrong without it.  keep: a dict that receives the tensor handed to mlp_fuse as keep['x'] and the column at which
+        h_cnn starts in it as keep['cnn_col'] (None without h_cnn); absent, nothing else happens."""
         if h_cnn is None:
             h_cnn = self._fcn(path_map) if (self.fcn is not None and path_map is not None) else None
         cache = self.__dict__.setdefault('_level_ids', {})
@@ -345,4 +346,8 @@ class PathModel(nn.Module):
         # segmented sum over contiguous runs
         h_global = MF.gather_rows(self.mlp_alpha(lv), target_levels, ascending=levels_ascending)   # (T, 32), alpha(level of t)
         parts = [p for p in (h_gnn, h_cnn, h_global) if p is not None]
-        return self.mlp_fuse(MF.concat_cols(*parts) if len(parts) > 1 else parts[0]).squeeze(-1)
+        x = MF.concat_cols(*parts) if len(parts) > 1 else parts[0]
+        if keep is not None:
+            keep['x'] = x
+            keep['cnn_col'] = None if h_cnn is None else (h_gnn.shape[1] if h_gnn is not None else 0)
+        return self.mlp_fuse(x).squeeze(-1)

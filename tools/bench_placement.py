@@ -30,6 +30,16 @@ sums of negative slack and the TNS shares from the same walk), whose device resu
 bitwise; the launches alone (crit_sums_alone_pins / crit_sums_alone); and the host route for the sums: np.add.at over path_nodes
 (host_sums_pins), the mask columns of design 0 (host_sums_cells_design0, masks given: the rasterisation is host_cells_design0's).
 --no-sums leaves every sums row out: for a run on an older build of the library (MMFT_LIB), which does not export the entry point.
+
+--trials [--candidates 4096], on the same designs (nothing of the above is run): ONE Predictor.trial_moves call over 4096
+single-pin candidates of design 0 (trials_single) and over 512 candidates of 8 pins each (trials_group8), each pin displaced by up
+to map / 8 cells: host milliseconds of validation, expansion and upload (host_ms), device milliseconds of the three launches
+(launches_ms, events), host milliseconds of the copy back and decoding (copy_back_ms), and the whole call under one host clock
+(call_ms); per row the median over `rounds` rounds.  Next to them, alternating inside the same rounds, update() + a replayed
+predict() for 64 of the same single-pin candidates one after another, their pins already on the device
+(sequential_update_predict, host clock around the 64, per trial).  The trial predictions of those 64 must equal the sequential
+ones bitwise.  speedup_over_sequential = K sequential trials / one call; beats_64_sequential_trials says whether one call of K
+candidates costs less than 64 sequential trials.
 Needs a GPU."""
 import argparse
 import copy
@@ -231,6 +241,116 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     emit(row='host_sums_cells_design0', repetitions=a.rebuilds, s_median=statistics.median(t), s_min=min(t), s_max=max(t))
 
 
+def trials_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--trials: one Predictor.trial_moves call over many candidates of design 0 next to update() + replayed predict() per
+    candidate, in the same run."""
+    from mmft import trial as TR
+    m, d = designs[0].map_size, designs[0]
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N = int(d.N)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    on = np.flatnonzero(count > 0)
+    rng = np.random.default_rng(7)
+    step = max(m // 8, 1)
+
+    def moved_to(pins):
+        x = np.clip(d.pin_x[pins] + rng.integers(-step, step + 1, pins.shape[0]), 0, m - 1)
+        y = np.clip(d.pin_y[pins] + rng.integers(-step, step + 1, pins.shape[0]), 0, m - 1)
+        return x.astype(np.int32), y.astype(np.int32)
+    single = rng.choice(on, a.candidates, replace=on.size < a.candidates).astype(np.int64)
+    groups = np.concatenate([rng.choice(on, 8, replace=False) for _ in range(a.candidates // 8)]).astype(np.int64)
+    sets = {'trials_single': (single, *moved_to(single), None),
+            'trials_group8': (groups, *moved_to(groups), np.arange(0, groups.shape[0] + 1, 8, dtype=np.int64))}
+    emit(row='trials_shapes', designs=a.designs, map=m, rows=int(p.T), rows_design0=int(p._trial.design_rows[0].numel()),
+         row_pin_first_occurrences=int(ptr[-1]), pins_on_a_row_design0=int(on.size), rows_per_such_pin_mean=float(count[on].mean()))
+
+    def staged(args):
+        """One call in its three stages: host seconds to the plan (validation, expansion, the one upload), device milliseconds of
+        the three launches (events), host seconds of the copy back; and the whole call under one host clock."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        plan = TR.prepare(p, 0, *args)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        TR.launch(p, plan)
+        e1.record()
+        e1.synchronize()
+        t2 = time.perf_counter()
+        res = TR.fetch(plan)
+        t3 = time.perf_counter()
+        whole0 = time.perf_counter()
+        p.trial_moves(0, *args)
+        whole = time.perf_counter() - whole0
+        return res, dict(host_ms=1e3 * (t1 - t0), launches_ms=e0.elapsed_time(e1), copy_back_ms=1e3 * (t3 - t2), call_ms=1e3 * whole)
+
+    # the sequential route on 64 of the single-pin candidates: update() with the candidate's pins, a replayed predict()
+    take = np.arange(0, a.candidates, max(a.candidates // 64, 1))[:64]
+    res, _ = staged(sets['trials_single'])
+    base_x, base_y = (torch.from_numpy(np.asarray(v).astype(np.int32)).to(dev) for v in (d.pin_x, d.pin_y))
+    seq_pins = []
+    for k in take:
+        x, y = base_x.clone(), base_y.clone()
+        x[int(single[k])], y[int(single[k])] = int(sets['trials_single'][1][k]), int(sets['trials_single'][2][k])
+        seq_pins.append((x, y))
+    same, base_bits = True, base.cpu().numpy().view(np.uint32)
+    for k, (x, y) in zip(take, seq_pins):
+        p.update(0, pin_x=x, pin_y=y)
+        y_seq = p.predict()[0].cpu().numpy()
+        rows = res['rows'][res['pair_ptr'][k]:res['pair_ptr'][k + 1]]
+        got = res['pred'][res['pair_ptr'][k]:res['pair_ptr'][k + 1]]
+        same &= bool(np.array_equal(got.view(np.uint32), y_seq[rows].view(np.uint32)))
+        changed = np.flatnonzero(y_seq.view(np.uint32) != base_bits)
+        same &= set(changed.tolist()) <= set(rows.tolist())
+    p.update(0, pin_x=base_x, pin_y=base_y)
+    assert torch.equal(p.predict()[0], base)
+    emit(row='trials_outputs', sequential_candidates=int(take.size), trial_equals_update_predict_bitwise=bool(same),
+         candidates_that_change_wns_row=int((res['wns_row'] != res['base']['wns_row']).sum()),
+         candidates_that_change_violations=int((res['violations'] != res['base']['violations']).sum()))
+    assert same
+
+    def sequential():
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for x, y in seq_pins:
+            p.update(0, pin_x=x, pin_y=y)
+            p.predict()
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0) / len(seq_pins)
+        p.update(0, pin_x=base_x, pin_y=base_y)                          # (not timed) the pins back: the next call's trials start from them
+        p.predict()
+        return ms
+
+    for nm in sets:                                                     # warm-up of every row
+        staged(sets[nm])
+    sequential()
+    parts = {nm: [] for nm in sets}
+    seq = []
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm in sets:
+            parts[nm].append(staged(sets[nm])[1])
+        seq.append(sequential())
+    p.update(0, pin_x=base_x, pin_y=base_y)
+    assert torch.equal(p.predict()[0], base)
+    seq_med = statistics.median(seq)
+    emit(row='sequential_update_predict', trials_per_round=len(seq_pins), rounds=a.rounds, ms_per_trial_median=seq_med,
+         ms_per_trial_min=min(seq), ms_per_trial_max=max(seq))
+    for nm, (pins, x, y, cptr) in sets.items():
+        K = pins.shape[0] if cptr is None else cptr.shape[0] - 1
+        plan = TR.prepare(p, 0, pins, x, y, cptr)
+        med = {k: statistics.median(r[k] for r in parts[nm]) for k in parts[nm][0]}
+        emit(row=nm, candidates=int(K), moves=int(pins.shape[0]), pairs=int(plan['n_pairs']), rounds=a.rounds,
+             **{k + '_median': v for k, v in med.items()}, call_ms_min=min(r['call_ms'] for r in parts[nm]),
+             call_ms_max=max(r['call_ms'] for r in parts[nm]), ms_per_candidate=med['call_ms'] / K,
+             sequential_ms_for_as_many=seq_med * K, speedup_over_sequential=seq_med * K / med['call_ms'],
+             beats_64_sequential_trials=bool(med['call_ms'] < 64 * seq_med))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -242,6 +362,8 @@ def main():
     ap.add_argument('--criticality', action='store_true')
     ap.add_argument('--no-sums', action='store_true', help='--criticality without the sums rows (a library older than version 207)')
     ap.add_argument('--scale-log2', type=int, default=20)
+    ap.add_argument('--trials', action='store_true')
+    ap.add_argument('--candidates', type=int, default=4096, help='--trials: single-pin candidates (and an eighth as many of 8 pins)')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -267,6 +389,10 @@ def main():
     if a.criticality:
         with lib.math_mode('bf16'), torch.no_grad():
             criticality_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.trials:
+        with lib.math_mode('bf16'), torch.no_grad():
+            trials_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
