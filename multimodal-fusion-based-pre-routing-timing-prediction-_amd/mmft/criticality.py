@@ -14,12 +14,14 @@ The rules (the header states them, `reference_criticality` restates them in nump
 The second half of the module (mmft_criticality_sums, include/mmft_crit_sums.h) adds the sums of negative slack per pin, per
 cell and per design as exact integer sums of quanta, and each pin's and cell's share of its design's TNS.
 """
+import functools
+
 import numpy as np
 import torch
 
 from . import lib
-from .placement import MAX_CELLS, rasterize_host
-from .report import reference_slack
+from .placement import MAX_CELLS, batch_tables, rasterize_host
+from .report import AfterHead, reference_slack
 
 FIELDS = ('node_slack', 'node_row', 'node_viol', 'node_crit', 'cell_slack', 'cell_viol', 'counts')
 SUM_FIELDS = ('node_nsum', 'cell_nsum', 'design_nsum', 'saturated', 'node_share', 'cell_share')
@@ -357,3 +359,65 @@ def decode_sums(node_slack, node_row, node_viol, node_crit, cell_slack, cell_vio
         d['tns'] = 0.0 - float(np.asarray(design_nsum)[b]) / unit
         d['saturated'] = int(np.asarray(saturated)[b])
     return out
+
+
+# ------------------------------------------------------------------------------------------------ the Predictor's side
+class PredictorCriticality(AfterHead):
+    """Predictor(criticality=True or dict(cells=..., sums=..., scale_log2=...)): the criticality launches on every predict()'s
+    output.  Holds the placement tables (those of placement=True, which follow update(); or tables of its own, whose pins never
+    move), the rows' slack inputs (predictor.slack), static output buffers and the keyed-word workspace - static addresses, kept
+    alive with the replay.  Plain or sums is decided ONCE, here: the buffer class, the workspace size, the launch and the decoder."""
+
+    @staticmethod
+    def spec(spec):
+        """criticality= as a dict, or None when the option is off; refuses anything else - host only, before a device is touched."""
+        if spec is None or spec is False:
+            return None
+        spec = {} if spec is True else spec
+        if not isinstance(spec, dict):
+            raise ValueError(f'Predictor: criticality= takes None, True or dict(cells=...), got {spec!r}')
+        unknown = set(spec) - {'cells', 'sums', 'scale_log2'}
+        if unknown:
+            raise ValueError(f'Predictor: criticality= takes cells, sums and scale_log2, got {sorted(unknown)}')
+        if 'scale_log2' in spec:
+            L = spec['scale_log2']
+            if not spec.get('sums'):
+                raise ValueError(f'Predictor: criticality= takes scale_log2 only with sums=True, got {spec!r}')
+            if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 0 <= L <= 30:
+                raise ValueError(f'Predictor: criticality= takes an integer scale_log2 in [0, 30], got {L!r}')
+        return spec
+
+    def __init__(self, predictor, spec):
+        b, dev = predictor.batch, predictor.device
+        self.cells, self.sums, self.scale_log2 = bool(spec.get('cells', True)), bool(spec.get('sums', False)), int(spec.get('scale_log2', 20))
+        s = self.slack = predictor.slack
+        s.require_regression(predictor.pmodel, 'Predictor: criticality=')
+        if self.cells and (b.P % 64 or b.P > MAX_CELLS):
+            raise ValueError(f'Predictor: criticality=dict(cells=True) needs a map of a multiple of 64 cells, at most {MAX_CELLS}; '
+                             f'it has {b.P}')
+        # tables of its own feed no projection: the paths' nodes are all it reads, so neither the run form nor masks that
+        # match the stored ones are asked for
+        self.placed = predictor._placed if predictor._placed is not None else \
+            batch_tables(b.designs, b, dev, 'Predictor(criticality=)', projection=False)
+        if self.sums and s.T * int(self.placed.maxlen) > MAX_ROW_PINS:
+            raise ValueError(f'Predictor: criticality=dict(sums=True) needs rows * maxlen <= 2^30 for the sums to fit int64; '
+                             f'it has {s.T} * {self.placed.maxlen}')
+        if self.sums:                                            # one launch group: the sums' kernels write the other outputs too
+            buffers, need = CritSumsBuffers, sums_workspace_bytes
+            self._launch = functools.partial(criticality_sums, scale_log2=self.scale_log2)
+            self._decode = functools.partial(decode_sums, scale_log2=self.scale_log2)
+        else:
+            buffers, need, self._launch, self._decode = CritBuffers, workspace_bytes, criticality, decode
+        N = int(b.node_off[-1])
+        self.required, self.row_design, self.paths, self.node_off = s.required, s.row_design, predictor._sel.paths, b.node_off
+        self.bufs = buffers(N, s.B, self.placed.P, dev, cells=self.cells)
+        self.scratch = torch.empty((need(N, s.B, self.placed.P if self.cells else 0) + 7) // 8, dtype=torch.int64, device=dev)
+
+    def launch(self, pred):
+        self._launch(pred.contiguous().reshape(-1), self.required, self.placed, self.paths, self.row_design, self.slack.B, cells=self.cells,
+                     out=self.bufs.tensors(), workspace=self.scratch)
+        self.ready = True
+
+    def result(self, i=None):
+        out = self._decode(*self.bufs.host(), node_off=self.node_off, map_x=self.placed.map_x, map_y=self.placed.map_y)
+        return out if i is None else out[i]

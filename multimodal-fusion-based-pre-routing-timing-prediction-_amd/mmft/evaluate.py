@@ -181,11 +181,10 @@ def timing_report(train_step, path_ids_per_design=None, k=32, hist=None, frozen_
     with frozen_statistics(train_step.cnn, frozen_stats):
         hats, ends_d, _ = train_step.forward(path_ids_per_design, _sel=sel)
     arrival = b.arrival[ends_d.long()].reshape(sel.T).contiguous()
-    required = sel.required_times(b)
-    ptr, rows = (torch.from_numpy(a).to(hats.device) for a in R.group_rows(sel.design, b.B))
+    slack = R.SlackRows(sel, b)
     bufs = R.ReportBuffers(b.B, k, hist, hats.device, reports=2)
-    R.timing_report(hats.contiguous(), required, ptr, rows, k, hist, out=bufs.tensors(0))
-    R.timing_report(arrival, required, ptr, rows, k, hist, out=bufs.tensors(1))
+    R.timing_report(hats.contiguous(), slack.required, *slack.groups, k, hist, out=bufs.tensors(0))
+    R.timing_report(arrival, slack.required, *slack.groups, k, hist, out=bufs.tensors(1))
     predicted, actual = (R.decode(*h, endpoints=np.asarray(sel.endpoints)) for h in bufs.host())
     out = []
     for p, a in zip(predicted, actual):

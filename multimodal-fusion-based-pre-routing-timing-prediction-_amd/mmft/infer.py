@@ -12,8 +12,11 @@ import contextlib
 import numpy as np
 import torch
 
-from . import gradsink, lib, ops
+from . import gradsink, lib, ops, trial
+from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
+from .placement import batch_tables, placed_fc
+from .report import PredictorReport, SlackRows
 from .train import DesignBatch, forward_to_head
 
 
@@ -93,8 +96,9 @@ def update_design(batch, perm, i, cell_feat=None, net_feat=None, image=None, row
 class ResidentDesigns:
     """What the front ends that keep a batch of designs on the device share (Predictor, sensitivity.Sensitivity): the
     DesignBatch, ONE Selection of paths made here (static_selection: its packed indices live in `_static_idx`, at addresses
-    a replayed graph may keep) with the rows' slack inputs - `required` (fp32 [T] on the device) and `row_design` (host int64
-    [T]) -, h, the per-design row permutations, and the module modes of a call."""
+    a replayed graph may keep) with the rows' slack inputs - `slack` (report.SlackRows); `required` (fp32 [T] on the device)
+    and `row_design` (host int64 [T]) are its `required` and `design` -, h, the per-design row permutations, and the module
+    modes of a call."""
 
     def __init__(self, who, pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap, static_selection=False):
         self.pmodel, self.cnn = pmodel, cnn
@@ -113,7 +117,8 @@ class ResidentDesigns:
             self._static_idx = torch.zeros(6 * self.T + b.path2level.shape[0], dtype=torch.int32, device=self.device)
         self._sel = b.select(path_ids_per_design, static=self._static_idx)
         self.endpoints = np.asarray(self._sel.endpoints)    # the caller's numbering: node_off[design] + the design's own node id
-        self.required, self.row_design = self._sel.required_times(b), self._sel.design
+        self.slack = SlackRows(self._sel, b)
+        self.required, self.row_design = self.slack.required, self.slack.design
         self.h = torch.zeros((b.N, b.out_dim), dtype=torch.float32, device=self.device)
         self._perm = [torch.from_numpy(p).to(self.device) for p in design_permutations(b.old_of_new, b.node_off)]
         self._modules = [m for root in (pmodel, cnn) if root is not None for m in root.modules()]
@@ -207,7 +212,7 @@ class Predictor(ResidentDesigns):
 
     def __init__(self, pmodel, cnn, designs, device, path_ids_per_design=None, frozen_stats=True, graphed=True, overlap=True,
                  cone=False, report=None, placement=False, incremental=False, criticality=None, trials=False):
-        criticality = self._criticality_spec(criticality)
+        criticality = self._criticality_spec(criticality)        # refusals before a device is touched
         if trials and not placement:
             raise ValueError('Predictor: trials=True needs placement=True (a trial move moves pins of the placement tables)')
         super().__init__('Predictor', pmodel, cnn, designs, device, path_ids_per_design, frozen_stats, overlap, static_selection=True)
@@ -225,91 +230,20 @@ class Predictor(ResidentDesigns):
         self._trusted, self._trust_sig, self._incr_ok = False, None, {}
         if self.incremental:
             self._perm32 = [q.to(torch.int32) for q in self._perm]
-        self._report = self._make_report(report) if report is not None else None
+        # the options: what runs after the head (report.AfterHead) in the order of its launches, and what trial_moves keeps
+        self._report = PredictorReport(self, report) if report is not None else None
         self._placed = self._make_placed(designs) if placement else None
-        self._crit = self._make_criticality(criticality, designs) if criticality is not None else None
-        self._trial = None                                 # trials=True: what trial_moves needs from the last predict() (mmft.trial)
-        if trials:
-            from .trial import TrialState
-            self._trial = TrialState(self)
+        self._crit = PredictorCriticality(self, criticality) if criticality is not None else None
+        self._trial = trial.TrialState(self) if trials else None
+
+    _criticality_spec = staticmethod(PredictorCriticality.spec)      # criticality= as a dict or None: host only, callable on its own
 
     def _make_placed(self, designs):
         """The batch's placement tables; refuses designs without placement data and designs whose stored masks are not the
         masks of their pins (turning the mode on then changes no prediction until a pin moves)."""
-        from . import placement as PL
         if self.pmodel.fcn is None or self.cnn is None:
             raise ValueError('Predictor: placement=True needs the masked projection (pmodel.fcn and a CNN)')
-        return PL.batch_tables(designs, self.batch, self.device, 'Predictor(placement=True)')
-
-    def _slacks_of(self, option):
-        """(required, row_design) for the options that form slacks (report=, criticality=); refuses a model whose head is not
-        the regression head."""
-        nlabels = self.pmodel.mlp_fuse.layers[-1].out_features
-        if nlabels != 1:
-            raise ValueError(f'Predictor: {option} needs the regression head (nlabels = 1), the model has {nlabels} labels')
-        return self.required, self.row_design
-
-    @staticmethod
-    def _criticality_spec(spec):
-        """criticality= as a dict, or None when the option is off; refuses anything else before a device is touched."""
-        if spec is None or spec is False:
-            return None
-        spec = {} if spec is True else spec
-        if not isinstance(spec, dict):
-            raise ValueError(f'Predictor: criticality= takes None, True or dict(cells=...), got {spec!r}')
-        unknown = set(spec) - {'cells', 'sums', 'scale_log2'}
-        if unknown:
-            raise ValueError(f'Predictor: criticality= takes cells, sums and scale_log2, got {sorted(unknown)}')
-        if 'scale_log2' in spec:
-            L = spec['scale_log2']
-            if not spec.get('sums'):
-                raise ValueError(f'Predictor: criticality= takes scale_log2 only with sums=True, got {spec!r}')
-            if isinstance(L, bool) or not isinstance(L, (int, np.integer)) or not 0 <= L <= 30:
-                raise ValueError(f'Predictor: criticality= takes an integer scale_log2 in [0, 30], got {L!r}')
-        return spec
-
-    def _make_criticality(self, spec, designs):
-        """Everything the criticality launch needs: the placement tables (those of placement=True, which follow update(); or
-        tables of its own, whose pins never move), the rows' required times and designs, static output buffers and the
-        keyed-word workspace - static addresses, kept alive with the replay."""
-        from . import criticality as K, placement as PL
-        cells, sums, scale_log2 = bool(spec.get('cells', True)), bool(spec.get('sums', False)), int(spec.get('scale_log2', 20))
-        required, design = self._slacks_of('criticality=')
-        b, dev = self.batch, self.device
-        if cells and (b.P % 64 or b.P > PL.MAX_CELLS):
-            raise ValueError(f'Predictor: criticality=dict(cells=True) needs a map of a multiple of 64 cells, at most {PL.MAX_CELLS}; '
-                             f'it has {b.P}')
-        # tables of its own feed no projection: the paths' nodes are all it reads, so neither the run form nor masks that
-        # match the stored ones are asked for
-        placed = self._placed if self._placed is not None else PL.batch_tables(designs, b, dev, 'Predictor(criticality=)',
-                                                                               projection=False)
-        row_design = torch.from_numpy(design.astype(np.int32)).to(dev) if b.B > 1 else None
-        N = int(b.node_off[-1])
-        if sums and required.numel() * int(placed.maxlen) > K.MAX_ROW_PINS:
-            raise ValueError(f'Predictor: criticality=dict(sums=True) needs rows * maxlen <= 2^30 for the sums to fit int64; '
-                             f'it has {required.numel()} * {placed.maxlen}')
-        bufs = (K.CritSumsBuffers if sums else K.CritBuffers)(N, b.B, placed.P, dev, cells=cells)
-        need = (K.sums_workspace_bytes if sums else K.workspace_bytes)(N, b.B, placed.P if cells else 0)
-        scratch = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
-        return dict(cells=cells, sums=sums, scale_log2=scale_log2, placed=placed, required=required, row_design=row_design, bufs=bufs,
-                    scratch=scratch, ready=False)
-
-    def _make_report(self, spec):
-        """Everything the report launch needs that the static selection decides: the endpoints' required times, the rows of
-        each design, the output buffers and the scratch - static addresses, kept alive with the replay."""
-        from . import report as R
-        unknown = set(spec) - {'k', 'hist'}
-        if unknown:
-            raise ValueError(f'Predictor: report= takes k and hist, got {sorted(unknown)}')
-        b, dev = self.batch, self.device
-        k, hist = int(spec.get('k', 32)), spec.get('hist')
-        required, design = self._slacks_of('report=')
-        T = required.numel()
-        ptr, rows = R.group_rows(design, b.B)
-        bufs = R.ReportBuffers(b.B, k, hist, dev)
-        scratch = torch.empty((R.workspace_bytes(T, b.B, k, hist) + 7) // 8, dtype=torch.int64, device=dev)
-        return dict(k=k, hist=hist, required=required, design_ptr=torch.from_numpy(ptr).to(dev), design_rows=torch.from_numpy(rows).to(dev),
-                    bufs=bufs, scratch=scratch, ready=False)
+        return batch_tables(designs, self.batch, self.device, 'Predictor(placement=True)')
 
     def _unet_is_fused_eval(self):
         """Inside frozen_statistics: the U-Net call is unet16's eval forward (19 launches, nothing written)."""
@@ -332,41 +266,23 @@ class Predictor(ResidentDesigns):
         return out
 
     def _placed_fc(self, pmap, feat):
-        """h_cnn from the pins as they are now (train.forward_to_head's project=, placement=True)."""
-        from .placement import placed_fc
+        """h_cnn from the pins as they are now (train.forward_to_head's project=, placement=True); with trials=True the prefix
+        table it projected through is kept for trial_moves."""
         b, fcn = self.batch, self.pmodel.fcn
-        if self._trial is not None:                          # ... and the prefix table it projected through is kept for trial_moves
-            return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks,
-                             keep=self._trial.kept)
-        return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks)
+        return placed_fc(self._placed, self._sel.paths, self._sel.feat_off if b.B > 1 else None, feat, fcn.weight, fcn.bias, b.masks,
+                         keep=self._trial.kept if self._trial is not None else None)
 
     def _launches(self):
-        b, pm_, paths_d = self.batch, self.pmodel, self._sel.paths
+        b, pm_ = self.batch, self.pmodel
         h_gnn, _, pmap, h_cnn = forward_to_head(pm_, self.cnn, b, self._sel, self.h, side=self.side, cone=self.cone, sweep=self._run_sweep,
                                                 project=self._placed_fc if self._placed is not None else None)
+        pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn, keep=self._trial.kept if self._trial is not None else None)
         if self._trial is not None:
             # the references of the latest eager or capturing call: a replay rewrites those same buffers
-            kept = self._trial.kept
-            pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn, keep=kept)
-            kept['pred'], kept['mode'] = pred, lib.get_math_mode()
-        else:
-            pred = pm_.fuse_heads(h_gnn, pmap, self._sel.levels, b.L, h_cnn=h_cnn)
-        if self._report is not None:
-            from . import report as R
-            r = self._report
-            R.timing_report(pred.contiguous(), r['required'], r['design_ptr'], r['design_rows'], r['k'], r['hist'],
-                            out=r['bufs'].tensors(), workspace=r['scratch'])
-            r['ready'] = True
-        if self._crit is not None:
-            from . import criticality as K
-            c = self._crit
-            if c['sums']:                                        # one launch group: the sums' kernels write the other outputs too
-                K.criticality_sums(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B,
-                                   scale_log2=c['scale_log2'], cells=c['cells'], out=c['bufs'].tensors(), workspace=c['scratch'])
-            else:
-                K.criticality(pred.contiguous().reshape(-1), c['required'], c['placed'], paths_d, c['row_design'], b.B, cells=c['cells'],
-                              out=c['bufs'].tensors(), workspace=c['scratch'])
-            c['ready'] = True
+            self._trial.kept['pred'], self._trial.kept['mode'] = pred, lib.get_math_mode()
+        for option in (self._report, self._crit):                # after the head, in this order, as the last launches of the call
+            if option is not None:
+                option.launch(pred)
         return pred
 
     @torch.no_grad()
@@ -380,31 +296,31 @@ class Predictor(ResidentDesigns):
                 lib.get_math_mode() == 'bf16' and self._unet_is_fused_eval()
             if self.incremental:
                 self._begin_incremental()
-            if not replay:
+            if replay:
+                out = self._replayed()
+            else:
                 out = self._launches()
-                self._trusted = self.incremental_active
-                self._trial_fresh()
-                return out, self.endpoints
-            # the graph bakes in where the model lives and which modes it ran in
-            sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
-            if self.incremental:
-                sig += (self.incremental_active,)                # ... and whether its sweep is the masked one
-            if self._replay is None or sig != self._sig:
-                self._sig = sig
-                self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed,
-                                                     self.seed, self.dirty, self._crit) +
-                                               ((self._trial,) if self._trial is not None else ()))
-            out = self._replay.run(self._launches)
             self._trusted = self.incremental_active
-            self._trial_fresh()
-            if out is not None:                                  # an eager or the capturing call
-                self._out = out
-            return self._out, self.endpoints
+            if self._trial is not None:
+                self._trial.fresh()
+            return out, self.endpoints
 
-    def _trial_fresh(self):
-        """A predict() has completed: what trial_moves keeps is that of the resident designs again."""
-        if self._trial is not None:
-            self._trial.ready, self._trial.stale = True, False
+    def _replayed(self):
+        """predict()'s launches through the GraphReplay: their result on an eager or the capturing call, the static buffer the
+        captured one returned on a replay."""
+        # the graph bakes in where the model lives and which modes it ran in
+        sig = (tuple(t.data_ptr() for t in self._tensors), tuple(m.training for m in self._modules))
+        if self.incremental:
+            sig += (self.incremental_active,)                    # ... and whether its sweep is the masked one
+        if self._replay is None or sig != self._sig:
+            self._sig = sig
+            self._replay = lib.GraphReplay(keep=(self._static_idx, self.h, self.batch, self._tensors, self._report, self._placed,
+                                                 self.seed, self.dirty, self._crit) +
+                                           ((self._trial,) if self._trial is not None else ()))
+        out = self._replay.run(self._launches)
+        if out is not None:                                      # an eager or the capturing call
+            self._out = out
+        return self._out
 
     def trial_moves(self, i, pins, pin_x, pin_y, cand_ptr=None):
         """Exact predictions of design i under K candidate pin moves, each taken ALONE, from the last predict()
@@ -422,7 +338,6 @@ class Predictor(ResidentDesigns):
         Writes nothing another call reads - not loc_x / loc_y, h, the model or predict()'s static output.  Eager: refused
         under an outer stream capture.  RuntimeError without trials=True, before the first predict() and after an update() that
         no predict() has followed; ValueError outside bf16 math mode with the fused regression head."""
-        from . import trial
         return trial.trial_moves(self, i, pins, pin_x, pin_y, cand_ptr)
 
     def _begin_incremental(self):
@@ -469,32 +384,22 @@ class Predictor(ResidentDesigns):
         """The timing report of the LAST predict(): one dict per design (mmft.report.decode: n, n_nan, violations, wns,
         wns_row, tns, worst, hist, wns_endpoint, worst_endpoints; rows are rows of `pred`, endpoints in the caller's
         numbering).  One small device->host copy."""
-        from . import report as R
         if self._report is None:
             raise RuntimeError('Predictor.report(): no report was requested (report=dict(k=..., hist=...))')
-        if not self._report['ready']:
-            raise RuntimeError('Predictor.report(): predict() has not run yet')
-        return R.decode(*self._report['bufs'].host()[0], endpoints=self.endpoints)
+        self._report.check_ready('Predictor.report()')
+        return self._report.result()
 
     def criticality(self, i=None):
         """The criticality of the LAST predict(): one dict per design, or design i's (mmft.criticality.decode: node_slack,
         node_row, node_viol, node_crit in the design's own node order - node_row is a row of `pred` -, cell_slack and
         cell_viol as [map, map] arrays or None, n, n_nan; with sums=True also node_tns, cell_tns, tns, node_share, cell_share and
         saturated: mmft.criticality.decode_sums).  One device->host copy."""
-        from . import criticality as K
         if self._crit is None:
             raise RuntimeError('Predictor.criticality(): no criticality was requested (criticality=True or dict(cells=...))')
-        if not self._crit['ready']:
-            raise RuntimeError('Predictor.criticality(): predict() has not run yet')
+        self._crit.check_ready('Predictor.criticality()')
         if i is not None:
             self._check_design(i, 'criticality')
-        placed = self._crit['placed']
-        if self._crit['sums']:
-            out = K.decode_sums(*self._crit['bufs'].host(), node_off=self.batch.node_off, scale_log2=self._crit['scale_log2'],
-                                map_x=placed.map_x, map_y=placed.map_y)
-        else:
-            out = K.decode(*self._crit['bufs'].host(), node_off=self.batch.node_off, map_x=placed.map_x, map_y=placed.map_y)
-        return out if i is None else out[i]
+        return self._crit.result(i)
 
     def update(self, i, cell_feat=None, net_feat=None, image=None, pin_x=None, pin_y=None, rows=None):
         """New features (rows in design i's own node order, float32 [N_i, width]) and / or a new layout image (float32, the

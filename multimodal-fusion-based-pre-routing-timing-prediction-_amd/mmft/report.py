@@ -8,6 +8,7 @@ The rules (the header states them, `reference_report` restates them in numpy / f
   evaluate.eval_sums); a row whose slack is NaN is counted in n_nan and takes part in nothing else; the worst rows are in
   ascending (slack, batch row) order - a total order.
 """
+import functools
 import math
 
 import numpy as np
@@ -30,6 +31,57 @@ def group_rows(design_of_row, B):
     ptr = np.zeros(B + 1, dtype=np.int32)
     np.cumsum(np.bincount(d, minlength=B), out=ptr[1:])
     return ptr, rows
+
+
+class SlackRows:
+    """The slack inputs of a selection's rows, stated once for everything that forms slacks per design (the report, the
+    criticality, the trial moves, evaluate.timing_report): SlackRows(selection, batch) has
+      required     fp32 [T] on the device, Selection.required_times(batch): one gather, made here
+      design       host int64 [T], Selection.design; B, T
+      groups       (design_ptr, design_rows) of `group_rows`, int32 on the device
+      rows_of(i)   design i's rows, ascending: the slice design_rows[ptr[i]:ptr[i + 1]], a view
+      row_design   int32 [T] on the device, None when B == 1 (every row belongs to design 0): what the criticality kernels take
+    `groups` and `row_design` are uploaded once, on first use - who launches on them from a captured graph touches them when it
+    is built.  `from_rows` builds the same from a design vector and any `required` tensor, a CPU one included."""
+
+    def __init__(self, selection, batch):
+        self._fill(selection.design, batch.B, selection.required_times(batch))
+
+    @classmethod
+    def from_rows(cls, design, B, required):
+        self = cls.__new__(cls)
+        self._fill(design, B, required)
+        return self
+
+    def _fill(self, design, B, required):
+        self.design, self.B, self.T, self.required = design, int(B), int(required.numel()), required
+
+    def _put(self, a):
+        return torch.from_numpy(a).to(self.required.device)
+
+    @functools.cached_property
+    def _grouped(self):
+        ptr, rows = group_rows(self.design, self.B)
+        return ptr.tolist(), (self._put(ptr), self._put(rows))
+
+    @property
+    def groups(self):
+        return self._grouped[1]
+
+    def rows_of(self, i):
+        cuts, (_, rows) = self._grouped
+        return rows[cuts[i]:cuts[i + 1]]
+
+    @functools.cached_property
+    def row_design(self):
+        return self._put(np.asarray(self.design).astype(np.int32)) if self.B > 1 else None
+
+    @staticmethod
+    def require_regression(pmodel, who):
+        """ValueError unless the model's head is the regression head: a slack needs ONE predicted arrival time per row."""
+        nlabels = pmodel.mlp_fuse.layers[-1].out_features
+        if nlabels != 1:
+            raise ValueError(f'{who} needs the regression head (nlabels = 1), the model has {nlabels} labels')
 
 
 def _hist_args(hist):
@@ -142,6 +194,42 @@ def decode(summary, worst_row, worst_slack, hist, endpoints=None):
             d['worst_endpoints'] = [int(endpoints[r]) for r, _ in d['worst']]
         out.append(d)
     return out
+
+
+class AfterHead:
+    """What Predictor runs on its predictions after the head, as one object per option: built from the predictor -
+    all validation and every static buffer there, nothing launched -, then `launch(pred)` on the current stream inside every
+    eager or capturing predict(), which sets `ready`, and `result(...)`, the decode of the last call's buffers in one
+    device->host copy.  The Predictor keeps the object alive with its replayed graph."""
+    ready = False
+
+    def check_ready(self, what):
+        if not self.ready:
+            raise RuntimeError(f'{what}: predict() has not run yet')
+
+
+class PredictorReport(AfterHead):
+    """Predictor(report=dict(k=32, hist=(lo, hi, nbins) or None)): the report kernel on every predict()'s output and the rows'
+    slack inputs (predictor.slack); the output buffers and the scratch are static, as a replayed launch needs them."""
+
+    def __init__(self, predictor, spec):
+        unknown = set(spec) - {'k', 'hist'}
+        if unknown:
+            raise ValueError(f'Predictor: report= takes k and hist, got {sorted(unknown)}')
+        s = self.slack = predictor.slack
+        s.require_regression(predictor.pmodel, 'Predictor: report=')
+        self.k, self.hist, self.endpoints = int(spec.get('k', 32)), spec.get('hist'), predictor.endpoints
+        self.design_ptr, self.design_rows = s.groups
+        self.bufs = ReportBuffers(s.B, self.k, self.hist, predictor.device)
+        self.scratch = torch.empty((workspace_bytes(s.T, s.B, self.k, self.hist) + 7) // 8, dtype=torch.int64, device=predictor.device)
+
+    def launch(self, pred):
+        timing_report(pred.contiguous(), self.slack.required, self.design_ptr, self.design_rows, self.k, self.hist,
+                      out=self.bufs.tensors(), workspace=self.scratch)
+        self.ready = True
+
+    def result(self):
+        return decode(*self.bufs.host()[0], endpoints=self.endpoints)
 
 
 def reference_slack(pred, required):

@@ -21,7 +21,7 @@ import torch
 from . import functional as MF
 from . import lib
 from . import placement as PL
-from .report import reference_slack
+from .report import AfterHead, reference_slack
 
 abi = lib.Header('mmft_trial.h')         # trial moves: rows under a candidate's overrides, per-candidate WNS / TNS
 abi_decls = abi.decls
@@ -163,10 +163,11 @@ def decode(summary):
 
 
 # ------------------------------------------------------------------------------------------------ the Predictor's side
-class TrialState:
-    """What Predictor(trials=True) keeps for trial_moves: the static incidence of its selection, the rows of each design, and
-    `kept` - the head's input x, the prefix table GP and pred of the latest eager or capturing predict() (a replay rewrites
-    those same buffers), the math mode they were made in.  `stale`: an update() has run that no predict() has followed."""
+class TrialState(AfterHead):
+    """What Predictor(trials=True) keeps for trial_moves: the static incidence of its selection and `kept` - the head's input
+    x, the prefix table GP and pred of the latest eager or capturing predict() (a replay rewrites those same buffers), the math
+    mode they were made in.  The rows of each design and their required times are predictor.slack's (rows_of(i), required).
+    `stale`: an update() has run that no predict() has followed; `fresh()`: a predict() has."""
 
     def __init__(self, predictor):
         p = predictor
@@ -174,9 +175,12 @@ class TrialState:
         paths = sel.paths.cpu().numpy().astype(np.int64)
         self.rows_of_pin = rows_of_pin(placed.nodes.cpu().numpy(), placed.lens.cpu().numpy(), paths, placed.maxlen,
                                        int(placed.node_off[-1]))
-        design = np.asarray(p.row_design).astype(np.int64)
-        self.design_rows = [torch.from_numpy(np.flatnonzero(design == i).astype(np.int32)).to(p.device) for i in range(p.batch.B)]
-        self.kept, self.ready, self.stale = {}, False, False
+        p.slack.groups                                       # uploaded here: no trial_moves call pays for it
+        self.kept, self.stale = {}, False
+
+    def fresh(self):
+        """A predict() has completed: what trial_moves keeps is that of the resident designs again."""
+        self.ready, self.stale = True, False
 
 
 def _refuse_mode(p):
@@ -187,9 +191,7 @@ def _refuse_mode(p):
     if st.kept.get('mode') != 'bf16' or lib.get_math_mode() != 'bf16':
         raise ValueError('trial_moves: bf16 math mode only (the generic fp32 layers do not promise the same bits for a row in '
                          'another batch); predict() and trial_moves() must both run in it')
-    nlabels = mods[-1].out_features
-    if nlabels != 1:
-        raise ValueError(f'trial_moves needs the regression head (nlabels = 1), the model has {nlabels} labels')
+    p.slack.require_regression(p.pmodel, 'trial_moves')
     if len(mods) != 3 or x is None or st.kept.get('cnn_col') is None or st.kept.get('GP') is None or \
             not MF.head_mlp_usable(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, p.pmodel.mlp_fuse.negative_slope):
         raise ValueError('trial_moves needs the fused head (mmft_head_mlp_supported: 288 -> 576 -> 1, ReLU) over a head input '
@@ -206,14 +208,13 @@ def prepare(p, i, pins, pin_x, pin_y, cand_ptr=None):
         raise RuntimeError('Predictor.trial_moves(): built without trials=True')
     if torch.cuda.is_current_stream_capturing():
         raise RuntimeError('Predictor.trial_moves() under an outer stream capture: the pair list is host work done per call')
-    if not st.ready:
-        raise RuntimeError('Predictor.trial_moves(): predict() has not run yet')
+    st.check_ready('Predictor.trial_moves()')
     if st.stale:
         raise RuntimeError('Predictor.trial_moves(): update() has run since the last predict(); the kept rows are not those of '
                            'the resident designs - call predict() first')
     _refuse_mode(p)
     p._check_design(i, 'trial_moves')
-    if st.design_rows[i].numel() == 0:
+    if p.slack.rows_of(i).numel() == 0:
         raise ValueError(f'trial_moves: design {i} has no selected path')
     placed = p._placed
     off = int(placed.node_off[i])
@@ -250,8 +251,8 @@ def launch(p, plan):
         lib.head('mmft_head_mlp_fwd', xt, width, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, None, pred_t,
                  n_pairs, mods[0].weight.shape[1], mods[0].weight.shape[0], 1, *lib.stream_args(x))
         plan['xt'] = xt
-    rows = st.design_rows[plan['i']]
-    abi('mmft_trial_reduce', pred.reshape(-1), pred_t if n_pairs else None, p.required, rows, rows.numel(), T,
+    rows = p.slack.rows_of(plan['i'])
+    abi('mmft_trial_reduce', pred.reshape(-1), pred_t if n_pairs else None, p.slack.required, rows, rows.numel(), T,
         d_pptr if K else None, d_row if n_pairs else None, n_pairs, K, summary, *lib.stream_args(x))
     plan['raw'] = raw
     return plan

@@ -233,7 +233,7 @@ def test_predictor_criticality_with_a_report_and_moving_pins(dev):
                 crit = got[i]['node_crit']
                 assert crit.max() <= 1.0 and ((crit > 0) & (crit < 1)).any() and (got[i]['node_slack'][crit == 1.0] == np.float32(r['wns'])).all()
                 assert (got[i]['cell_viol'] > 0).any() and got[i]['cell_slack'].min() >= np.float32(r['wns'])
-        assert p._replay.graph is not None and p._replay.calls == 3 and p._crit in p._replay.keep and p._crit['placed'] is p._placed
+        assert p._replay.graph is not None and p._replay.calls == 3 and p._crit in p._replay.keep and p._crit.placed is p._placed
         one = p.criticality(1)
         assert np.array_equal(one['node_slack'], got[1]['node_slack']) and one['n'] == got[1]['n']
         with pytest.raises(IndexError):
@@ -263,7 +263,7 @@ def test_predictor_criticality_without_placement_mode_and_next_to_incremental_sw
         pmodel, cnn = _live_models(designs, dev)
         plain = Predictor(pmodel, cnn, designs, dev)
         p = Predictor(pmodel, cnn, designs, dev, criticality=dict(cells=False))
-        assert p._placed is None and p._crit['placed'] is not None
+        assert p._placed is None and p._crit.placed is not None
         for call in range(3):
             y0, y = plain.predict()[0], p.predict()[0]
             assert torch.equal(y, y0), call

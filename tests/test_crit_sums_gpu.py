@@ -265,7 +265,7 @@ def test_predictor_sums_eager_replayed_with_a_report_and_moving_pins(dev):
         pmodel, cnn = _live_models(designs, dev)
         plain = Predictor(pmodel, cnn, designs, dev, placement=True, criticality=True)
         p = Predictor(pmodel, cnn, designs, dev, criticality=dict(sums=True, scale_log2=L), placement=True, report=dict(k=8))
-        assert isinstance(p._crit['bufs'], K.CritSumsBuffers) and isinstance(plain._crit['bufs'], K.CritBuffers)
+        assert isinstance(p._crit.bufs, K.CritSumsBuffers) and isinstance(plain._crit.bufs, K.CritBuffers)
         with pytest.raises(RuntimeError, match='predict'):
             p.criticality()
         node_off = p.batch.node_off
@@ -290,7 +290,7 @@ def test_predictor_sums_eager_replayed_with_a_report_and_moving_pins(dev):
                 assert got[i]['tns'] < 0 and got[i]['node_tns'].min() >= got[i]['tns'] and got[i]['cell_tns'].min() >= got[i]['tns']
                 share = got[i]['node_share']
                 assert share.max() <= 1.0 and ((share > 0) & (share < 1)).any() and (got[i]['cell_share'] > 0).any()
-        assert p._replay.graph is not None and p._replay.calls == 3 and p._crit in p._replay.keep and p._crit['placed'] is p._placed
+        assert p._replay.graph is not None and p._replay.calls == 3 and p._crit in p._replay.keep and p._crit.placed is p._placed
         one = p.criticality(1)
         assert np.array_equal(one['node_tns'], got[1]['node_tns']) and one['tns'] == got[1]['tns']
         # design 1's pins move: the replayed cell sums follow them, design 0's stay
@@ -316,7 +316,7 @@ def test_predictor_sums_pins_only_without_placement_mode_and_eager(dev):
         plain = Predictor(pmodel, cnn, designs, dev)
         p = Predictor(pmodel, cnn, designs, dev, criticality=dict(cells=False, sums=True, scale_log2=30))
         e = Predictor(pmodel, cnn, designs, dev, criticality=dict(sums=True), graphed=False)
-        assert p._placed is None and p._crit['placed'] is not None and e._crit['scale_log2'] == 20
+        assert p._placed is None and p._crit.placed is not None and e._crit.scale_log2 == 20
         for call in range(3):
             y0, y, ye = plain.predict()[0], p.predict()[0], e.predict()[0]
             assert torch.equal(y, y0) and torch.equal(ye, y0), call

@@ -89,6 +89,55 @@ def test_group_rows_is_stable_and_covers_every_row_once():
         R.group_rows(np.array([0, 4]), 4)
 
 
+@pytest.mark.parametrize('design, B', [([2, 0, 3, 0, 2, 2, 0], 4),          # design 1 empty, in the middle; rows interleaved
+                                       ([0, 0, 0, 0], 1),                   # one design
+                                       ([1, 0, 2, 1, 0, 2, 2, 1, 0], 3)])   # three designs interleaved, none empty
+def test_slack_rows_state_the_grouping_once(design, B):
+    import torch
+    design = np.array(design, dtype=np.int64)
+    required = torch.arange(design.shape[0], dtype=torch.float32)
+    s = R.SlackRows.from_rows(design, B, required)
+    assert (s.B, s.T) == (B, design.shape[0]) and s.design is design and s.required is required
+    ptr, rows = R.group_rows(design, B)
+    assert all(t.dtype == torch.int32 for t in s.groups) and s.groups[0] is s.groups[0]          # made once
+    assert np.array_equal(s.groups[0].numpy(), ptr) and np.array_equal(s.groups[1].numpy(), rows)
+    for i in range(B):
+        mine = s.rows_of(i)
+        assert np.array_equal(mine.numpy(), np.flatnonzero(design == i))
+        assert mine.numel() == 0 or mine.data_ptr() == s.groups[1].data_ptr() + 4 * int(ptr[i])  # a view of the one grouping
+    assert B == 1 or s.rows_of(1).numel() == (0 if B == 4 else 3)
+    if B == 1:
+        assert s.row_design is None
+    else:
+        assert s.row_design.dtype == torch.int32 and np.array_equal(s.row_design.numpy(), design.astype(np.int32))
+        assert s.row_design is s.row_design
+
+
+def test_slack_rows_from_a_selection_gather_the_required_times_once():
+    import types
+    import torch
+    calls = []
+
+    def required_times(batch):
+        calls.append(batch)
+        return torch.tensor([3.0, 1.0, 2.0])
+    sel = types.SimpleNamespace(design=np.array([1, 0, 1], dtype=np.int64), T=3, required_times=required_times)
+    batch = types.SimpleNamespace(B=2)
+    s = R.SlackRows(sel, batch)
+    assert calls == [batch] and s.required.tolist() == [3.0, 1.0, 2.0] and s.design is sel.design and (s.B, s.T) == (2, 3)
+    assert s.rows_of(1).tolist() == [0, 2] and s.row_design.tolist() == [1, 0, 1] and calls == [batch]
+
+
+def test_require_regression_refuses_a_classification_head():
+    import types
+    head = lambda n: types.SimpleNamespace(mlp_fuse=types.SimpleNamespace(layers=[types.SimpleNamespace(out_features=n)]))
+    assert R.SlackRows.require_regression(head(1), 'Predictor: report=') is None
+    for who in ('Predictor: report=', 'Predictor: criticality=', 'trial_moves'):
+        with pytest.raises(ValueError) as e:
+            R.SlackRows.require_regression(head(2), who)
+        assert str(e.value) == f'{who} needs the regression head (nlabels = 1), the model has 2 labels'
+
+
 def test_decode_strips_padding_and_maps_endpoints():
     summary = np.array([[3, 1, 2, -2.0, 5, -2.5], [0, 2, 0, np.nan, -1, 0.0]])
     worst_row = np.array([[5, 0, 7, -1], [-1, -1, -1, -1]], dtype=np.int32)

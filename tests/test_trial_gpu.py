@@ -358,6 +358,74 @@ def test_trial_moves_on_a_128_x_128_map(dev):
     _trials_against_the_truth([d], dev, singles=1, groups=1, eager_too=False)
 
 
+def _same_bits(a, b, where='result'):
+    """Decoded results compared bitwise: dicts key by key, sequences item by item, arrays by dtype, shape and bytes, floats by
+    their fp64 bits (a NaN equals itself)."""
+    if isinstance(a, dict):
+        assert isinstance(b, dict) and sorted(a) == sorted(b), where
+        for k in a:
+            _same_bits(a[k], b[k], f'{where}[{k!r}]')
+    elif isinstance(a, (list, tuple)):
+        assert isinstance(b, (list, tuple)) and len(a) == len(b), where
+        for j, (x, y) in enumerate(zip(a, b)):
+            _same_bits(x, y, f'{where}[{j}]')
+    elif isinstance(a, np.ndarray):
+        assert isinstance(b, np.ndarray) and a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), where
+    elif isinstance(a, float):
+        assert isinstance(b, float) and np.float64(a).tobytes() == np.float64(b).tobytes(), where
+    else:
+        assert type(a) is type(b) and a == b, where
+
+
+def test_every_option_on_one_predictor_equals_each_option_alone(dev):
+    """report=, criticality= (cells and sums), placement= and trials= on ONE Predictor against four Predictors with one of them
+    each: after the same move of design 1's pins, the eager, the capturing and the replayed predict() give the same bits, and
+    so do report(), criticality() and trial_moves().  update(pin_x=) needs placement=True, so each of the four has it; the
+    option named is what it adds.  The options share the rows' slack inputs (Predictor.slack) and, here, the placement tables,
+    and launch one after another on the same predictions: that they do not disturb one another is what this pins."""
+    from mmft.infer import Predictor
+    designs = list(_small_designs())
+    assert len(designs) == 2 and designs[0].map_size ** 2 % 64 == 0
+    report, crit = dict(k=8, hist=(-1.0, 1.0, 16)), dict(cells=True, sums=True)
+    xy = C.move(designs[1], seed=75, frac=0.3)
+    with lib.math_mode('bf16'):
+        pmodel, cnn = _live_models(designs, dev)
+        combined = Predictor(pmodel, cnn, designs, dev, report=report, criticality=crit, placement=True, trials=True)
+        alone = dict(report=Predictor(pmodel, cnn, designs, dev, placement=True, report=report),
+                     criticality=Predictor(pmodel, cnn, designs, dev, placement=True, criticality=crit),
+                     placement=Predictor(pmodel, cnn, designs, dev, placement=True),
+                     trials=Predictor(pmodel, cnn, designs, dev, placement=True, trials=True))
+        objs = [combined] + list(alone.values())
+        assert combined._crit.placed is combined._placed and combined._report.slack is combined._crit.slack is combined.slack
+        # required times a hair above and below the moved predictions: about every other row violates
+        probe = Predictor(pmodel, cnn, designs, dev, placement=True, graphed=False)
+        unmoved = probe.predict()[0].clone()
+        probe.update(1, pin_x=xy[0], pin_y=xy[1])
+        first = probe.predict()[0].clone()
+        assert not torch.equal(first, unmoved)                                    # the move shows
+        sign = torch.where(torch.arange(first.numel(), device=dev) % 2 == 0, 1.0, -1.0)
+        near = (first + sign * first.abs().clamp_min(1e-3) * 2.0 ** -18).to(torch.float32)
+        for q in objs:
+            q.update(1, pin_x=xy[0], pin_y=xy[1])
+            q.required.copy_(near)
+        calls = _candidates(combined._trial, designs, combined._placed.node_off, 0, singles=3, groups=1)
+        for call in range(3):                                                     # eager, the capturing call, a replay
+            y, ends = combined.predict()
+            assert np.array_equal(U32(y.cpu().numpy()), U32(first.cpu().numpy())), call
+            for name, q in alone.items():
+                yq, eq = q.predict()
+                assert torch.equal(yq, y) and np.array_equal(eq, ends), (call, name)
+            rep = combined.report()
+            _same_bits(rep, alone['report'].report(), f'call {call}: report')
+            _same_bits(combined.criticality(), alone['criticality'].criticality(), f'call {call}: criticality')
+            assert all(0 < r['violations'] < r['n'] for r in rep)
+            for i, (pins, x, py, ptr) in enumerate(calls):
+                _same_bits(combined.trial_moves(i, pins, x, py, ptr), alone['trials'].trial_moves(i, pins, x, py, ptr),
+                           f'call {call}: trial_moves({i})')
+        assert combined._replay.graph is not None and combined._replay.calls == 3
+        assert all(q._replay.graph is not None and q._replay.calls == 3 for q in alone.values())
+
+
 # ------------------------------------------------------------------------------------------------ 5. state and refusals
 def test_state_and_refusals(dev):
     from mmft.infer import Predictor

@@ -97,8 +97,8 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     p = preds['predict_crit']
     c = p._crit
     paths = p._sel[1].cpu().numpy().astype(np.int64)
-    nodes, lens = c['placed'].nodes.cpu().numpy(), c['placed'].lens.cpu().numpy()
-    design = np.zeros(paths.shape[0], dtype=np.int64) if c['row_design'] is None else c['row_design'].cpu().numpy().astype(np.int64)
+    nodes, lens = c.placed.nodes.cpu().numpy(), c.placed.lens.cpu().numpy()
+    design = np.zeros(paths.shape[0], dtype=np.int64) if c.row_design is None else c.row_design.cpu().numpy().astype(np.int64)
     cells_of = np.concatenate([np.diff(d.mask_indptr) for d in designs])
     pin_pairs, cell_pairs = int(np.minimum(lens, nodes.shape[1])[paths].sum()), int(cells_of[paths].sum())
     emit(row='shapes', designs=a.designs, map=m, rows=int(paths.shape[0]), pins=int(nodes.max()) + 1, maxlen=int(nodes.shape[1]),
@@ -106,9 +106,9 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
 
     # the device result against the numpy restatement, from the same predictions
     pred = ys[0].cpu().numpy().reshape(-1)
-    required = c['required'].cpu().numpy()
+    required = c.required.cpu().numpy()
     px, py = np.concatenate([d.pin_x for d in designs]), np.concatenate([d.pin_y for d in designs])
-    got = c['bufs'].host()
+    got = c.bufs.host()
     ref = K.reference_criticality(pred, required, nodes, lens, px, py, m, m, paths, design if len(designs) > 1 else None, got[0].shape[0],
                                   len(designs), masks=(np.concatenate([[0], np.cumsum(cells_of)]), np.concatenate([d.mask_cols for d in designs])))
     bits = lambda x: np.ascontiguousarray(x).view(np.int32)
@@ -122,8 +122,8 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
         ref13 = K.reference_criticality_sums(pred, required, nodes, lens, px, py, m, m, paths, design if len(designs) > 1 else None,
                                              got[0].shape[0], len(designs), scale_log2=a.scale_log2, masks=masks)
         bits13 = lambda x: np.ascontiguousarray(x).view(np.int32 if x.dtype.itemsize == 4 else np.int64)
-        got13 = preds['predict_crit_sums']._crit['bufs'].host()
-        pins13 = preds['predict_crit_sums_pins']._crit['bufs'].host()
+        got13 = preds['predict_crit_sums']._crit.bufs.host()
+        pins13 = preds['predict_crit_sums_pins']._crit.bufs.host()
         same13 = all(np.array_equal(bits13(g), bits13(r)) for g, r in zip(got13, ref13))
         same_pins = all(np.array_equal(bits13(g), bits13(r)) for g, r in zip(pins13, ref13) if g is not None)
         emit(row='outputs_sums', equals_reference_bitwise=bool(same13), pins_only_equals_reference_bitwise=bool(same_pins),
@@ -136,15 +136,15 @@ def criticality_rows(a, emit, designs, ids, pmodel, cnn, dev):
     # replayed predict() with and without the option, and the three launches alone
     def alone(q):
         k = q._crit
-        return lambda: K.criticality(ys[0].reshape(-1), k['required'], k['placed'], q._sel[1], k['row_design'], len(designs), cells=k['cells'],
-                                     out=k['bufs'].tensors(), workspace=k['scratch'])
+        return lambda: K.criticality(ys[0].reshape(-1), k.required, k.placed, q._sel[1], k.row_design, len(designs), cells=k.cells,
+                                     out=k.bufs.tensors(), workspace=k.scratch)
     rows = {nm: (lambda q=q: q.predict()[0]) for nm, q in preds.items()}
     rows['crit_alone_pins'], rows['crit_alone'] = alone(preds['predict_crit_pins']), alone(p)
 
     def sums_alone(q):
         k = q._crit
-        return lambda: K.criticality_sums(ys[0].reshape(-1), k['required'], k['placed'], q._sel[1], k['row_design'], len(designs),
-                                          scale_log2=k['scale_log2'], cells=k['cells'], out=k['bufs'].tensors(), workspace=k['scratch'])
+        return lambda: K.criticality_sums(ys[0].reshape(-1), k.required, k.placed, q._sel[1], k.row_design, len(designs),
+                                          scale_log2=k.scale_log2, cells=k.cells, out=k.bufs.tensors(), workspace=k.scratch)
     if not a.no_sums:
         rows['crit_sums_alone_pins'], rows['crit_sums_alone'] = sums_alone(preds['predict_crit_sums_pins']), sums_alone(preds['predict_crit_sums'])
     for fn in rows.values():
@@ -265,7 +265,7 @@ def trials_rows(a, emit, designs, ids, pmodel, cnn, dev):
     groups = np.concatenate([rng.choice(on, 8, replace=False) for _ in range(a.candidates // 8)]).astype(np.int64)
     sets = {'trials_single': (single, *moved_to(single), None),
             'trials_group8': (groups, *moved_to(groups), np.arange(0, groups.shape[0] + 1, 8, dtype=np.int64))}
-    emit(row='trials_shapes', designs=a.designs, map=m, rows=int(p.T), rows_design0=int(p._trial.design_rows[0].numel()),
+    emit(row='trials_shapes', designs=a.designs, map=m, rows=int(p.T), rows_design0=int(p.slack.rows_of(0).numel()),
          row_pin_first_occurrences=int(ptr[-1]), pins_on_a_row_design0=int(on.size), rows_per_such_pin_mean=float(count[on].mean()))
 
     def staged(args):

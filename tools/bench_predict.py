@@ -129,8 +129,8 @@ def run_config(name, cfg, a, emit, dev):
             hist = (-1.0, 1.0, 32)
             pr = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, report=dict(k=a.report, hist=hist))
             ph = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
-            host = dict(required=pr._report['required'].cpu().numpy(), ptr=pr._report['design_ptr'].cpu().numpy(),
-                        rows=pr._report['design_rows'].cpu().numpy())
+            host = dict(required=pr.slack.required.cpu().numpy(), ptr=pr.slack.groups[0].cpu().numpy(),
+                        rows=pr.slack.groups[1].cpu().numpy())
             last = {}
 
             def graph_report():
