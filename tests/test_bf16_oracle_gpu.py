@@ -24,7 +24,9 @@ would fail, so the test sees where rounding happens) depends on the part of the 
     every parameter gradient in relative L2 (ceiling 0.35; OutConv's bias gradient, one cancelling sum of +-g, relative to
     the sum of |g| it adds up), the mean over all tensors (ceiling 0.25), output and running statistics; teeth per group:
     the plain oracle's mean distance exceeds 1.5 x the HIP result's.  The proposed 2e-2 ceiling and 10 x teeth are out of
-    reach here for the reason above.
+    reach here for the reason above.  These whole-network bounds are therefore loose - a wrong BatchNorm backward term or
+    a misrouted gradient would pass them - and tests/test_unet_stages_gpu.py is where a wrong stage is caught: it feeds
+    every stage of one real step its own stored inputs and holds it to the fp64 stage reference almost bit for bit.
 """
 import numpy as np
 import pytest

@@ -350,7 +350,9 @@ def test_unet_module_bf16_storage_vs_fp64_oracle(dev, N, H, W, pooling):
     """UNet.forward + backward on the bf16-storage path (bf16 math mode) against the fp64 oracle run image by image: output
     within 5e-2 of its scale, gradient directions cos >= 0.8 per tensor and >= 0.93 on average (14 chained BatchNorm layers
     on bf16 activations), running statistics within 1e-2; two runs are bitwise equal; the per-operator path of the same
-    math mode (unet16.ENABLED = False) is no closer to fp64 than 2.5x."""
+    math mode (unet16.ENABLED = False) is no closer to fp64 than 2.5x.  These bounds are loose because the 14 chained
+    BatchNorm layers turn last-bit differences into bf16-sized ones; tests/test_unet_stages_gpu.py, which checks every
+    stage of one step on its own stored inputs, is where a wrong stage is caught."""
     import Unet
     from oracle import restatement as R
 
