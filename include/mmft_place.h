@@ -7,7 +7,7 @@
  *
  * THE MASK RULE (the rule of path_mask_kernel in csrc/prep.hip, reference src/verilog_parser_asap7.py:1302-1369; stated
  * here once, restated in numpy by mmft.placement.rasterize_host; its device code is csrc/mask_rule.h, which every kernel
- * that builds a mask or moves a pin of one calls: prep.hip, place.hip, crit.hip, pin_move.hip, trial.hip):
+ * that builds a mask or moves a pin of one calls: prep.hip, place.hip, crit.hip, pin_move.hip, trial.hip, search.hip):
  *
  *   The mask of path q over a map_x x map_y map is the union, over the consecutive node pairs (path[j], path[j + 1]) with
  *   j + 1 < min(path_lens[q], maxlen), of the boxes [min x, max x] x [min y, max y] of the two pins' map cells, where

@@ -24,6 +24,7 @@
 #include "common.h"
 #include "mask_rule.h"
 #include "slack_key.h"
+#include "slack_quanta.h"
 #include "../../include/mmft_crit.h"
 #include "../../include/mmft_crit_sums.h"
 
@@ -68,16 +69,7 @@ struct CritArgs {
   float* cell_share;
 };
 
-// The quanta of a violating slack s < 0 (-inf included): rint(min(-s, 2^(32 - L)) * 2^L), exactly.  The scaling by a power of
-// two is exact in fp32 (it only raises the exponent; a denormal scaled by at most 2^30 rounds to 0 whether or not it is flushed
-// first), rintf rounds to nearest even, and below the cap the result is an integer fp32 below 2^32 (at most 2^32 - 256), which
-// the conversion to unsigned takes as it is.
-__device__ __forceinline__ crit_u64 crit_quanta(float s, int scale_log2, bool& capped) {
-  const float m = -s;
-  capped = m >= ldexpf(1.f, 32 - scale_log2);
-  const unsigned below = (unsigned)rintf(ldexpf(capped ? 0.f : m, scale_log2));    // (never converts a value out of range)
-  return capped ? (1ull << 32) : (crit_u64)below;
-}
+// The quanta of a violating slack: crit_quanta (slack_quanta.h), shared with the window search.
 
 template <bool SUMS>
 __global__ void __launch_bounds__(CRIT_THREADS) crit_init_kernel(CritArgs a) {

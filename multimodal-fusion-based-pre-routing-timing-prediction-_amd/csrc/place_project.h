@@ -17,7 +17,7 @@ constexpr int PLACE_LIST = 1024;            // masks of up to this many runs (bo
 // Dynamic LDS only (a static array in front of it would move its base off 16 bytes):
 //   part [256] f32x4 | list [PLACE_LIST] unsigned | cnt [nblk + 1] int, padded to 16 bytes | red [8] int | pin [2][256] int |
 //   bits [P / 32] unsigned                 (at MASK_MAX_CELLS: bitmap 8 KB, block counts 4 KB)
-// What a kernel keeps besides (trial.hip: a candidate's overrides) goes behind the bitmap.
+// What a kernel keeps besides (trial_row.h: the overrides of a row) goes behind the bitmap.
 __host__ __device__ inline int place_cnt_slots(int nblk) { return (nblk + 1 + 3) & ~3; }
 inline size_t place_lds_bytes(int P) {
   return 256 * sizeof(f32x4) + (size_t)(PLACE_LIST + place_cnt_slots(P >> 6) + 8 + 512) * 4 + (size_t)(P >> 5) * 4;

@@ -3,79 +3,44 @@
 // trial_rows_kernel: one workgroup per (row, candidate) pair.  The candidate's overrides are staged in LDS, the row's mask is
 // rasterised with them (mask_raster_path_moved, mask_rule.h: the boxes of mask_raster_path, on the same mask_or_box) and
 // projected by place_project (place_project.h), the function placed_fc_fwd_kernel calls - the h_cnn columns are that kernel's
-// bits on moved tables, and the tables are never written.  The row's other columns are copied.
+// bits on moved tables, and the tables are never written.  The row's other columns are copied.  Everything after the staging
+// is trial_row_write (trial_row.h), which search.hip calls too.
 // trial_reduce_kernel: one workgroup per candidate walks the design's rows, takes the trial prediction where the candidate has
 // a pair and the resident one elsewhere, and reduces counts, the worst (slack, row) key and the fp64 negative sum in one fixed
 // tree.
 #include "common.h"
-#include "mask_rule.h"
-#include "place_project.h"
 #include "slack_key.h"
+#include "trial_row.h"
 #include "../../include/mmft_trial.h"
 
 namespace mmft {
 
-constexpr int TRIAL_MOVES = 64;              // moves of one candidate, staged behind the bitmap: [3][TRIAL_MOVES] int
-inline size_t trial_lds_bytes(int P) { return place_lds_bytes(P) + 3 * TRIAL_MOVES * 4; }
-
 struct TrialRowsArgs {
-  const int* path_nodes;
-  const int* path_lens;
-  const int* loc_x;
-  const int* loc_y;
-  const int* paths;
-  const int* foff;
+  TrialRowArgs row;
   const int* pair_row;
   const int* pair_cand;
   const int* mv_ptr;
   const int* mv_node;
   const int* mv_x;
   const int* mv_y;
-  const float* GP;
-  const float* bias;
-  const float* x;
-  float* xt;
-  long long ldx, ldxt;
-  int maxlen, map_x, map_y, width, cnn_col, Dout;
 };
 
 __global__ void __launch_bounds__(256) trial_rows_kernel(TrialRowsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char trial_smem[];
-  const int P = a.map_x * a.map_y, words = P >> 5, nblk = P >> 6;
-  const PlaceLds L = place_lds(trial_smem, nblk);
-  int* mv_node = reinterpret_cast<int*>(L.bits + words);
-  int* mv_x = mv_node + TRIAL_MOVES;
-  int* mv_y = mv_x + TRIAL_MOVES;
+  const int P = a.row.map_x * a.row.map_y;
+  const PlaceLds L = place_lds(trial_smem, P >> 6);
+  const TrialMoves mv = trial_moves_lds(L, P);
   const int p = blockIdx.x, tid = threadIdx.x;
   const int t = a.pair_row[p], k = a.pair_cand[p];
   const int m0 = a.mv_ptr[k];
   int n_mv = a.mv_ptr[k + 1] - m0;                      // the same for every thread
   n_mv = n_mv < 0 ? 0 : (n_mv > TRIAL_MOVES ? TRIAL_MOVES : n_mv);
   if (tid < n_mv) {
-    mv_node[tid] = a.mv_node[m0 + tid];
-    mv_x[tid] = a.mv_x[m0 + tid];
-    mv_y[tid] = a.mv_y[m0 + tid];
+    mv.node[tid] = a.mv_node[m0 + tid];
+    mv.x[tid] = a.mv_x[m0 + tid];
+    mv.y[tid] = a.mv_y[m0 + tid];
   }
-  for (int w = tid; w < words; w += 256) L.bits[w] = 0u;
-  // ---- the columns around h_cnn: the row as the resident batch has it
-  {
-    const float* src = a.x + (long long)t * a.ldx;
-    float* dst = a.xt + (long long)p * a.ldxt;
-    const int rest = a.width - a.Dout;                  // columns [0, cnn_col) and [cnn_col + Dout, width)
-    for (int c = tid; c < rest; c += 256) {
-      const int col = c < a.cnn_col ? c : c + a.Dout;
-      dst[col] = src[col];
-    }
-  }
-  // ---- the union of boxes under the candidate: THE MASK RULE, staged, with the overrides applied at the staging
-  const int q = a.paths[t];
-  const int* path = a.path_nodes + (long long)q * a.maxlen;
-  const int len = a.path_lens[q] < a.maxlen ? a.path_lens[q] : a.maxlen;
-  mask_raster_path_moved<256>(L.bits, L.pin_x, L.pin_y, path, len, a.loc_x, a.loc_y, mv_node, mv_x, mv_y, n_mv, a.map_x, a.map_y, tid);
-  __syncthreads();
-  // ---- the runs numbered and accumulated through the prefix table (place_project.h)
-  place_project(L, nblk, a.GP + (long long)(a.foff ? a.foff[t] : 0) * a.Dout, a.bias, a.xt + (long long)p * a.ldxt + a.cnn_col, a.Dout,
-                nullptr, tid);
+  trial_row_write(a.row, L, mv, n_mv, t, p, tid);       // trial_row.h: the copy, the raster under the overrides, the projection
 }
 
 typedef unsigned long long trial_u64;
@@ -183,10 +148,11 @@ int mmft_trial_rows(const int* path_nodes, const int* path_lens, int maxlen, con
   int arc = ensure_dyn_lds(once, (const void*)trial_rows_kernel, (int)trial_lds_bytes(MASK_MAX_CELLS), "trial_rows");
   if (arc) return arc;
   TrialRowsArgs a;
-  a.path_nodes = path_nodes; a.path_lens = path_lens; a.loc_x = loc_x; a.loc_y = loc_y; a.paths = paths; a.foff = f_off;
+  TrialRowArgs& r = a.row;
+  r.path_nodes = path_nodes; r.path_lens = path_lens; r.loc_x = loc_x; r.loc_y = loc_y; r.paths = paths; r.foff = f_off;
+  r.GP = GP; r.bias = bias; r.x = x; r.xt = xt; r.ldx = ldx; r.ldxt = ldxt;
+  r.maxlen = maxlen; r.map_x = map_x; r.map_y = map_y; r.width = width; r.cnn_col = cnn_col; r.Dout = Dout;
   a.pair_row = pair_row; a.pair_cand = pair_cand; a.mv_ptr = mv_ptr; a.mv_node = mv_node; a.mv_x = mv_x; a.mv_y = mv_y;
-  a.GP = GP; a.bias = bias; a.x = x; a.xt = xt; a.ldx = ldx; a.ldxt = ldxt;
-  a.maxlen = maxlen; a.map_x = map_x; a.map_y = map_y; a.width = width; a.cnn_col = cnn_col; a.Dout = Dout;
   MMFT_LAUNCH_LDS("trial_rows_kernel", 0.0, 0.0, trial_rows_kernel, dim3(n_pairs), dim3(256), trial_lds_bytes(P), (hipStream_t)stream, a);
   return check_launch("trial_rows");
 }

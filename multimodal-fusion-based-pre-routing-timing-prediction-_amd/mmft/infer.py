@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import gradsink, lib, ops, trial
+from . import gradsink, lib, ops, search, trial
 from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
 from .placement import batch_tables, placed_fc
@@ -206,7 +206,10 @@ class Predictor(ResidentDesigns):
                           masked projection and its predictions, and trial_moves(i, pins, pin_x, pin_y, cand_ptr) returns the
                           exact predictions and WNS / TNS of design i under a batch of candidate pin moves, each taken alone,
                           without writing the placement (mmft.trial, include/mmft_trial.h).  bf16 math mode with the fused
-                          regression head.  Left at False, nothing about the object, its launches or its results changes
+                          regression head.  search_plan(i, pins, group_ptr) / search_moves(plan, radius) enumerate a window
+                          of rigid displacements per pin group on the device instead and return every candidate's score and the
+                          best offset per group (mmft.search, include/mmft_search.h); they need nothing more at construction.
+                          Left at False, nothing about the object, its launches or its results changes
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
 
@@ -339,6 +342,38 @@ class Predictor(ResidentDesigns):
         under an outer stream capture.  RuntimeError without trials=True, before the first predict() and after an update() that
         no predict() has followed; ValueError outside bf16 math mode with the fused regression head."""
         return trial.trial_moves(self, i, pins, pin_x, pin_y, cand_ptr)
+
+    def search_plan(self, i, pins, group_ptr=None):
+        """The static tables of G pin groups of design i for search_moves (trials=True; mmft.search).  pins: int64 [M] node ids in
+        design i's own numbering; group_ptr: int64 [G + 1], CSR over pins - non-decreasing, from 0 to M -, None: every pin a
+        group of its own.  A group is a set of at most 64 distinct pins that move rigidly together (a cell).  Host work and ONE
+        upload, no launch: per group the ascending union of its pins' rows (grow_ptr, grow_row), the group of each entry
+        (grow_grp) and the groups' pins in the tables' numbering (mv_ptr, mv_node).  The plan stays valid for the life of this
+        Predictor - the incidence is static, pin moves do not change it - and belongs to it alone.
+        RuntimeError without trials=True; TypeError / IndexError / ValueError as trial_moves validates its pins."""
+        return search.search_plan(self, i, pins, group_ptr)
+
+    def search_moves(self, plan, radius=1, scale_log2=20, max_rows=65536):
+        """Every displacement of every group of `plan` within a window, each taken ALONE, scored exactly from the last
+        predict() (mmft.search, include/mmft_search.h).  radius r in [1, 8]: W = (2 r + 1)^2 offsets, offset w = (dx, dy) =
+        (w // (2 r + 1) - r, w % (2 r + 1) - r), x the first map axis, the centre w = 2 r (r + 1) the zero move; under (g, w)
+        the pins of group g sit at their resident coordinates + (dx, dy), saturated to int32.  The window is enumerated on
+        the device in chunks of max(1, max_rows // R) offsets (R: the plan's entries), which bounds the buffer of head input
+        rows; the results do not depend on max_rows.  No host table is built per call.
+
+        Returns host data (one device -> host copy), tables [G, W]: dq int64 - the change of the design's sum of negative-slack
+        quanta of 2^-scale_log2 (THE QUANTUM of mmft_crit_sums.h): -dq * 2^-scale_log2 is the candidate's TNS gain, negative dq
+        an improvement -, dviol (change of the number of violating rows), new_nan (rows whose slack becomes NaN; a candidate
+        is eligible iff 0), capped (rows at the quantum's cap), worst / worst_row (the smallest valid slack among the group's
+        rows under the candidate, NaN / -1 without one); per group best_w, best_dx, best_dy, best_dq, best_gain - the eligible
+        offset with the smallest (dq, |dx| + |dy|, w); best_w == centre: no move in the window helps -; base: nsum, violations,
+        n_nan of design i on the pins as they are; grow_ptr and rows from the plan.
+
+        Writes nothing another call reads.  Refusals as trial_moves: RuntimeError without trials=True, under an outer stream
+        capture, before the first predict() and after an update() no predict() has followed; ValueError outside bf16 math mode
+        with the fused regression head, for a radius outside [1, 8], a scale_log2 outside [0, 30], max_rows < 1, R * W >= 2^31
+        and a plan of another Predictor."""
+        return search.search_moves(self, plan, radius, scale_log2, max_rows)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

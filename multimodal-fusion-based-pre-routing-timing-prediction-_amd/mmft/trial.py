@@ -39,15 +39,40 @@ def rows_of_pin(path_nodes, path_lens, paths, maxlen, n_nodes):
     return ptr, slot // int(maxlen)
 
 
-def _host(a, name, kinds):
-    """`a` (numpy array or tensor) as a host numpy array of one of the dtypes `kinds`, 1-D."""
+def _host(a, name, kinds, who='trial_moves'):
+    """`a` (numpy array or tensor) as a host numpy array of one of the dtypes `kinds`, 1-D; `who` names the caller's method."""
     h = a.detach().cpu().numpy() if torch.is_tensor(a) else a
     if not isinstance(h, np.ndarray) or h.dtype not in kinds:
-        raise TypeError(f'trial_moves: {name} must be a numpy array or tensor of {" or ".join(np.dtype(k).name for k in kinds)}, '
+        raise TypeError(f'{who}: {name} must be a numpy array or tensor of {" or ".join(np.dtype(k).name for k in kinds)}, '
                         f'got {getattr(h, "dtype", type(a).__name__)}')
     if h.ndim != 1:
-        raise ValueError(f'trial_moves: {name} must be 1-D, got shape {h.shape}')
+        raise ValueError(f'{who}: {name} must be 1-D, got shape {h.shape}')
     return h
+
+
+def check_pin_sets(n_nodes, pins, ptr=None, who='trial_moves', ptr_name='cand_ptr', unit='candidate', item='moves'):
+    """(pins int64 [M], ptr int64 [K + 1]) or an exception: the part of `check_moves` that has no coordinates - sets of at most
+    MAX_MOVES distinct pins, CSR over `pins`; None: every pin a set of its own.  search.check_groups is this under its own names."""
+    pins = _host(pins, 'pins', (np.int64,), who)
+    M = pins.shape[0]
+    if M and (int(pins.min()) < 0 or int(pins.max()) >= n_nodes):
+        raise IndexError(f'{who}: pins outside the design\'s {n_nodes} nodes')
+    if ptr is None:
+        ptr = np.arange(M + 1, dtype=np.int64)
+    else:
+        ptr = _host(ptr, ptr_name, (np.int64,), who)
+        if ptr.shape[0] < 1 or int(ptr[0]) != 0:
+            raise ValueError(f'{who}: {ptr_name} must start at 0')
+        if (np.diff(ptr) < 0).any():
+            raise ValueError(f'{who}: {ptr_name} must not decrease')
+        if int(ptr[-1]) != M:
+            raise ValueError(f'{who}: {ptr_name} must end at the number of {item}, {M}, got {int(ptr[-1])}')
+        if ptr.shape[0] > 1 and int(np.diff(ptr).max()) > MAX_MOVES:
+            raise ValueError(f'{who}: a {unit} holds {int(np.diff(ptr).max())} {item}, at most {MAX_MOVES} are supported')
+        cand = np.repeat(np.arange(ptr.shape[0] - 1, dtype=np.int64), np.diff(ptr))
+        if np.unique(cand * max(int(n_nodes), 1) + pins).shape[0] != M:
+            raise ValueError(f'{who}: the same pin twice in one {unit}')
+    return np.ascontiguousarray(pins), np.ascontiguousarray(ptr)
 
 
 def check_moves(n_nodes, pins, pin_x, pin_y, cand_ptr=None):
@@ -55,8 +80,7 @@ def check_moves(n_nodes, pins, pin_x, pin_y, cand_ptr=None):
     TypeError for a wrong type or dtype, IndexError for a pin outside [0, n_nodes), ValueError for everything else: shapes,
     coordinates beyond 32 bits, a cand_ptr that does not start at 0 / decreases / does not end at M, a candidate of more than
     MAX_MOVES moves, a pin twice in one candidate."""
-    pins = _host(pins, 'pins', (np.int64,))
-    M = pins.shape[0]
+    M = _host(pins, 'pins', (np.int64,)).shape[0]
     xy = []
     for name, a in (('pin_x', pin_x), ('pin_y', pin_y)):
         h = _host(a, name, (np.int32, np.int64))
@@ -65,24 +89,8 @@ def check_moves(n_nodes, pins, pin_x, pin_y, cand_ptr=None):
         if h.dtype == np.int64 and M and (int(h.max()) >= 2 ** 31 or int(h.min()) < -2 ** 31):
             raise ValueError(f'trial_moves: {name} does not fit 32-bit integers')
         xy.append(h.astype(np.int32))
-    if M and (int(pins.min()) < 0 or int(pins.max()) >= n_nodes):
-        raise IndexError(f'trial_moves: pins outside the design\'s {n_nodes} nodes')
-    if cand_ptr is None:
-        ptr = np.arange(M + 1, dtype=np.int64)
-    else:
-        ptr = _host(cand_ptr, 'cand_ptr', (np.int64,))
-        if ptr.shape[0] < 1 or int(ptr[0]) != 0:
-            raise ValueError('trial_moves: cand_ptr must start at 0')
-        if (np.diff(ptr) < 0).any():
-            raise ValueError('trial_moves: cand_ptr must not decrease')
-        if int(ptr[-1]) != M:
-            raise ValueError(f'trial_moves: cand_ptr must end at the number of moves, {M}, got {int(ptr[-1])}')
-        if ptr.shape[0] > 1 and int(np.diff(ptr).max()) > MAX_MOVES:
-            raise ValueError(f'trial_moves: a candidate holds {int(np.diff(ptr).max())} moves, at most {MAX_MOVES} are supported')
-        cand = np.repeat(np.arange(ptr.shape[0] - 1, dtype=np.int64), np.diff(ptr))
-        if np.unique(cand * max(int(n_nodes), 1) + pins).shape[0] != M:
-            raise ValueError('trial_moves: the same pin twice in one candidate')
-    return np.ascontiguousarray(pins), xy[0], xy[1], np.ascontiguousarray(ptr)
+    pins, ptr = check_pin_sets(n_nodes, pins, cand_ptr)
+    return pins, xy[0], xy[1], ptr
 
 
 def expand_candidates(rows_of_pin, node_off, pins, cand_ptr):
@@ -183,36 +191,44 @@ class TrialState(AfterHead):
         self.ready, self.stale = True, False
 
 
-def _refuse_mode(p):
+def _refuse_mode(p, who='trial_moves'):
     """ValueError unless the kept predict() and this call are what the bitwise contract covers: bf16 math mode, the
     regression head, the fused head kernel, h_cnn in the head's input."""
     st = p._trial
     x, mods = st.kept.get('x'), list(p.pmodel.mlp_fuse.layers)
     if st.kept.get('mode') != 'bf16' or lib.get_math_mode() != 'bf16':
-        raise ValueError('trial_moves: bf16 math mode only (the generic fp32 layers do not promise the same bits for a row in '
-                         'another batch); predict() and trial_moves() must both run in it')
-    p.slack.require_regression(p.pmodel, 'trial_moves')
+        raise ValueError(f'{who}: bf16 math mode only (the generic fp32 layers do not promise the same bits for a row in '
+                         f'another batch); predict() and {who}() must both run in it')
+    p.slack.require_regression(p.pmodel, who)
     if len(mods) != 3 or x is None or st.kept.get('cnn_col') is None or st.kept.get('GP') is None or \
             not MF.head_mlp_usable(x, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, p.pmodel.mlp_fuse.negative_slope):
-        raise ValueError('trial_moves needs the fused head (mmft_head_mlp_supported: 288 -> 576 -> 1, ReLU) over a head input '
+        raise ValueError(f'{who} needs the fused head (mmft_head_mlp_supported: 288 -> 576 -> 1, ReLU) over a head input '
                          'that holds h_cnn')
     if x.stride(1) != 1 or x.stride(0) % 4 or x.data_ptr() % 16:
-        raise ValueError('trial_moves: the head\'s input rows are not 16-byte aligned')
+        raise ValueError(f'{who}: the head\'s input rows are not 16-byte aligned')
+
+
+def check_state(p, who='trial_moves', why='the pair list is host work done per call'):
+    """The state and mode refusals of a call that reads what predict() kept (trial_moves, search_moves): RuntimeError without
+    trials=True, under an outer stream capture, before the first predict() and after an update() no predict() has followed;
+    ValueError outside bf16 math mode with the fused regression head.  Returns the TrialState."""
+    st = getattr(p, '_trial', None)
+    if st is None:
+        raise RuntimeError(f'Predictor.{who}(): built without trials=True')
+    if torch.cuda.is_current_stream_capturing():
+        raise RuntimeError(f'Predictor.{who}() under an outer stream capture: {why}')
+    st.check_ready(f'Predictor.{who}()')
+    if st.stale:
+        raise RuntimeError(f'Predictor.{who}(): update() has run since the last predict(); the kept rows are not those of '
+                           'the resident designs - call predict() first')
+    _refuse_mode(p, who)
+    return st
 
 
 def prepare(p, i, pins, pin_x, pin_y, cand_ptr=None):
     """Stage 1, host: state and mode refusals, validation, the pair list, ONE upload of the call's integer tables.  Returns the
     plan `launch` takes.  Nothing is launched."""
-    st = getattr(p, '_trial', None)
-    if st is None:
-        raise RuntimeError('Predictor.trial_moves(): built without trials=True')
-    if torch.cuda.is_current_stream_capturing():
-        raise RuntimeError('Predictor.trial_moves() under an outer stream capture: the pair list is host work done per call')
-    st.check_ready('Predictor.trial_moves()')
-    if st.stale:
-        raise RuntimeError('Predictor.trial_moves(): update() has run since the last predict(); the kept rows are not those of '
-                           'the resident designs - call predict() first')
-    _refuse_mode(p)
+    st = check_state(p)
     p._check_design(i, 'trial_moves')
     if p.slack.rows_of(i).numel() == 0:
         raise ValueError(f'trial_moves: design {i} has no selected path')

@@ -3,6 +3,8 @@
     python tools/bench_placement.py [--designs 8] [--paths 1350] [--reps 20] [--rounds 7] [--rebuilds 3] [--out FILE]
     python tools/bench_placement.py --trace        (the launches alone, for a kernel trace of its own)
     python tools/bench_placement.py --criticality  (what Predictor(criticality=...) adds to a replayed predict(), see below)
+    python tools/bench_placement.py --trials       (one trial_moves call over many candidates, see below)
+    python tools/bench_placement.py --search       (one search_moves call over a window per pin group, see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -40,6 +42,16 @@ predict() for 64 of the same single-pin candidates one after another, their pins
 (sequential_update_predict, host clock around the 64, per trial).  The trial predictions of those 64 must equal the sequential
 ones bitwise.  speedup_over_sequential = K sequential trials / one call; beats_64_sequential_trials says whether one call of K
 candidates costs less than 64 sequential trials.
+
+--search [--groups 4096] [--radius 2], on the same designs (nothing of the above is run): ONE Predictor.search_moves call over
+4096 single-pin groups of design 0 at radius 2 (search_single: 102 400 candidates) and over 512 groups of 8 pins (search_group8),
+required times at the median prediction: host milliseconds of search_plan, once per set of groups (plan_ms), and per call the
+host milliseconds of the refusals and the buffer (host_ms), device milliseconds of the launches (launches_ms, events), host
+milliseconds of the copy back and decoding (copy_back_ms) and the whole call under one host clock (call_ms).  Next to each,
+alternating inside the same rounds, Predictor.trial_moves on the SAME candidates written out by the host (trial_route_single /
+trial_route_group8): the writing-out (enumerate_ms, vectorised numpy), its three stages, and enumerate + call under one clock
+(call_ms).  search_moves' tables must equal, bitwise, score_host fed with that route's predictions.  Per row the median over
+`rounds` rounds; speedup_over_trial_route = the route's call_ms / search_moves' call_ms.
 Needs a GPU."""
 import argparse
 import copy
@@ -351,6 +363,118 @@ def trials_rows(a, emit, designs, ids, pmodel, cnn, dev):
              beats_64_sequential_trials=bool(med['call_ms'] < 64 * seq_med))
 
 
+def search_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--search: one Predictor.search_moves call over a window per pin group of design 0 next to trial_moves on the same
+    candidates written out by the host, in the same run."""
+    from mmft import search as SE
+    from mmft import trial as TR
+    m, d, radius = designs[0].map_size, designs[0], a.radius
+    # required times at the median prediction: about half of the endpoints violate (the batch copies them when it is built)
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N = int(d.N)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    on = np.flatnonzero(count > 0)
+    rng = np.random.default_rng(7)
+    single = rng.choice(on, a.groups, replace=on.size < a.groups).astype(np.int64)
+    eights = np.concatenate([rng.choice(on, 8, replace=False) for _ in range(a.groups // 8)]).astype(np.int64)
+    sets = {'single': (single, None, 1), 'group8': (eights, np.arange(0, eights.shape[0] + 1, 8, dtype=np.int64), 8)}
+    dx, dy = SE.offsets(radius)
+    W = dx.shape[0]
+    px, py = np.asarray(d.pin_x), np.asarray(d.pin_y)
+    emit(row='search_shapes', designs=a.designs, map=m, rows=int(p.T), rows_design0=int(p.slack.rows_of(0).numel()), radius=radius, offsets=W,
+         pins_on_a_row_design0=int(on.size), rows_per_such_pin_mean=float(count[on].mean()))
+
+    def written_out(pins, size):
+        """The window of every group as explicit trial_moves candidates, candidate g * W + w (groups of one size: vectorised)."""
+        every = np.broadcast_to(pins.reshape(-1, 1, size), (pins.shape[0] // size, W, size))
+        x, y = SE.moved_coords(px[every], dx[None, :, None]), SE.moved_coords(py[every], dy[None, :, None])
+        return every.reshape(-1).astype(np.int64), x.reshape(-1), y.reshape(-1), np.arange(0, every.size + 1, size, dtype=np.int64)
+
+    def staged(mod, prepare):
+        """One call of mmft.search or mmft.trial in its three stages, as trials_rows times them."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call = prepare()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        mod.launch(p, call)
+        e1.record()
+        e1.synchronize()
+        t2 = time.perf_counter()
+        res = mod.fetch(call)
+        t3 = time.perf_counter()
+        return res, dict(host_ms=1e3 * (t1 - t0), launches_ms=e0.elapsed_time(e1), copy_back_ms=1e3 * (t3 - t2))
+
+    def search_once(pins, gptr, size):
+        t0 = time.perf_counter()
+        plan = p.search_plan(0, pins, gptr)
+        torch.cuda.synchronize()
+        plan_ms = 1e3 * (time.perf_counter() - t0)
+        res, parts = staged(SE, lambda: SE.prepare(p, plan, radius, a.scale_log2, a.max_rows))
+        t0 = time.perf_counter()
+        p.search_moves(plan, radius, a.scale_log2, a.max_rows)
+        return res, plan, dict(plan_ms=plan_ms, **parts, call_ms=1e3 * (time.perf_counter() - t0))
+
+    def route_once(pins, gptr, size):
+        t0 = time.perf_counter()
+        args = written_out(pins, size)
+        enumerate_ms = 1e3 * (time.perf_counter() - t0)
+        res, parts = staged(TR, lambda: TR.prepare(p, 0, *args))
+        t0 = time.perf_counter()
+        p.trial_moves(0, *written_out(pins, size))
+        return res, dict(enumerate_ms=enumerate_ms, **parts, call_ms=1e3 * (time.perf_counter() - t0))
+
+    # the two routes give the same tables, bitwise
+    pred, required = base.cpu().numpy().reshape(-1), p.required.cpu().numpy()
+    for nm, args in sets.items():
+        res, plan, _ = search_once(*args)
+        tm, _ = route_once(*args)
+        G, R = plan.G, plan.R
+        assert np.array_equal(tm['pair_ptr'], np.concatenate([[0], np.cumsum(np.repeat(np.diff(plan.grow_ptr), W))]))
+        trial = np.zeros((W, R), dtype=np.float32)
+        for g in range(G):                                              # candidate g * W + w: the group's entries under offset w
+            e0, e1 = int(plan.grow_ptr[g]), int(plan.grow_ptr[g + 1])
+            k0 = int(tm['pair_ptr'][g * W])
+            trial[:, e0:e1] = tm['pred'][k0:k0 + W * (e1 - e0)].reshape(W, e1 - e0)
+        want = SE.score_host(pred, required, plan.grow_ptr, plan.grow_row, trial, radius, a.scale_log2)
+        bits = lambda v: np.ascontiguousarray(v).view(np.uint8)
+        same = all(np.array_equal(bits(res[k]), bits(want[k])) for k in SE.TABLES + ('best_w', 'best_dq'))
+        same &= res['base'] == SE.base_host(pred, required, p.slack.rows_of(0).cpu().numpy(), a.scale_log2)
+        cw = SE.centre(radius)
+        emit(row=f'search_outputs_{nm}', groups=G, entries=R, candidates=G * W, equals_trial_moves_route_bitwise=bool(same),
+             groups_with_a_move_that_helps=int((res['best_w'] != cw).sum()), candidates_that_change_violations=int(np.count_nonzero(res['dviol'])),
+             ineligible_candidates=int(np.count_nonzero(res['new_nan'])), best_gain_max=float(res['best_gain'].max()),
+             base_tns=-res['base']['nsum'] * 2.0 ** -a.scale_log2, base_violations=res['base']['violations'])
+        assert same
+    assert torch.equal(p.predict()[0], base)
+    found, routed = {nm: [] for nm in sets}, {nm: [] for nm in sets}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, args in sets.items():
+            found[nm].append(search_once(*args)[2])
+            routed[nm].append(route_once(*args)[1])
+    for nm, (pins, gptr, size) in sets.items():
+        plan = p.search_plan(0, pins, gptr)
+        K = plan.G * W
+        med = {k: statistics.median(r[k] for r in found[nm]) for k in found[nm][0]}
+        old = {k: statistics.median(r[k] for r in routed[nm]) for k in routed[nm][0]}
+        emit(row=f'search_{nm}', groups=plan.G, pins=int(pins.shape[0]), entries=plan.R, candidates=K, chunks=-(-W // SE.check_call(plan.R, radius, a.scale_log2, a.max_rows)[1]),
+             rounds=a.rounds, **{k + '_median': v for k, v in med.items()}, call_ms_min=min(r['call_ms'] for r in found[nm]),
+             call_ms_max=max(r['call_ms'] for r in found[nm]), us_per_candidate=1e3 * med['call_ms'] / K)
+        emit(row=f'trial_route_{nm}', candidates=K, moves=K * size, pairs=plan.R * W, rounds=a.rounds, **{k + '_median': v for k, v in old.items()},
+             call_ms_min=min(r['call_ms'] for r in routed[nm]), call_ms_max=max(r['call_ms'] for r in routed[nm]),
+             us_per_candidate=1e3 * old['call_ms'] / K, speedup_over_trial_route=old['call_ms'] / med['call_ms'],
+             search_is_faster=bool(med['call_ms'] < old['call_ms']))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -364,6 +488,10 @@ def main():
     ap.add_argument('--scale-log2', type=int, default=20)
     ap.add_argument('--trials', action='store_true')
     ap.add_argument('--candidates', type=int, default=4096, help='--trials: single-pin candidates (and an eighth as many of 8 pins)')
+    ap.add_argument('--search', action='store_true')
+    ap.add_argument('--groups', type=int, default=4096, help='--search: single-pin groups (and an eighth as many of 8 pins)')
+    ap.add_argument('--radius', type=int, default=2, help='--search: the window holds (2 radius + 1)^2 offsets')
+    ap.add_argument('--max-rows', type=int, default=65536, help='--search: head input rows per chunk of offsets')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -393,6 +521,10 @@ def main():
     if a.trials:
         with lib.math_mode('bf16'), torch.no_grad():
             trials_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.search:
+        with lib.math_mode('bf16'), torch.no_grad():
+            search_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
