@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import gradsink, lib, ops, search, trial
+from . import commit, gradsink, lib, ops, search, trial
 from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
 from .placement import batch_tables, placed_fc
@@ -209,6 +209,9 @@ class Predictor(ResidentDesigns):
                           regression head.  search_plan(i, pins, group_ptr) / search_moves(plan, radius) enumerate a window
                           of rigid displacements per pin group on the device instead and return every candidate's score and the
                           best offset per group (mmft.search, include/mmft_search.h); they need nothing more at construction.
+                          commit_moves(plan) runs that search, selects on the device a set of groups whose best moves cannot
+                          see each other and moves their pins in place; refine_moves(plan) repeats it with a predict() in
+                          between (mmft.commit, include/mmft_commit.h).
                           Left at False, nothing about the object, its launches or its results changes
 
     Construction touches no module mode and no requires_grad; predict() leaves every module in the mode it found."""
@@ -374,6 +377,32 @@ class Predictor(ResidentDesigns):
         with the fused regression head, for a radius outside [1, 8], a scale_log2 outside [0, 30], max_rows < 1, R * W >= 2^31
         and a plan of another Predictor."""
         return search.search_moves(self, plan, radius, scale_log2, max_rows)
+
+    def commit_moves(self, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+        """search_moves, then the commit of a conflict-free set of its best moves, on the device (mmft.commit,
+        include/mmft_commit.h).  A group is a CANDIDATE iff its best offset is not the centre and improves the design's sum
+        by at least max(1, ceil(min_gain * 2^scale_log2)) quanta; two groups CONFLICT iff they share a row of the plan.  The
+        selected set is the one a loop over the candidates in the order of (best_dq, g) gives that takes a group iff none of
+        its rows belongs to a group already taken.  Its groups share no row and - the plan is checked once - no pin, so each
+        row changes exactly as under its own group's move alone: the next predict() has the negative-slack sum
+        predicted_nsum, to the quantum.
+
+        Returns everything search_moves returns, and selected (bool [G]), n_selected, n_candidates, rounds (of the selection
+        kernel), sum_dq (int, the sum of the selected groups' best_dq), gain (float64, -sum_dq * 2^-scale_log2) and
+        predicted_nsum = base['nsum'] + sum_dq; one device -> host copy.
+
+        apply=True: the selected groups' pins are moved in place by their best offsets (addresses stay: a replayed graph
+        sees them), and the trial state is stale as after update(): trial_moves / search_moves / commit_moves refuse until a
+        predict() has run.  apply=False: nothing another call reads is written.  Eager: refused under an outer stream
+        capture.  Refusals: those of search_moves; ValueError for a plan in which two groups hold one pin, and for a
+        min_gain that is negative, not finite or too large for 62 bits of quanta."""
+        return commit.commit_moves(self, plan, radius, scale_log2, max_rows, min_gain, apply)
+
+    def refine_moves(self, plan, radius=1, passes=4, **kw):
+        """commit_moves(plan, radius, **kw), then predict(), repeated until a pass selects nothing or `passes` have run: the
+        list of the passes' results.  Each pass's predicted_nsum is the next pass's base['nsum'], and the sums never
+        increase.  Needs a predict() before the call, like every trial call, and leaves one behind."""
+        return commit.refine_moves(self, plan, radius, passes, **kw)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

@@ -62,21 +62,21 @@ def check_groups(n_nodes, pins, group_ptr=None):
     return TR.check_pin_sets(n_nodes, pins, group_ptr, who='search_plan', ptr_name='group_ptr', unit='group', item='pins')
 
 
-def check_call(R, radius=1, scale_log2=20, max_rows=65536):
+def check_call(R, radius=1, scale_log2=20, max_rows=65536, who='search_moves'):
     """(W, Wc) of a search_moves call over a plan of R entries - the offsets of the window and of one chunk - or ValueError: a
-    radius outside [1, 8], a scale_log2 outside [0, 30], max_rows < 1, R * W >= 2^31."""
+    radius outside [1, 8], a scale_log2 outside [0, 30], max_rows < 1, R * W >= 2^31.  `who`: the caller the messages name."""
     for name, v in (('radius', radius), ('scale_log2', scale_log2), ('max_rows', max_rows)):
         if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-            raise ValueError(f'search_moves: {name} must be an integer, got {v!r}')
+            raise ValueError(f'{who}: {name} must be an integer, got {v!r}')
     if not 1 <= radius <= MAX_RADIUS:
-        raise ValueError(f'search_moves: radius must lie in [1, {MAX_RADIUS}], got {radius}')
+        raise ValueError(f'{who}: radius must lie in [1, {MAX_RADIUS}], got {radius}')
     if not 0 <= scale_log2 <= 30:
-        raise ValueError(f'search_moves: scale_log2 must lie in [0, 30], got {scale_log2}')
+        raise ValueError(f'{who}: scale_log2 must lie in [0, 30], got {scale_log2}')
     if max_rows < 1:
-        raise ValueError(f'search_moves: max_rows must be at least 1, got {max_rows}')
+        raise ValueError(f'{who}: max_rows must be at least 1, got {max_rows}')
     W = (2 * int(radius) + 1) ** 2
     if int(R) * W >= 2 ** 31:
-        raise ValueError(f'search_moves: {R} entries times {W} offsets do not stay below 2^31')
+        raise ValueError(f'{who}: {R} entries times {W} offsets do not stay below 2^31')
     return W, min(W, max(1, int(max_rows) // max(int(R), 1)))
 
 
@@ -93,8 +93,9 @@ class SearchPlan:
     """What search_plan returns: design i's groups as host tables and, in ONE int32 buffer on the device, grow_ptr, grow_row,
     grow_grp, mv_ptr, mv_node.  Valid for the life of its Predictor: the incidence is static, and pin moves do not change it."""
 
-    def __init__(self, owner, i, tables, device):
-        self.owner, self.i = owner, int(i)
+    def __init__(self, owner, i, tables, device, node_off=0):
+        self.owner, self.i, self.node_off = owner, int(i), int(node_off)
+        self.pins_distinct = None                            # commit.check_plan's verdict, made once: None, True or its message
         self.grow_ptr, self.grow_row, self.grow_grp, self.mv_ptr, self.mv_node = tables
         self.G, self.R, self.M = self.mv_ptr.shape[0] - 1, self.grow_row.shape[0], self.mv_node.shape[0]
         sizes = [a.shape[0] for a in tables]
@@ -116,7 +117,7 @@ def search_plan(p, i, pins, group_ptr=None):
     pins, group_ptr = check_groups(int(placed.node_off[i + 1]) - off, pins, group_ptr)
     if group_ptr.shape[0] < 2:
         raise ValueError('search_plan: no group')
-    return SearchPlan(p, i, plan_tables(st.rows_of_pin, off, pins, group_ptr), p.device)
+    return SearchPlan(p, i, plan_tables(st.rows_of_pin, off, pins, group_ptr), p.device, node_off=off)
 
 
 # ------------------------------------------------------------------------------------------------ the scores on the host
@@ -198,20 +199,21 @@ def base_host(pred_base, required, design_rows, scale_log2=20):
 
 
 # ------------------------------------------------------------------------------------------------ the Predictor's side
-def prepare(p, plan, radius=1, scale_log2=20, max_rows=65536):
+def prepare(p, plan, radius=1, scale_log2=20, max_rows=65536, who='search_moves', extra=0):
     """Stage 1, host: state and mode refusals, validation, the call's output buffer.  No host table is built and nothing is
-    uploaded: the plan holds the tables.  Returns the call `launch` takes."""
-    TR.check_state(p, 'search_moves', 'the chunks of the window are launched from the host per call')
+    uploaded: the plan holds the tables.  Returns the call `launch` takes.  `who`: the caller the messages name; `extra`:
+    int64 words behind the tables in the same buffer, for a caller that returns more in the same copy (mmft.commit)."""
+    TR.check_state(p, who, 'the chunks of the window are launched from the host per call')
     if not isinstance(plan, SearchPlan):
-        raise TypeError(f'search_moves: plan must come from search_plan(), got {type(plan).__name__}')
+        raise TypeError(f'{who}: plan must come from search_plan(), got {type(plan).__name__}')
     if plan.owner is not p:
-        raise ValueError('search_moves: the plan belongs to another Predictor')
-    W, Wc = check_call(plan.R, radius, scale_log2, max_rows)
+        raise ValueError(f'{who}: the plan belongs to another Predictor')
+    W, Wc = check_call(plan.R, radius, scale_log2, max_rows, who)
     G = plan.G
     # ONE buffer for everything that goes back: int64 [dq G W | best_dq G | base 3], then int32 [5 tables G W | best_w G]
     n64, n32 = G * W + G + 3, 5 * G * W + G
-    raw = torch.empty(n64 + (n32 + 1) // 2, dtype=torch.int64, device=p.device)
-    return dict(plan=plan, radius=int(radius), scale_log2=int(scale_log2), W=W, Wc=Wc, raw=raw, n64=n64)
+    raw = torch.empty(n64 + (n32 + 1) // 2 + int(extra), dtype=torch.int64, device=p.device)
+    return dict(plan=plan, radius=int(radius), scale_log2=int(scale_log2), W=W, Wc=Wc, raw=raw, n64=n64, tail=n64 + (n32 + 1) // 2)
 
 
 def _views(raw, G, W, n64):
@@ -254,10 +256,11 @@ def launch(p, call):
 
 
 def fetch(call):
-    """Stage 3: ONE device -> host copy, decoded.  The result of search_moves."""
+    """Stage 3: ONE device -> host copy (kept as call['host']), decoded.  The result of search_moves."""
     plan, W, radius = call['plan'], call['W'], call['radius']
     G = plan.G
-    v = _views(call['raw'].cpu().numpy(), G, W, call['n64'])
+    host = call['host'] = call['raw'].cpu().numpy()
+    v = _views(host, G, W, call['n64'])
     res = {k: v[k].reshape(G, W).copy() for k in TABLES}
     dx, dy = offsets(radius)
     best_w, best_dq = v['best_w'].copy(), v['best_dq'].copy()

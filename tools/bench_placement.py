@@ -5,6 +5,7 @@
     python tools/bench_placement.py --criticality  (what Predictor(criticality=...) adds to a replayed predict(), see below)
     python tools/bench_placement.py --trials       (one trial_moves call over many candidates, see below)
     python tools/bench_placement.py --search       (one search_moves call over a window per pin group, see below)
+    python tools/bench_placement.py --commit       (one commit_moves call next to the host's route to the same pins, see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -52,6 +53,18 @@ alternating inside the same rounds, Predictor.trial_moves on the SAME candidates
 trial_route_group8): the writing-out (enumerate_ms, vectorised numpy), its three stages, and enumerate + call under one clock
 (call_ms).  search_moves' tables must equal, bitwise, score_host fed with that route's predictions.  Per row the median over
 `rounds` rounds; speedup_over_trial_route = the route's call_ms / search_moves' call_ms.
+
+--commit [--groups 4096] [--radius 2] [--min-gain 0], on the same designs (nothing of the above is run): ONE
+Predictor.commit_moves call over 4096 single-pin groups of design 0 at radius 2 (commit_single) and over 512 groups of 8 pins
+(commit_group8; distinct pins throughout), required times at the median prediction: host milliseconds of the refusals and
+the buffer (host_ms), device milliseconds of the search's launches, of the select kernel and of the apply kernel, each
+between events of its own (search_launches_ms, select_launch_ms, apply_launch_ms), the copy back and decoding (copy_back_ms),
+the whole call under one host clock (call_ms), and the rounds the select kernel ran.  Next to each, alternating inside the
+same rounds, the host's route to the same pins (host_route_single / host_route_group8): search_moves, commit.select_host on its
+tables, commit.apply_host on the design's pins, update(0, pin_x=, pin_y=), each under the host clock and all under one
+(call_ms).  The two routes must leave the same pins and return the same selection, and the predict() that follows must have
+exactly the predicted sum.  Between calls the pins go home and a predict() runs, outside every clock.  Per row the median
+over `rounds` rounds; speedup_over_host_route = the route's call_ms / commit_moves' call_ms.
 Needs a GPU."""
 import argparse
 import copy
@@ -475,6 +488,122 @@ def search_rows(a, emit, designs, ids, pmodel, cnn, dev):
              search_is_faster=bool(med['call_ms'] < old['call_ms']))
 
 
+def commit_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--commit: one Predictor.commit_moves call over the pin groups of design 0 next to the host's route to the same pins
+    (search_moves, select_host, apply_host, update), in the same run."""
+    from mmft import commit as CM
+    from mmft import search as SE
+    m, d, radius = designs[0].map_size, designs[0], a.radius
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N, T = int(d.N), int(p.T)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    on = np.random.default_rng(7).permutation(np.flatnonzero(count > 0)).astype(np.int64)
+    n8 = min(a.groups // 8, on.size // 8)
+    sets = {'single': (on[:a.groups], None), 'group8': (on[:8 * n8], np.arange(0, 8 * n8 + 1, 8, dtype=np.int64))}
+    home_x, home_y = np.asarray(d.pin_x).copy(), np.asarray(d.pin_y).copy()
+    rows0 = p.slack.rows_of(0).cpu().numpy()
+    required = p.required.cpu().numpy()
+    min_q = CM.min_quanta(a.min_gain, a.scale_log2)
+    emit(row='commit_shapes', designs=a.designs, map=m, rows=T, rows_design0=int(rows0.shape[0]), radius=radius,
+         offsets=(2 * radius + 1) ** 2, pins_on_a_row_design0=int(on.size), min_quanta=min_q)
+
+    def go_home():
+        p.update(0, pin_x=home_x, pin_y=home_y)
+        p.predict()
+        torch.cuda.synchronize()
+
+    def pins_now():
+        return p._placed.loc_x[:N].cpu().numpy(), p._placed.loc_y[:N].cpu().numpy()
+
+    def commit_once(plan):
+        """commit_moves in its three stages with the launches of its three parts between events of their own, then the pins
+        home, then the whole call under one host clock."""
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call = CM.prepare(p, plan, radius, a.scale_log2, a.max_rows, a.min_gain, True)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        marks = {}
+
+        def between_events(name, fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            marks[name] = (e0, e1)
+        CM.launch(p, call, timed=between_events)
+        torch.cuda.synchronize()
+        t2 = time.perf_counter()
+        res = CM.fetch(call)
+        t3 = time.perf_counter()
+        parts = dict(host_ms=1e3 * (t1 - t0), search_launches_ms=marks['search'][0].elapsed_time(marks['search'][1]),
+                     select_launch_ms=marks['select'][0].elapsed_time(marks['select'][1]),
+                     apply_launch_ms=marks['apply'][0].elapsed_time(marks['apply'][1]), copy_back_ms=1e3 * (t3 - t2))
+        go_home()
+        t0 = time.perf_counter()
+        res = p.commit_moves(plan, radius, a.scale_log2, a.max_rows, a.min_gain)
+        torch.cuda.synchronize()
+        return res, dict(**parts, call_ms=1e3 * (time.perf_counter() - t0), select_rounds=res['rounds'])
+
+    def route_once(plan):
+        t0 = time.perf_counter()
+        res = p.search_moves(plan, radius, a.scale_log2, a.max_rows)
+        t1 = time.perf_counter()
+        sel, figures = CM.select_host(res['best_w'], res['best_dq'], radius, plan.grow_ptr, plan.grow_row, T, min_q)
+        t2 = time.perf_counter()
+        nx, ny = CM.apply_host(home_x, home_y, sel, res['best_w'], radius, plan.mv_ptr, plan.mv_node)
+        t3 = time.perf_counter()
+        p.update(0, pin_x=nx, pin_y=ny)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        return (res, sel, figures), dict(search_moves_ms=1e3 * (t1 - t0), select_host_ms=1e3 * (t2 - t1), apply_host_ms=1e3 * (t3 - t2),
+                                         update_ms=1e3 * (t4 - t3), call_ms=1e3 * (t4 - t0))
+
+    plans = {nm: p.search_plan(0, pins, gptr) for nm, (pins, gptr) in sets.items()}
+    # the two routes leave the same pins, and the predict() that follows has exactly the predicted sum
+    for nm, plan in plans.items():
+        go_home()
+        (found, sel, figures), _ = route_once(plan)
+        routed = pins_now()
+        go_home()
+        res, _ = commit_once(plan)
+        mine = pins_now()
+        same = np.array_equal(res['selected'], sel != 0) and (res['n_selected'], res['sum_dq'], res['n_candidates']) == figures
+        same &= np.array_equal(mine[0], routed[0]) and np.array_equal(mine[1], routed[1])
+        same &= all(np.array_equal(np.ascontiguousarray(res[k]).view(np.uint8), np.ascontiguousarray(found[k]).view(np.uint8))
+                    for k in SE.TABLES + ('best_w', 'best_dq'))
+        after = SE.base_host(p.predict()[0].cpu().numpy().reshape(-1), required, rows0, a.scale_log2)
+        emit(row=f'commit_outputs_{nm}', groups=plan.G, entries=plan.R, candidates=res['n_candidates'], selected=res['n_selected'],
+             select_rounds=res['rounds'], gain=res['gain'], base_tns=-res['base']['nsum'] * 2.0 ** -a.scale_log2,
+             predicted_tns=-res['predicted_nsum'] * 2.0 ** -a.scale_log2, equals_host_route=bool(same),
+             predict_has_the_predicted_sum=bool(after['nsum'] == res['predicted_nsum']))
+        assert same and after['nsum'] == res['predicted_nsum']
+    done, routed = {nm: [] for nm in sets}, {nm: [] for nm in sets}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, plan in plans.items():
+            go_home()
+            done[nm].append(commit_once(plan)[1])
+            go_home()
+            routed[nm].append(route_once(plan)[1])
+    go_home()
+    assert torch.equal(p.predict()[0], base)
+    for nm, plan in plans.items():
+        med = {k: statistics.median(r[k] for r in done[nm]) for k in done[nm][0]}
+        old = {k: statistics.median(r[k] for r in routed[nm]) for k in routed[nm][0]}
+        emit(row=f'commit_{nm}', groups=plan.G, pins=plan.M, entries=plan.R, rounds=a.rounds, **{k + '_median': v for k, v in med.items()},
+             call_ms_min=min(r['call_ms'] for r in done[nm]), call_ms_max=max(r['call_ms'] for r in done[nm]))
+        emit(row=f'host_route_{nm}', rounds=a.rounds, **{k + '_median': v for k, v in old.items()},
+             call_ms_min=min(r['call_ms'] for r in routed[nm]), call_ms_max=max(r['call_ms'] for r in routed[nm]),
+             speedup_over_host_route=old['call_ms'] / med['call_ms'], commit_is_faster=bool(med['call_ms'] < old['call_ms']))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -492,6 +621,8 @@ def main():
     ap.add_argument('--groups', type=int, default=4096, help='--search: single-pin groups (and an eighth as many of 8 pins)')
     ap.add_argument('--radius', type=int, default=2, help='--search: the window holds (2 radius + 1)^2 offsets')
     ap.add_argument('--max-rows', type=int, default=65536, help='--search: head input rows per chunk of offsets')
+    ap.add_argument('--commit', action='store_true')
+    ap.add_argument('--min-gain', type=float, default=0.0, help='--commit: the smallest TNS gain that makes a group a candidate')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -525,6 +656,10 @@ def main():
     if a.search:
         with lib.math_mode('bf16'), torch.no_grad():
             search_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.commit:
+        with lib.math_mode('bf16'), torch.no_grad():
+            commit_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
