@@ -319,7 +319,7 @@ using namespace mmft;
 
 extern "C" {
 
-int mmft_version(void) { return 213; }      // 202: include/mmft_report.h (mmft_timing_report); 203: include/mmft_place.h (mmft_placed_fc_fwd); 204: include/mmft_incr.h; 205: include/mmft_crit.h (mmft_criticality); 206: include/mmft_head.h (mmft_head_mlp_fwd / _bwd); 207: include/mmft_crit_sums.h (mmft_criticality_sums); 208: include/mmft_sens.h (mmft_mlp2_feat_dx_bf16); 209: include/mmft_sens_image.h (mmft_u16_frozen_bwd, mmft_u16_conv3x3_dgrad_image); 210: include/mmft_sens_pins.h (mmft_pin_move_rows, mmft_pin_move_sum); 211: include/mmft_trial.h (mmft_trial_rows, mmft_trial_reduce); 212: include/mmft_search.h (mmft_search_rows, mmft_search_score, mmft_search_best); 213: include/mmft_commit.h (mmft_commit_select, mmft_commit_apply)
+int mmft_version(void) { return 214; }      // 202: include/mmft_report.h (mmft_timing_report); 203: include/mmft_place.h (mmft_placed_fc_fwd); 204: include/mmft_incr.h; 205: include/mmft_crit.h (mmft_criticality); 206: include/mmft_head.h (mmft_head_mlp_fwd / _bwd); 207: include/mmft_crit_sums.h (mmft_criticality_sums); 208: include/mmft_sens.h (mmft_mlp2_feat_dx_bf16); 209: include/mmft_sens_image.h (mmft_u16_frozen_bwd, mmft_u16_conv3x3_dgrad_image); 210: include/mmft_sens_pins.h (mmft_pin_move_rows, mmft_pin_move_sum); 211: include/mmft_trial.h (mmft_trial_rows, mmft_trial_reduce); 212: include/mmft_search.h (mmft_search_rows, mmft_search_score, mmft_search_best); 213: include/mmft_commit.h (mmft_commit_select, mmft_commit_apply)
 
 int mmft_set_math_mode(int mode) {
   MMFT_REQUIRE(mode == MMFT_MATH_F32 || mode == MMFT_MATH_BF16, "set_math_mode: unknown mode %d", mode);

@@ -14,6 +14,10 @@ its pins in place; the next predict() is the truth of the prediction it returns.
                                       and apply on the same stream, everything in ONE buffer and one copy back
     commit_moves / refine_moves       what the Predictor's methods of those names delegate to
 
+patch=True (mmft.refine, include/mmft_refine.h) puts three launches between select and apply that write the selected entries'
+rows into the kept head state, so that the next search needs no predict(); refine_moves(resident=True) enqueues all its
+passes that way and copies their results back once.
+
 The entry points are bound by `abi`, an accessor of this module: the table of mmft.lib's accessors is pinned by its own ledger
 and is not touched here.
 """
@@ -23,6 +27,7 @@ import numpy as np
 import torch
 
 from . import lib
+from . import refine as RF
 from . import search as SE
 
 abi = lib.Header('mmft_commit.h')        # a conflict-free set of best moves: its selection, the write of its pins
@@ -113,13 +118,20 @@ def min_quanta(min_gain, scale_log2=20):
 
 
 # ------------------------------------------------------------------------------------------------ the Predictor's side
-def prepare(p, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+def prepare(p, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True, patch=False):
     """Stage 1, host: search.prepare's refusals under this caller's name, check_plan, min_quanta; the search's buffer with
-    room behind its tables for stats [4] int64 and sel [G] int32.  Returns the call `launch` takes."""
+    room behind its tables for stats [4] int64 and sel [G] int32 - and, patch=True, the two counts of mmft_refine_patch behind
+    those.  Returns the call `launch` takes."""
+    if patch and not apply:
+        raise ValueError('commit_moves: patch=True writes the rows of the moved pins into the kept state; it needs apply=True')
     G = getattr(plan, 'G', 0)
-    call = SE.prepare(p, plan, radius, scale_log2, max_rows, who='commit_moves', extra=4 + (G + 1) // 2)
+    call = SE.prepare(p, plan, radius, scale_log2, max_rows, who='commit_moves', extra=4 + (G + 1) // 2 + (2 if patch else 0))
     check_plan(plan)
-    call['min_q'], call['apply'] = min_quanta(min_gain, scale_log2), bool(apply)
+    call['min_q'], call['apply'], call['patch'] = min_quanta(min_gain, scale_log2), bool(apply), bool(patch)
+    if patch:
+        if not p._trial.kept['pred'].is_contiguous():
+            raise ValueError('commit_moves: patch=True writes the kept predictions in place; they are not contiguous')
+        call['scratch'] = RF.scratch(p, plan)
     owner = getattr(plan, 'commit_owner', None)              # scratch over the rows, kept with the plan
     T = p._trial.kept['pred'].numel()
     if owner is None or owner.numel() * 8 < owner_bytes(T):
@@ -133,10 +145,18 @@ def _tail(raw, tail, G):
     return raw[tail:tail + 4], raw[tail + 4:].view(torch.int32 if torch.is_tensor(raw) else np.int32)[:G]
 
 
+def _patch_stats(raw, tail, G):
+    """The counts [2] int64 of mmft_refine_patch behind sel, in the buffer of a patch=True call."""
+    at = tail + 4 + (G + 1) // 2
+    return raw[at:at + 2]
+
+
 def launch(p, call, timed=None):
     """Stage 2, device, on the current stream: search.launch, then mmft_commit_select on its best_w / best_dq and - apply=True -
-    mmft_commit_apply on the resident pins, after which the trial state is stale as after update().  Returns the call.
-    `timed`: a callable that is handed each of the three parts as a function (tools/bench_placement.py times them apart)."""
+    mmft_commit_apply on the resident pins, after which the trial state is stale as after update().  patch=True: refine.launch
+    (rows, head, patch) between the two - the rows kernel reads the pins before apply moves them - and the trial state
+    stays fresh.  Returns the call.  `timed`: a callable that is handed each part as a function (tools/bench_placement.py
+    times them apart)."""
     run = timed if timed is not None else (lambda name, fn: fn())
     run('search', lambda: SE.launch(p, call))
     plan, placed = call['plan'], p._placed
@@ -147,8 +167,10 @@ def launch(p, call, timed=None):
     T = p._trial.kept['pred'].numel()
     run('select', lambda: abi('mmft_commit_select', v['best_w'], v['best_dq'], G, call['radius'], d_gptr, d_grow if plan.R else None, plan.R,
                               T, call['min_q'], sel, stats, call['owner'], *lib.stream_args(sel)))
+    if call['patch']:
+        RF.launch(p, call, sel, v['best_w'], _patch_stats(call['raw'], call['tail'], G), run)
     if call['apply']:
-        p._trial.stale = True                                # until the next predict(), exactly as update() leaves it
+        p._trial.stale = not call['patch']                   # unpatched: until the next predict(), exactly as update() leaves it
         run('apply', lambda: abi('mmft_commit_apply', placed.loc_x, placed.loc_y, placed.loc_x.numel(), sel, v['best_w'], call['radius'],
                                  d_mptr, d_node if plan.M else None, G, plan.M, *lib.stream_args(sel)))
     return call
@@ -161,20 +183,44 @@ def fetch(call):
     sum_dq = int(stats[1])
     res.update(selected=sel != 0, n_selected=int(stats[0]), n_candidates=int(stats[2]), rounds=int(stats[3]), sum_dq=sum_dq,
                gain=float(-sum_dq) * 2.0 ** -call['scale_log2'], predicted_nsum=res['base']['nsum'] + sum_dq)
+    if call['patch']:
+        res['n_patched'] = int(_patch_stats(call['host'], call['tail'], call['plan'].G)[0])
     return res
 
 
-def commit_moves(p, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+def commit_moves(p, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True, patch=False):
     """Predictor.commit_moves: see there."""
-    return fetch(launch(p, prepare(p, plan, radius, scale_log2, max_rows, min_gain, apply)))
+    return fetch(launch(p, prepare(p, plan, radius, scale_log2, max_rows, min_gain, apply, patch)))
 
 
-def refine_moves(p, plan, radius=1, passes=4, **kw):
+def _refine_resident(p, plan, radius, passes, **kw):
+    """refine_moves(resident=True): host validation once, `passes` patched commits enqueued back to back - each with a result
+    buffer of its own, a row of ONE tensor -, one copy back, the list cut after the first pass that selected nothing, and
+    the predict() the call leaves behind."""
+    first = prepare(p, plan, radius, patch=True, **kw)
+    raws = torch.empty((passes, first.pop('raw').numel()), dtype=torch.int64, device=p.device)       # (its own buffer: only its size)
+    calls = [launch(p, dict(first, raw=raws[k])) for k in range(passes)]
+    host = raws.cpu()                                        # the one synchronisation
+    out = []
+    for k, call in enumerate(calls):
+        call['raw'] = host[k]                                # (search.fetch's copy is none: the row is on the host already)
+        out.append(fetch(call))
+        if out[-1]['n_selected'] == 0:                       # the later passes found the same state and did the same: nothing
+            break
+    p.predict()
+    return out
+
+
+def refine_moves(p, plan, radius=1, passes=4, resident=False, **kw):
     """Predictor.refine_moves: see there."""
     if isinstance(passes, bool) or not isinstance(passes, (int, np.integer)) or passes < 1:
         raise ValueError(f'refine_moves: passes must be an integer of at least 1, got {passes!r}')
     if not kw.get('apply', True):
         raise ValueError('refine_moves: every pass applies its moves (apply=False is commit_moves\' alone)')
+    if resident:
+        if 'patch' in kw:
+            raise ValueError('refine_moves: resident=True patches every pass; patch= is not its caller\'s to set')
+        return _refine_resident(p, plan, radius, int(passes), **kw)
     out = []
     for _ in range(int(passes)):
         out.append(commit_moves(p, plan, radius, **kw))

@@ -378,7 +378,7 @@ class Predictor(ResidentDesigns):
         and a plan of another Predictor."""
         return search.search_moves(self, plan, radius, scale_log2, max_rows)
 
-    def commit_moves(self, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+    def commit_moves(self, plan, radius=1, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True, patch=False):
         """search_moves, then the commit of a conflict-free set of its best moves, on the device (mmft.commit,
         include/mmft_commit.h).  A group is a CANDIDATE iff its best offset is not the centre and improves the design's sum
         by at least max(1, ceil(min_gain * 2^scale_log2)) quanta; two groups CONFLICT iff they share a row of the plan.  The
@@ -395,14 +395,28 @@ class Predictor(ResidentDesigns):
         sees them), and the trial state is stale as after update(): trial_moves / search_moves / commit_moves refuse until a
         predict() has run.  apply=False: nothing another call reads is written.  Eager: refused under an outer stream
         capture.  Refusals: those of search_moves; ValueError for a plan in which two groups hold one pin, and for a
-        min_gain that is negative, not finite or too large for 62 bits of quanta."""
-        return commit.commit_moves(self, plan, radius, scale_log2, max_rows, min_gain, apply)
+        min_gain that is negative, not finite or too large for 62 bits of quanta.
 
-    def refine_moves(self, plan, radius=1, passes=4, **kw):
+        patch=True (needs apply=True, else ValueError; mmft.refine, include/mmft_refine.h): before the pins move, the rows of
+        the selected groups' entries are recomputed at their best offsets and written into the kept head state - the h_cnn
+        columns of the head's input and the predictions -, which then holds, bit for bit, what a predict() on the moved
+        pins would write.  The trial state stays fresh: trial_moves, search_moves and commit_moves may follow at once.  The
+        result gains n_patched, the entries written, in the same copy.  The kept predictions ARE the static buffer a replayed
+        predict() returned: a tensor the caller still holds from the last predict() changes in place.  report() and
+        criticality() keep describing the last predict()."""
+        return commit.commit_moves(self, plan, radius, scale_log2, max_rows, min_gain, apply, patch)
+
+    def refine_moves(self, plan, radius=1, passes=4, resident=False, **kw):
         """commit_moves(plan, radius, **kw), then predict(), repeated until a pass selects nothing or `passes` have run: the
         list of the passes' results.  Each pass's predicted_nsum is the next pass's base['nsum'], and the sums never
-        increase.  Needs a predict() before the call, like every trial call, and leaves one behind."""
-        return commit.refine_moves(self, plan, radius, passes, **kw)
+        increase.  Needs a predict() before the call, like every trial call, and leaves one behind.
+
+        resident=True: the same list without a predict() or a host decision between the passes.  Everything is validated
+        once, then all `passes` commits are enqueued back to back with patch=True, each into a result buffer of its own; one
+        copy brings them back, and the list is cut after the first pass that selected nothing (the later ones found the same
+        state and did nothing).  One predict() follows, after which the static output, report() and criticality() are
+        current again."""
+        return commit.refine_moves(self, plan, radius, passes, resident, **kw)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

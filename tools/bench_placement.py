@@ -6,6 +6,7 @@
     python tools/bench_placement.py --trials       (one trial_moves call over many candidates, see below)
     python tools/bench_placement.py --search       (one search_moves call over a window per pin group, see below)
     python tools/bench_placement.py --commit       (one commit_moves call next to the host's route to the same pins, see below)
+    python tools/bench_placement.py --refine       (refine_moves: the host loop next to resident=True, see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -65,6 +66,15 @@ tables, commit.apply_host on the design's pins, update(0, pin_x=, pin_y=), each 
 (call_ms).  The two routes must leave the same pins and return the same selection, and the predict() that follows must have
 exactly the predicted sum.  Between calls the pins go home and a predict() runs, outside every clock.  Per row the median
 over `rounds` rounds; speedup_over_host_route = the route's call_ms / commit_moves' call_ms.
+
+--refine [--groups 4096] [--radius 2] [--passes 4] [--min-gain 0], on the same designs and groups as --commit (nothing of the
+above is run): ONE Predictor.refine_moves call from the pins at home, whole under one host clock (call_ms), with resident=True
+(refine_resident_single / refine_resident_group8: `passes` patched commits enqueued back to back, one copy back, one
+predict()) and as the host loop (refine_host_loop_*: per pass a commit_moves and a replayed predict(); it stops after the
+first pass that selects nothing), alternating inside the same rounds.  per_pass_ms = call_ms / the passes the route ran;
+per_pass_ratio_host_over_resident is the ratio of the two.  Next to them one patched commit from the pins at home with its
+launches between events of their own (first_pass_*: the search, select, the rows kernel, the head, the patch, apply).  The
+two routes must return the same passes and leave the same pins and the same predictions.  Per row the median over `rounds`.
 Needs a GPU."""
 import argparse
 import copy
@@ -604,6 +614,102 @@ def commit_rows(a, emit, designs, ids, pmodel, cnn, dev):
              speedup_over_host_route=old['call_ms'] / med['call_ms'], commit_is_faster=bool(med['call_ms'] < old['call_ms']))
 
 
+def refine_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--refine: Predictor.refine_moves over the pin groups of design 0, the host loop (commit_moves + a replayed predict() per
+    pass) next to resident=True (patched commits enqueued back to back, one copy back, one predict()), in the same run."""
+    from mmft import commit as CM
+    m, d, radius, passes = designs[0].map_size, designs[0], a.radius, a.passes
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N, T = int(d.N), int(p.T)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    on = np.random.default_rng(7).permutation(np.flatnonzero(count > 0)).astype(np.int64)
+    n8 = min(a.groups // 8, on.size // 8)
+    sets = {'single': (on[:a.groups], None), 'group8': (on[:8 * n8], np.arange(0, 8 * n8 + 1, 8, dtype=np.int64))}
+    home_x, home_y = np.asarray(d.pin_x).copy(), np.asarray(d.pin_y).copy()
+    kw = dict(scale_log2=a.scale_log2, max_rows=a.max_rows, min_gain=a.min_gain)
+    emit(row='refine_shapes', designs=a.designs, map=m, rows=T, radius=radius, offsets=(2 * radius + 1) ** 2, passes=passes,
+         pins_on_a_row_design0=int(on.size))
+
+    def go_home():
+        p.update(0, pin_x=home_x, pin_y=home_y)
+        p.predict()
+        torch.cuda.synchronize()
+
+    def state_now():
+        return p._placed.loc_x[:N].cpu().numpy(), p._placed.loc_y[:N].cpu().numpy(), p.predict()[0].clone()
+
+    def refine_once(plan, resident):
+        """(the passes' results, figures): the whole refine_moves call under one host clock, from the pins at home."""
+        go_home()
+        t0 = time.perf_counter()
+        out = p.refine_moves(plan, radius, passes, resident=resident, **kw)
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0)
+        ran = passes if resident else len(out)                          # the resident route enqueues every pass
+        return out, dict(call_ms=ms, passes_run=ran, passes_with_moves=sum(r['n_selected'] > 0 for r in out), per_pass_ms=ms / ran)
+
+    def patched_commit_parts(plan):
+        """One patched commit from the pins at home, its launches between events of their own."""
+        go_home()
+        call = CM.prepare(p, plan, radius, a.scale_log2, a.max_rows, a.min_gain, True, True)
+        marks = {}
+
+        def between_events(name, fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            marks[name] = (e0, e1)
+        CM.launch(p, call, timed=between_events)
+        torch.cuda.synchronize()
+        res = CM.fetch(call)
+        names = dict(search='search_launches_ms', select='select_launch_ms', rows='rows_launch_ms', head='head_launch_ms',
+                     patch='patch_launch_ms', apply='apply_launch_ms')
+        return dict({names[k]: e0.elapsed_time(e1) for k, (e0, e1) in marks.items()}, n_patched=res['n_patched'])
+
+    plans = {nm: p.search_plan(0, pins, gptr) for nm, (pins, gptr) in sets.items()}
+    # the two routes return the same passes and leave the same pins and the same predictions
+    for nm, plan in plans.items():
+        want, _ = refine_once(plan, False)
+        routed = state_now()
+        got, _ = refine_once(plan, True)
+        mine = state_now()
+        same = len(got) == len(want) and all(np.array_equal(g['selected'], w['selected']) and g['base'] == w['base'] and
+                                             (g['sum_dq'], g['predicted_nsum']) == (w['sum_dq'], w['predicted_nsum']) and
+                                             np.array_equal(g['dq'], w['dq']) for g, w in zip(got, want))
+        same &= np.array_equal(mine[0], routed[0]) and np.array_equal(mine[1], routed[1]) and torch.equal(mine[2], routed[2])
+        emit(row=f'refine_outputs_{nm}', groups=plan.G, entries=plan.R, passes_returned=len(got), selected=[r['n_selected'] for r in got],
+             patched=[r['n_patched'] for r in got], base_tns=-got[0]['base']['nsum'] * 2.0 ** -a.scale_log2,
+             final_tns=-got[-1]['predicted_nsum'] * 2.0 ** -a.scale_log2, equals_host_loop=bool(same))
+        assert same
+    done = {(nm, res): [] for nm in sets for res in (True, False)}
+    parts = {nm: [] for nm in sets}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, plan in plans.items():
+            for res in (True, False):
+                done[nm, res].append(refine_once(plan, res)[1])
+            parts[nm].append(patched_commit_parts(plan))
+    go_home()
+    assert torch.equal(p.predict()[0], base)
+    for nm, plan in plans.items():
+        med = {res: {k: statistics.median(r[k] for r in done[nm, res]) for k in done[nm, res][0]} for res in (True, False)}
+        one = {k: statistics.median(r[k] for r in parts[nm]) for k in parts[nm][0]}
+        emit(row=f'refine_resident_{nm}', groups=plan.G, pins=plan.M, entries=plan.R, rounds=a.rounds, passes=passes,
+             **{k + '_median': v for k, v in med[True].items()}, call_ms_min=min(r['call_ms'] for r in done[nm, True]),
+             call_ms_max=max(r['call_ms'] for r in done[nm, True]), **{'first_pass_' + k + '_median': v for k, v in one.items()})
+        emit(row=f'refine_host_loop_{nm}', rounds=a.rounds, passes=passes, **{k + '_median': v for k, v in med[False].items()},
+             call_ms_min=min(r['call_ms'] for r in done[nm, False]), call_ms_max=max(r['call_ms'] for r in done[nm, False]),
+             per_pass_ratio_host_over_resident=med[False]['per_pass_ms'] / med[True]['per_pass_ms'],
+             resident_is_faster=bool(med[True]['per_pass_ms'] < med[False]['per_pass_ms']))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -623,6 +729,8 @@ def main():
     ap.add_argument('--max-rows', type=int, default=65536, help='--search: head input rows per chunk of offsets')
     ap.add_argument('--commit', action='store_true')
     ap.add_argument('--min-gain', type=float, default=0.0, help='--commit: the smallest TNS gain that makes a group a candidate')
+    ap.add_argument('--refine', action='store_true')
+    ap.add_argument('--passes', type=int, default=4, help='--refine: the passes of one refine_moves call')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -660,6 +768,10 @@ def main():
     if a.commit:
         with lib.math_mode('bf16'), torch.no_grad():
             commit_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.refine:
+        with lib.math_mode('bf16'), torch.no_grad():
+            refine_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
