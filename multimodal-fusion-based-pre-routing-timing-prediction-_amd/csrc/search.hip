@@ -4,20 +4,17 @@
 // and the offset - a 64-bit sum saturated to int32 -, staged in LDS where trial_rows_kernel stages a candidate's, and the row
 // is written by trial_row_write (trial_row.h), the function that kernel calls: the same bits, and the tables are never written.
 // search_score_kernel: one wave per (group, offset) walks the group's entries and reduces the change of the quanta, of the
-// violations, the new NaN rows, the capped rows and the worst (slack, row) key in integers.
+// violations, the new NaN rows, the capped rows and the worst (slack, row) key in integers (search_score.h, shared with swap.hip).
 // search_best_kernel: one wave per group takes the smallest (dq, |dx| + |dy|, w) key among the eligible offsets.
-// search_base_kernel: the design's own sum of quanta, violations and NaN rows, by integer atomics.
+// search_base_kernel: the design's own sum of quanta, violations and NaN rows, by integer atomics (search_score.h).
 #include "common.h"
-#include "slack_key.h"
-#include "slack_quanta.h"
+#include "search_score.h"
 #include "trial_row.h"
 #include "../../include/mmft_search.h"
 
 namespace mmft {
 
 constexpr int SEARCH_MAX_RADIUS = 8;
-typedef unsigned long long search_u64;
-constexpr search_u64 SEARCH_KEY_NONE = ~0ull;   // no valid key has all-ones slack bits (that pattern is a NaN)
 
 __host__ __device__ inline int search_side(int radius) { return 2 * radius + 1; }
 
@@ -70,45 +67,10 @@ __global__ void __launch_bounds__(256) search_score_kernel(const float* __restri
   const int g = (int)(item / Wc), wc = (int)(item - (long long)g * Wc);
   const int e0 = grow_ptr[g], e1 = grow_ptr[g + 1];
   const float* trial = pred_trial + (long long)wc * R;
-  long long sum = 0;
-  int viol = 0, nans = 0, caps = 0;
-  search_u64 best = SEARCH_KEY_NONE;
-  for (int e = e0 + lane; e < e1; e += 64) {
-    const int r = grow_row[e];
-    if ((unsigned)r >= (unsigned)T) continue;
-    const float req = required[r];
-    const float sb = slack_of(req, pred_base[r]), st = slack_of(req, trial[e]);
-    bool cb = false, ct = false;
-    const long long qb = sb < 0.f ? (long long)crit_quanta(sb, scale_log2, cb) : 0ll;
-    const long long qt = st < 0.f ? (long long)crit_quanta(st, scale_log2, ct) : 0ll;
-    sum += qt - qb;
-    viol += (st < 0.f ? 1 : 0) - (sb < 0.f ? 1 : 0);
-    caps += (cb || ct) ? 1 : 0;
-    if (st != st) {
-      nans += (sb == sb) ? 1 : 0;
-    } else {
-      const search_u64 key = ((search_u64)ordered_bits(st) << 32) | (unsigned)r;
-      best = key < best ? key : best;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o, 64);
-    viol += __shfl_xor(viol, o, 64);
-    nans += __shfl_xor(nans, o, 64);
-    caps += __shfl_xor(caps, o, 64);
-    const search_u64 other = __shfl_xor(best, o, 64);
-    best = other < best ? other : best;
-  }
-  if (lane == 0) {
-    const long long at = (long long)g * W + w0 + wc;
-    dq[at] = sum;
-    dviol[at] = viol;
-    new_nan[at] = nans;
-    capped[at] = caps;
-    worst[at] = best == SEARCH_KEY_NONE ? __uint_as_float(0x7fc00000u) : ordered_float((unsigned)(best >> 32));
-    worst_row[at] = best == SEARCH_KEY_NONE ? -1 : (int)(unsigned)(best & 0xffffffffull);
-  }
+  SearchAcc acc;
+  for (int e = e0 + lane; e < e1; e += 64) search_acc_entry(acc, grow_row[e], T, required, pred_base, trial + e, scale_log2);
+  search_acc_wave(acc);
+  if (lane == 0) search_acc_store(acc, (long long)g * W + w0 + wc, dq, dviol, new_nan, capped, worst, worst_row);
 }
 
 __global__ void __launch_bounds__(256) search_best_kernel(const long long* __restrict__ dq, const int* __restrict__ new_nan, int G,
@@ -145,31 +107,7 @@ __global__ void __launch_bounds__(256) search_best_kernel(const long long* __res
 __global__ void __launch_bounds__(256) search_base_kernel(const float* __restrict__ pred_base, const float* __restrict__ required,
                                                           const int* __restrict__ design_rows, int n, int T, int scale_log2,
                                                           search_u64* __restrict__ base) {
-  search_u64 sum = 0ull;
-  int viol = 0, nans = 0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const int r = design_rows[i];
-    float s = __uint_as_float(0x7fc00000u);
-    if ((unsigned)r < (unsigned)T) s = slack_of(required[r], pred_base[r]);
-    if (s != s) {
-      ++nans;
-    } else if (s < 0.f) {
-      bool cap;
-      sum += crit_quanta(s, scale_log2, cap);
-      ++viol;
-    }
-  }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    sum += __shfl_xor(sum, o, 64);
-    viol += __shfl_xor(viol, o, 64);
-    nans += __shfl_xor(nans, o, 64);
-  }
-  if ((threadIdx.x & 63) == 0) {                        // integer adds: the order of the waves does not show
-    if (sum) atomicAdd(base, sum);
-    if (viol) atomicAdd(base + 1, (search_u64)viol);
-    if (nans) atomicAdd(base + 2, (search_u64)nans);
-  }
+  search_base_rows(pred_base, required, design_rows, n, T, scale_log2, base);
 }
 
 static bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }

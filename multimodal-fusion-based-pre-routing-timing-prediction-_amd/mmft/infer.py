@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import commit, gradsink, lib, ops, search, trial
+from . import commit, gradsink, lib, ops, search, swap, trial
 from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
 from .placement import batch_tables, placed_fc
@@ -417,6 +417,58 @@ class Predictor(ResidentDesigns):
         state and did nothing).  One predict() follows, after which the static output, report() and criticality() are
         current again."""
         return commit.refine_moves(self, plan, radius, passes, resident, **kw)
+
+    def swap_plan(self, plan, pair_a, pair_b):
+        """K swaps of the groups of `plan` (from search_plan) for swap_moves / commit_swaps (trials=True; mmft.swap,
+        include/mmft_swap.h).  pair_a, pair_b: int64 [K], K >= 1, group ids of the plan: pair k swaps the cells pair_a[k] and
+        pair_b[k].  The ANCHOR of a group is its first pin: under the swap the two anchors exchange positions and every pin
+        keeps its offset from its own anchor, the sums formed in 64 bits and saturated to int32; the anchors are read on the
+        device at call time, so the plan stays valid while the placement moves.  Host work and ONE upload, no launch: per
+        pair the ascending union of its two groups' rows (prow_ptr, prow_row, prow_pair) and the select table of
+        commit_swaps.  The same pair twice, or (a, b) beside (b, a), is allowed: they conflict.  Valid for the life of this
+        Predictor, and its alone.
+        RuntimeError without trials=True; TypeError for something that is no search plan; IndexError for a group id outside
+        the plan; ValueError for arrays that are not int64 [K], a pair of a group with itself, an empty group, groups of more
+        than 64 pins together, a plan of another Predictor, a plan in which two groups hold one pin, and more than 2^24 rows
+        and groups together."""
+        return swap.swap_plan(self, plan, pair_a, pair_b)
+
+    def swap_moves(self, splan, scale_log2=20, max_rows=65536):
+        """Every swap of `splan`, each taken ALONE, scored exactly from the last predict() (mmft.swap, include/mmft_swap.h).
+        The pairs are walked on the device in chunks cut at pair boundaries so that a chunk's entries stay within max_rows
+        (a single larger pair goes alone), which bounds the buffer of head input rows; the results do not depend on
+        max_rows.  No host table is built per call.
+
+        Returns host data (one device -> host copy), tables [K] with search_moves' definitions, a pair's entries in the
+        place of a group's: dq int64, dviol, new_nan, capped, worst, worst_row; eligible (bool: new_nan == 0); gain float64
+        = -dq * 2^-scale_log2; base: nsum, violations, n_nan of the design on the pins as they are; prow_ptr and rows from
+        the plan; and per group of the search plan best_pair [G] - the eligible pair that holds the group with the
+        smallest key (dq, k), -1 without one - and best_pair_dq [G], both decoded on the host from that same copy.
+
+        Writes nothing predict() returns and no pin.  Refusals as search_moves: RuntimeError without trials=True, under an
+        outer stream capture, before the first predict() and after an update() or a commit no predict() has followed;
+        ValueError outside bf16 math mode with the fused regression head, for a scale_log2 outside [0, 30], max_rows < 1 and a
+        plan of another Predictor; TypeError for something that is no swap plan."""
+        return swap.swap_moves(self, splan, scale_log2, max_rows)
+
+    def commit_swaps(self, splan, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+        """swap_moves, then the commit of a conflict-free set of swaps, on the device (mmft.swap; the selection is
+        mmft_commit_select of include/mmft_commit.h as it stands).  A pair is a CANDIDATE iff it is eligible and improves the
+        design's sum by at least max(1, ceil(min_gain * 2^scale_log2)) quanta, commit_moves' own threshold; two pairs
+        CONFLICT iff they share a row or a group - also a group that lies on no row.  The selected set is the one a loop over
+        the candidates in the order of (dq, k) gives that takes a pair iff it conflicts with none already taken.  Its swaps
+        cannot see each other: the next predict() has the negative-slack sum predicted_nsum, to the quantum.
+
+        Returns everything swap_moves returns - the per-pair gain under the name pair_gain -, and selected (bool [K]),
+        n_selected, n_candidates, rounds (of the selection kernel), sum_dq (int, the sum of the selected pairs' dq), gain
+        (float64, -sum_dq * 2^-scale_log2) and predicted_nsum = base['nsum'] + sum_dq; one device -> host copy.
+
+        apply=True: the pins of both groups of every selected pair are written in place at their swapped coordinates
+        (addresses stay: a replayed graph sees them), and the trial state is stale exactly as after commit_moves():
+        trial_moves / search_moves / swap_moves / commit_swaps refuse until a predict() has run.  apply=False: nothing
+        another call reads is written.  Eager: refused under an outer stream capture.  Refusals: those of swap_moves, and
+        ValueError for a min_gain that is negative, not finite or too large for 62 bits of quanta."""
+        return swap.commit_swaps(self, splan, scale_log2, max_rows, min_gain, apply)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

@@ -9,7 +9,7 @@ the best offset per group - without writing the placement, h or anything predict
     offsets / centre / moved_coords   the window: offset w -> (dx, dy), the zero move, the saturating add
     check_groups / check_call         host validation of search_plan's and search_moves' arguments
     plan_tables                       the tables of a plan from the incidence, through trial.expand_candidates
-    score_host                        mmft_search_score + mmft_search_best restated in numpy
+    tables_host / score_host          mmft_search_score, and with it mmft_search_best, restated in numpy
     prepare / launch / fetch          the three stages of a call (refusals and buffers, the launches, one copy back);
                                       search_moves runs them one after another, tools/bench_placement.py times them apart
 
@@ -145,15 +145,17 @@ def best_host(dq, new_nan, radius, scale_log2=20):
                 best_dq=best_dq, best_gain=(-best_dq).astype(np.float64) * 2.0 ** -int(scale_log2))
 
 
-def score_host(pred_base, required, grow_ptr, grow_row, pred_trial, radius, scale_log2=20):
-    """Every table of mmft_search_score and the best of mmft_search_best from host arrays, in numpy: pred_trial fp32 [W, R] - row
-    grow_row[e] under offset w -, the slack rule of mmft_report.h (reference_slack), THE QUANTUM (reference_quanta), the
-    smallest row on equal worst slack.  An entry whose row lies outside pred_base takes part in nothing."""
+def tables_host(pred_base, required, grow_ptr, grow_row, pred_trial, scale_log2=20):
+    """The six tables [G, W] of mmft_search_score from host arrays, in numpy: pred_trial fp32 [W, R] - row grow_row[e] under
+    candidate w of its group -, the slack rule of mmft_report.h (reference_slack), THE QUANTUM (reference_quanta), the smallest
+    row on equal worst slack.  An entry whose row lies outside pred_base takes part in nothing.  mmft.swap scores its pairs
+    with it too (W == 1, a pair's entries as a group's): the definitions are stated once."""
     pred_base, required = np.asarray(pred_base, dtype=np.float32), np.asarray(required, dtype=np.float32)
     grow_ptr, grow_row = np.asarray(grow_ptr, dtype=np.int64), np.asarray(grow_row, dtype=np.int64)
-    W = offsets(radius)[0].shape[0]
     G, R, T = grow_ptr.shape[0] - 1, grow_row.shape[0], pred_base.shape[0]
-    pred_trial = np.asarray(pred_trial, dtype=np.float32).reshape(W, R)
+    pred_trial = np.asarray(pred_trial, dtype=np.float32)
+    pred_trial = pred_trial if pred_trial.ndim == 2 else pred_trial.reshape(1, R)       # [R]: one candidate per group
+    W = pred_trial.shape[0]
     inside = (grow_row >= 0) & (grow_row < T)
     safe = np.where(inside, grow_row, 0)
     sb = reference_slack(pred_base[safe], required[safe])                   # [R]
@@ -181,6 +183,15 @@ def score_host(pred_base, required, grow_ptr, grow_row, pred_trial, radius, scal
             worst[g] = np.where(found, st[np.arange(W), at], np.float32(np.nan))
             worst_row[g] = np.where(found, grow_row[at], -1)
     out['worst'], out['worst_row'] = worst, worst_row
+    return out
+
+
+def score_host(pred_base, required, grow_ptr, grow_row, pred_trial, radius, scale_log2=20):
+    """Every table of mmft_search_score and the best of mmft_search_best from host arrays, in numpy: pred_trial fp32 [W, R] - row
+    grow_row[e] under offset w -, the slack rule of mmft_report.h (reference_slack), THE QUANTUM (reference_quanta), the
+    smallest row on equal worst slack.  An entry whose row lies outside pred_base takes part in nothing."""
+    W, R = offsets(radius)[0].shape[0], np.asarray(grow_row).shape[0]
+    out = tables_host(pred_base, required, grow_ptr, grow_row, np.asarray(pred_trial, dtype=np.float32).reshape(W, R), scale_log2)
     out.update(best_host(out['dq'], out['new_nan'], radius, scale_log2))
     return out
 

@@ -7,6 +7,7 @@
     python tools/bench_placement.py --search       (one search_moves call over a window per pin group, see below)
     python tools/bench_placement.py --commit       (one commit_moves call next to the host's route to the same pins, see below)
     python tools/bench_placement.py --refine       (refine_moves: the host loop next to resident=True, see below)
+    python tools/bench_placement.py --swaps        (one swap_moves / commit_swaps call over pairs of pin groups, see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -75,6 +76,17 @@ first pass that selects nothing), alternating inside the same rounds.  per_pass_
 per_pass_ratio_host_over_resident is the ratio of the two.  Next to them one patched commit from the pins at home with its
 launches between events of their own (first_pass_*: the search, select, the rows kernel, the head, the patch, apply).  The
 two routes must return the same passes and leave the same pins and the same predictions.  Per row the median over `rounds`.
+
+--swaps [--groups 4096] [--min-gain 0], on the same designs and groups as --commit (nothing of the above is run): every group
+paired with a seeded partner, so as many pairs as groups.  ONE Predictor.swap_moves call over the 4096 pairs of single pins
+(swap_moves_single) and over the 512 pairs of groups of 8 (swap_moves_group8) in its three stages (host_ms, launches_ms between
+events, copy_back_ms) and whole under one host clock (call_ms); next to each, alternating inside the same rounds,
+Predictor.trial_moves on the SAME swaps written out by the host with swap.swapped_coords (swap_trial_route_*: enumerate_ms,
+its three stages, enumerate + call under one clock).  Then ONE commit_swaps call (commit_swaps_*: call_ms, the select kernel's
+rounds) next to the host's route to the same pins (swap_host_route_*: swap_moves, swap.select_host, swap.apply_host,
+update(0, pin_x=, pin_y=)).  swap_moves' tables must equal, bitwise, score_host fed with the trial route's predictions; the
+two commits must leave the same pins and return the same selection, and the predict() that follows must have exactly the
+predicted sum.  Between commits the pins go home and a predict() runs, outside every clock.  Per row the median over `rounds`.
 Needs a GPU."""
 import argparse
 import copy
@@ -498,6 +510,155 @@ def search_rows(a, emit, designs, ids, pmodel, cnn, dev):
              search_is_faster=bool(med['call_ms'] < old['call_ms']))
 
 
+def swaps_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--swaps: one Predictor.swap_moves call over the pairs of design 0 next to trial_moves on the same swaps written out by
+    the host, and one commit_swaps call next to the host's route to the same pins (swap_moves, select_host, apply_host,
+    update), in the same run."""
+    from mmft import commit as CM
+    from mmft import search as SE
+    from mmft import swap as SW
+    from mmft import trial as TR
+    m, d = designs[0].map_size, designs[0]
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N, T = int(d.N), int(p.T)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    rng = np.random.default_rng(7)
+    on = rng.permutation(np.flatnonzero(count > 0)).astype(np.int64)
+    n1, n8 = min(a.groups, on.size), min(a.groups // 8, on.size // 8)
+    sets = {'single': (on[:n1], None), 'group8': (on[:8 * n8], np.arange(0, 8 * n8 + 1, 8, dtype=np.int64))}
+    home_x, home_y = np.asarray(d.pin_x).copy(), np.asarray(d.pin_y).copy()
+    rows0, required = p.slack.rows_of(0).cpu().numpy(), p.required.cpu().numpy()
+    pred = base.cpu().numpy().reshape(-1)
+    min_q = CM.min_quanta(a.min_gain, a.scale_log2)
+    emit(row='swap_shapes', designs=a.designs, map=m, rows=T, rows_design0=int(rows0.shape[0]), pins_on_a_row_design0=int(on.size), min_quanta=min_q)
+    plans, splans = {}, {}
+    for nm, (pins, gptr) in sets.items():                               # every group paired with a seeded partner
+        t0 = time.perf_counter()
+        plans[nm] = p.search_plan(0, pins, gptr)
+        G = plans[nm].G
+        pa = np.arange(G, dtype=np.int64)
+        pb = (pa + rng.integers(1, G, G)) % G
+        splans[nm] = p.swap_plan(plans[nm], pa, pb)
+        torch.cuda.synchronize()
+        emit(row=f'swap_plan_{nm}', groups=G, pairs=splans[nm].K, entries=splans[nm].RP, plans_ms=1e3 * (time.perf_counter() - t0))
+
+    def go_home():
+        p.update(0, pin_x=home_x, pin_y=home_y)
+        p.predict()
+        torch.cuda.synchronize()
+
+    def written_out(splan):
+        plan = splan.plan
+        c_ptr, c_node, c_x, c_y = SW.swapped_coords(home_x, home_y, plan.mv_ptr, plan.mv_node, splan.pair_a, splan.pair_b)
+        return c_node, c_x.astype(np.int64), c_y.astype(np.int64), c_ptr
+
+    def staged(mod, prepare):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        call = prepare()
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        mod.launch(p, call)
+        e1.record()
+        e1.synchronize()
+        t2 = time.perf_counter()
+        res = mod.fetch(call)
+        t3 = time.perf_counter()
+        return res, dict(host_ms=1e3 * (t1 - t0), launches_ms=e0.elapsed_time(e1), copy_back_ms=1e3 * (t3 - t2))
+
+    def swap_once(splan):
+        res, parts = staged(SW, lambda: SW.prepare(p, splan, a.scale_log2, a.max_rows))
+        t0 = time.perf_counter()
+        p.swap_moves(splan, a.scale_log2, a.max_rows)
+        return res, dict(**parts, call_ms=1e3 * (time.perf_counter() - t0))
+
+    def route_once(splan):
+        t0 = time.perf_counter()
+        args = written_out(splan)
+        enumerate_ms = 1e3 * (time.perf_counter() - t0)
+        res, parts = staged(TR, lambda: TR.prepare(p, 0, *args))
+        t0 = time.perf_counter()
+        p.trial_moves(0, *written_out(splan))
+        return res, dict(enumerate_ms=enumerate_ms, **parts, call_ms=1e3 * (time.perf_counter() - t0))
+
+    def commit_once(splan):
+        t0 = time.perf_counter()
+        res = p.commit_swaps(splan, a.scale_log2, a.max_rows, a.min_gain)
+        torch.cuda.synchronize()
+        return res, dict(call_ms=1e3 * (time.perf_counter() - t0), select_rounds=res['rounds'])
+
+    def host_commit_once(splan):
+        t0 = time.perf_counter()
+        res = p.swap_moves(splan, a.scale_log2, a.max_rows)
+        t1 = time.perf_counter()
+        pick = np.where(res['eligible'], 0, -1)
+        sel, figures = SW.select_host(pick, res['dq'], splan.sel_ptr, splan.sel_row, T, splan.G, min_q)
+        t2 = time.perf_counter()
+        nx, ny = SW.apply_host(home_x, home_y, sel, pick, splan.pair_a, splan.pair_b, splan.plan.mv_ptr, splan.plan.mv_node)
+        t3 = time.perf_counter()
+        p.update(0, pin_x=nx, pin_y=ny)
+        torch.cuda.synchronize()
+        t4 = time.perf_counter()
+        return (res, sel, figures), dict(swap_moves_ms=1e3 * (t1 - t0), select_host_ms=1e3 * (t2 - t1), apply_host_ms=1e3 * (t3 - t2),
+                                         update_ms=1e3 * (t4 - t3), call_ms=1e3 * (t4 - t0))
+
+    bits = lambda v: np.ascontiguousarray(v).view(np.uint8)
+    for nm, splan in splans.items():                                    # the routes agree, and the commit is the truth
+        res, _ = swap_once(splan)
+        tm, _ = route_once(splan)
+        assert np.array_equal(tm['pair_ptr'], splan.prow_ptr)
+        want = SW.score_host(pred, required, splan.prow_ptr, splan.prow_row, tm['pred'], a.scale_log2)
+        same = all(np.array_equal(bits(res[k]), bits(want[k])) for k in SW.TABLES + ('eligible',))
+        same &= res['base'] == SE.base_host(pred, required, rows0, a.scale_log2)
+        (found, sel, figures), _ = host_commit_once(splan)
+        routed = (p._placed.loc_x[:N].cpu().numpy(), p._placed.loc_y[:N].cpu().numpy())
+        go_home()
+        got, _ = commit_once(splan)
+        mine = (p._placed.loc_x[:N].cpu().numpy(), p._placed.loc_y[:N].cpu().numpy())
+        agree = np.array_equal(got['selected'], sel != 0) and (got['n_selected'], got['sum_dq'], got['n_candidates']) == figures
+        agree &= np.array_equal(mine[0], routed[0]) and np.array_equal(mine[1], routed[1])
+        after = SE.base_host(p.predict()[0].cpu().numpy().reshape(-1), required, rows0, a.scale_log2)
+        go_home()
+        emit(row=f'swap_outputs_{nm}', pairs=splan.K, entries=splan.RP, equals_trial_moves_route_bitwise=bool(same),
+             pairs_that_help=int((res['eligible'] & (res['dq'] < 0)).sum()), ineligible_pairs=int((~res['eligible']).sum()),
+             candidates=got['n_candidates'], selected=got['n_selected'], select_rounds=got['rounds'], gain=got['gain'],
+             base_tns=-got['base']['nsum'] * 2.0 ** -a.scale_log2, predicted_tns=-got['predicted_nsum'] * 2.0 ** -a.scale_log2,
+             commit_equals_host_route=bool(agree), predict_has_the_predicted_sum=bool(after['nsum'] == got['predicted_nsum']))
+        assert same and agree and after['nsum'] == got['predicted_nsum']
+    assert torch.equal(p.predict()[0], base)
+    rows = {nm: dict(swap=[], trial=[], commit=[], host=[]) for nm in splans}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, splan in splans.items():
+            rows[nm]['swap'].append(swap_once(splan)[1])
+            rows[nm]['trial'].append(route_once(splan)[1])
+            rows[nm]['commit'].append(commit_once(splan)[1])
+            go_home()
+            rows[nm]['host'].append(host_commit_once(splan)[1])
+            go_home()
+    for nm, splan in splans.items():
+        med = {w: {k: statistics.median(r[k] for r in rs) for k in rs[0]} for w, rs in rows[nm].items()}
+        span = lambda w: dict(call_ms_min=min(r['call_ms'] for r in rows[nm][w]), call_ms_max=max(r['call_ms'] for r in rows[nm][w]))
+        K = splan.K
+        emit(row=f'swap_moves_{nm}', pairs=K, pins=int(splan.plan.M), entries=splan.RP, chunks=len(SW.chunks(splan.prow_ptr, a.max_rows)), rounds=a.rounds,
+             **{k + '_median': v for k, v in med['swap'].items()}, **span('swap'), us_per_pair=1e3 * med['swap']['call_ms'] / K)
+        emit(row=f'swap_trial_route_{nm}', candidates=K, pairs=splan.RP, rounds=a.rounds, **{k + '_median': v for k, v in med['trial'].items()},
+             **span('trial'), us_per_pair=1e3 * med['trial']['call_ms'] / K, speedup_over_trial_route=med['trial']['call_ms'] / med['swap']['call_ms'],
+             swap_moves_is_faster=bool(med['swap']['call_ms'] < med['trial']['call_ms']))
+        emit(row=f'commit_swaps_{nm}', pairs=K, rounds=a.rounds, **{k + '_median': v for k, v in med['commit'].items()}, **span('commit'))
+        emit(row=f'swap_host_route_{nm}', pairs=K, rounds=a.rounds, **{k + '_median': v for k, v in med['host'].items()}, **span('host'),
+             speedup_over_host_route=med['host']['call_ms'] / med['commit']['call_ms'],
+             commit_is_faster=bool(med['commit']['call_ms'] < med['host']['call_ms']))
+
+
 def commit_rows(a, emit, designs, ids, pmodel, cnn, dev):
     """--commit: one Predictor.commit_moves call over the pin groups of design 0 next to the host's route to the same pins
     (search_moves, select_host, apply_host, update), in the same run."""
@@ -730,6 +891,7 @@ def main():
     ap.add_argument('--commit', action='store_true')
     ap.add_argument('--min-gain', type=float, default=0.0, help='--commit: the smallest TNS gain that makes a group a candidate')
     ap.add_argument('--refine', action='store_true')
+    ap.add_argument('--swaps', action='store_true')
     ap.add_argument('--passes', type=int, default=4, help='--refine: the passes of one refine_moves call')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
@@ -772,6 +934,10 @@ def main():
     if a.refine:
         with lib.math_mode('bf16'), torch.no_grad():
             refine_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.swaps:
+        with lib.math_mode('bf16'), torch.no_grad():
+            swaps_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
