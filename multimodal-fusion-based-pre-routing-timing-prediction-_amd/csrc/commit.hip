@@ -4,13 +4,14 @@
 // candidates under the key (best_dq, g), in rounds.  `sel` is the state on the way (0 dead or no candidate, 1 taken, 2 live);
 // the row-owner table lives in global memory and is touched only through relaxed agent-scope atomics (loads and stores that
 // go past L1), with every wave's memory operations drained before each barrier.
-// commit_apply_kernel: one wave per selected group moves its pins by the group's best offset, saturating.
+// commit_apply_kernel: one wave per selected group moves its pins by the group's best offset (THE WINDOW and THE MOVE RULE,
+// move_rule.h).
 #include "common.h"
+#include "move_rule.h"
 #include "../../include/mmft_commit.h"
 
 namespace mmft {
 
-constexpr int COMMIT_MAX_RADIUS = 8;
 constexpr int COMMIT_THREADS = 1024;
 constexpr long long COMMIT_NO_BID = 0x7fffffffffffffffll;
 constexpr int COMMIT_NO_GROUP = 0x7fffffff;
@@ -36,13 +37,11 @@ __device__ __forceinline__ void commit_barrier() {
   __syncthreads();
 }
 
-__device__ __forceinline__ int commit_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
 // f(r) for every row r in [0, T) among the entries of group g
 template <typename F>
 __device__ __forceinline__ void commit_rows_of(const int* __restrict__ grow_ptr, const int* __restrict__ grow_row, int g, int R, int T, F f) {
-  const int e1 = commit_clamp(grow_ptr[g + 1], R);
-  for (int e = commit_clamp(grow_ptr[g], R); e < e1; ++e) {
+  const int e1 = clamp_to(grow_ptr[g + 1], R);
+  for (int e = clamp_to(grow_ptr[g], R); e < e1; ++e) {
     const int r = grow_row[e];
     if ((unsigned)r < (unsigned)T) f(r);
   }
@@ -149,20 +148,18 @@ __global__ void __launch_bounds__(256) commit_apply_kernel(int* __restrict__ loc
   const int lane = threadIdx.x & 63;
   const long long g = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);          // the same for the lanes of a wave
   if (g >= G || sel[g] == 0) return;
-  const int side = 2 * radius + 1, w = best_w[g];
-  if (w < 0 || w >= side * side) return;
-  const long long dx = w / side - radius, dy = w % side - radius;
-  const int m1 = commit_clamp(mv_ptr[g + 1], M);
-  for (int m = commit_clamp(mv_ptr[g], M) + lane; m < m1; m += 64) {
+  const int w = best_w[g];
+  if (w < 0 || w >= window_cells(radius)) return;
+  int dx, dy;
+  window_offset(w, radius, dx, dy);
+  const int m1 = clamp_to(mv_ptr[g + 1], M);
+  for (int m = clamp_to(mv_ptr[g], M) + lane; m < m1; m += 64) {
     const int n = mv_node[m];
     if ((unsigned)n >= (unsigned)n_nodes) continue;
-    const long long x = (long long)loc_x[n] + dx, y = (long long)loc_y[n] + dy;
-    loc_x[n] = x > 2147483647ll ? 2147483647 : (x < -2147483648ll ? (int)-2147483648ll : (int)x);
-    loc_y[n] = y > 2147483647ll ? 2147483647 : (y < -2147483648ll ? (int)-2147483648ll : (int)y);
+    loc_x[n] = moved(loc_x[n], dx);
+    loc_y[n] = moved(loc_y[n], dy);
   }
 }
-
-static bool commit_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace mmft
 
@@ -174,23 +171,23 @@ int mmft_commit_select(const int* best_w, const long long* best_dq, int G, int r
                        int T, long long min_q, int* sel, long long* stats, void* owner, int device, void* stream) {
   MMFT_REQUIRE(G >= 1 && R >= 0 && T >= 1 && T <= (1 << 24), "commit_select: need G >= 1, R >= 0, 1 <= T <= 2^24 (got G %d, R %d, T %d)", G, R,
                T);
-  MMFT_REQUIRE(radius >= 1 && radius <= COMMIT_MAX_RADIUS, "commit_select: radius must lie in [1, %d] (got %d)", COMMIT_MAX_RADIUS, radius);
+  MMFT_REQUIRE(radius >= 1 && radius <= WINDOW_RADIUS_MAX, "commit_select: radius must lie in [1, %d] (got %d)", WINDOW_RADIUS_MAX, radius);
   MMFT_REQUIRE(min_q >= 1, "commit_select: min_q must be at least 1 (got %lld)", min_q);
   MMFT_REQUIRE(best_w && best_dq && grow_ptr && sel && stats && owner && (grow_row || R == 0), "commit_select: null pointer");
-  MMFT_REQUIRE(commit_aligned8(best_dq) && commit_aligned8(stats) && commit_aligned8(owner),
+  MMFT_REQUIRE(aligned8(best_dq) && aligned8(stats) && aligned8(owner),
                "commit_select: best_dq, stats and owner must be 8-byte aligned");
   DeviceGuard dg(device);
   long long* own_q = static_cast<long long*>(owner);
   int* own_g = reinterpret_cast<int*>(own_q + T);
   MMFT_LAUNCH("commit_select_kernel", 0.0, 0.0, commit_select_kernel, dim3(1), dim3(COMMIT_THREADS), (hipStream_t)stream, best_w, best_dq, G,
-              2 * radius * (radius + 1), grow_ptr, grow_row, R, T, min_q, sel, stats, own_q, own_g);
+              window_centre(radius), grow_ptr, grow_row, R, T, min_q, sel, stats, own_q, own_g);
   return check_launch("commit_select");
 }
 
 int mmft_commit_apply(int* loc_x, int* loc_y, int n_nodes, const int* sel, const int* best_w, int radius, const int* mv_ptr,
                       const int* mv_node, int G, int M, int device, void* stream) {
   MMFT_REQUIRE(n_nodes >= 1 && G >= 1 && M >= 0, "commit_apply: need n_nodes >= 1, G >= 1, M >= 0 (got %d, %d, %d)", n_nodes, G, M);
-  MMFT_REQUIRE(radius >= 1 && radius <= COMMIT_MAX_RADIUS, "commit_apply: radius must lie in [1, %d] (got %d)", COMMIT_MAX_RADIUS, radius);
+  MMFT_REQUIRE(radius >= 1 && radius <= WINDOW_RADIUS_MAX, "commit_apply: radius must lie in [1, %d] (got %d)", WINDOW_RADIUS_MAX, radius);
   MMFT_REQUIRE(loc_x && loc_y && sel && best_w && mv_ptr && (mv_node || M == 0), "commit_apply: null pointer");
   if (M == 0) return MMFT_OK;
   DeviceGuard dg(device);

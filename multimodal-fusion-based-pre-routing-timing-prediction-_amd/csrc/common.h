@@ -118,6 +118,10 @@ void prof_commit();
 inline int cdiv(long long a, long long b) { return (int)((a + b - 1) / b); }
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
+
+// v held to [0, hi]: an offset read from a caller's table before it indexes one
+__host__ __device__ inline int clamp_to(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 // grid for memory-bound elementwise work: cap at ~8 blocks/CU and grid-stride the rest
 inline int ew_grid(long long work_items, int block = 256) {

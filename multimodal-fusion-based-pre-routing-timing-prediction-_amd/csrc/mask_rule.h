@@ -1,8 +1,8 @@
 // THE MASK RULE of include/mmft_place.h as device code, stated once: the box of two pins (min / max per axis, lower corner
 // clamped to 0, upper to map - 1, empty boxes skipped) ORed into an LDS bitmap, cell (x, y) = bit x * map_y + y.
-// path_mask_kernel (prep.hip), placed_fc_fwd_kernel (place.hip), crit_scatter_kernel (crit.hip), trial_rows_kernel and
-// search_rows_kernel (trial.hip, search.hip: under overrides, through trial_row.h) build their bitmaps with it, pin_move.hip takes the axis arithmetic: the tests
-// compare these kernels bitwise, and the rule they share is here.
+// path_mask_kernel (prep.hip), placed_fc_fwd_kernel (place.hip), crit_scatter_kernel (crit.hip) and the four rows kernels
+// (trial.hip, search.hip, refine.hip, swap.hip: under overrides, through trial_row_write of trial_row.h) build their bitmaps
+// with it, pin_move.hip takes the axis arithmetic: the tests compare these kernels bitwise, and the rule they share is here.
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,8 +1,8 @@
 // The masked projection of ONE row from its mask's bitmap in LDS (include/mmft_place.h): the LDS layout, the numbering of the
-// runs and the accumulation through the block-prefix table.  placed_fc_fwd_kernel (place.hip) and trial_rows_kernel
-// (trial.hip) rasterise their bitmaps differently - the pins as they are, or with a candidate's overrides - and both call
-// place_project for everything after the raster: the tests hold the two kernels to the same bits, and the code that makes
-// those bits is here once.
+// runs and the accumulation through the block-prefix table.  placed_fc_fwd_kernel (place.hip) and trial_row_write
+// (trial_row.h, the body of the four rows kernels) rasterise their bitmaps differently - the pins as they are, or with a set of
+// overrides - and both call place_project for everything after the raster: the tests hold these kernels to the same bits, and
+// the code that makes those bits is here once.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stddef.h>

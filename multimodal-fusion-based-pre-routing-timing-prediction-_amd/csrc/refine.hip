@@ -1,9 +1,9 @@
 // Patch the kept head rows after a commit (include/mmft_refine.h).
 //
 // refine_rows_kernel: one workgroup per entry e.  A selected entry forms its group's overrides from the resident pins and the
-// offset best_w[g] - a 64-bit sum saturated to int32, as search_rows_kernel does -, stages them in LDS and writes the row by
-// trial_row_write (trial_row.h), the function search_rows_kernel and trial_rows_kernel call: the same bits.  Every other
-// entry copies its row of x.
+// offset best_w[g] by trial_stage_group (trial_row.h), the call search_rows_kernel makes, and writes the row by
+// trial_row_write, the function search_rows_kernel and trial_rows_kernel call: the same bits.  Every other entry copies its
+// row of x.
 // refine_patch_kernel: one wave per selected entry copies the h_cnn columns of its row of xt into x and its prediction into
 // pred, with plain vector stores: the selected groups share no row.
 #include "common.h"
@@ -11,15 +11,6 @@
 #include "../../include/mmft_refine.h"
 
 namespace mmft {
-
-constexpr int REFINE_MAX_RADIUS = 8;
-typedef unsigned long long refine_u64;
-
-// a resident coordinate moved by d cells: the sum in 64 bits, saturated to int32 (the rule of mmft_search.h)
-__device__ __forceinline__ int refine_moved(int c, int d) {
-  const long long v = (long long)c + d;
-  return v > 2147483647ll ? 2147483647 : (v < -2147483648ll ? (int)-2147483648ll : (int)v);
-}
 
 // the offset of entry e's group if the group is selected, else -1; the same for every thread that asks about one entry
 __device__ __forceinline__ int refine_offset(const int* __restrict__ sel, const int* __restrict__ best_w, int g, int G, int W) {
@@ -43,9 +34,8 @@ __global__ void __launch_bounds__(256) refine_rows_kernel(RefineRowsArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char refine_smem[];
   const int e = blockIdx.x, tid = threadIdx.x;
   const int t = a.grow_row[e], g = a.grow_grp[e];
-  const int side = 2 * a.radius + 1;
   const bool inside = (unsigned)t < (unsigned)a.T && (unsigned)g < (unsigned)a.G;
-  const int w = inside ? refine_offset(a.sel, a.best_w, g, a.G, side * side) : -1;
+  const int w = inside ? refine_offset(a.sel, a.best_w, g, a.G, window_cells(a.radius)) : -1;
   if (w < 0) {                                          // the same for every thread: the row as the resident batch has it
     float* dst = a.row.xt + (long long)e * a.row.ldxt;
     const float* src = a.row.x + (long long)(inside ? t : 0) * a.row.ldx;
@@ -59,16 +49,9 @@ __global__ void __launch_bounds__(256) refine_rows_kernel(RefineRowsArgs a) {
   const int P = a.row.map_x * a.row.map_y;
   const PlaceLds L = place_lds(refine_smem, P >> 6);
   const TrialMoves mv = trial_moves_lds(L, P);
-  const int dx = w / side - a.radius, dy = w % side - a.radius;
-  const int m0 = a.mv_ptr[g];
-  int n_mv = a.mv_ptr[g + 1] - m0;                      // the same for every thread
-  n_mv = n_mv < 0 ? 0 : (n_mv > TRIAL_MOVES ? TRIAL_MOVES : n_mv);
-  if (tid < n_mv) {
-    const int node = a.mv_node[m0 + tid];
-    mv.node[tid] = node;
-    mv.x[tid] = refine_moved(a.row.loc_x[node], dx);
-    mv.y[tid] = refine_moved(a.row.loc_y[node], dy);
-  }
+  int dx, dy;
+  window_offset(w, a.radius, dx, dy);
+  const int n_mv = trial_stage_group(a.row, mv, a.mv_ptr, a.mv_node, g, dx, dy, tid);
   trial_row_write(a.row, L, mv, n_mv, t, e, tid);
 }
 
@@ -77,7 +60,7 @@ __global__ void __launch_bounds__(256) refine_patch_kernel(float* __restrict__ x
                                                            const float* __restrict__ pred_t, const int* __restrict__ sel,
                                                            const int* __restrict__ best_w, int W, const int* __restrict__ grow_row,
                                                            const int* __restrict__ grow_grp, int R, int G, int cnn_col, int Dout,
-                                                           refine_u64* __restrict__ stats) {
+                                                           unsigned long long* __restrict__ stats) {
   __shared__ int s_count[8];                            // [0..4) patched per wave, [4..8) skipped per wave
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int quads = Dout >> 2;
@@ -103,11 +86,9 @@ __global__ void __launch_bounds__(256) refine_patch_kernel(float* __restrict__ x
   if (threadIdx.x < 2) {                                // integer adds: the order of the workgroups does not show
     const int* c = s_count + 4 * threadIdx.x;
     const int n = c[0] + c[1] + c[2] + c[3];
-    if (n) atomicAdd(stats + threadIdx.x, (refine_u64)n);
+    if (n) atomicAdd(stats + threadIdx.x, (unsigned long long)n);
   }
 }
-
-static bool refine_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace mmft
 
@@ -120,47 +101,31 @@ int mmft_refine_rows(const int* path_nodes, const int* path_lens, int maxlen, co
                      const int* mv_ptr, const int* mv_node, int G, const int* sel, const int* best_w, int radius, const float* GP,
                      const float* bias, const float* x, long long ldx, float* xt, long long ldxt, int width, int cnn_col, int Dout,
                      int S, int device, void* stream) {
-  MMFT_REQUIRE(S == 64, "refine_rows: the prefix block must be 64 cells (one bitmap word per block)");
-  MMFT_REQUIRE(mask_map_ok(map_x, map_y), "refine_rows: the map must hold a multiple of 64 cells, at most 65536");
-  MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && maxlen >= 1 && T >= 1 && T <= (1 << 24) && G >= 1 && R >= 0,
-               "refine_rows: bad sizes (Dout a multiple of 4 in [4, 1024], maxlen >= 1, 1 <= T <= 2^24, G >= 1, R >= 0)");
-  MMFT_REQUIRE(cnn_col >= 0 && cnn_col % 4 == 0 && ldx % 4 == 0 && ldxt % 4 == 0 && (long long)cnn_col + Dout <= width &&
-                   width <= ldx && width <= ldxt,
-               "refine_rows: bad columns (cnn_col, ldx, ldxt multiples of 4, 0 <= cnn_col, cnn_col + Dout <= width <= ldx, ldxt)");
-  MMFT_REQUIRE(radius >= 1 && radius <= REFINE_MAX_RADIUS, "refine_rows: radius must lie in [1, %d] (got %d)", REFINE_MAX_RADIUS, radius);
+  const TrialRowCall c = {"refine_rows", path_nodes, path_lens, maxlen, loc_x, loc_y, map_x, map_y, paths, f_off, GP, bias,
+                          x, ldx, xt, ldxt, width, cnn_col, Dout, S, device, stream};
+  int rc = trial_row_check(c, T >= 1 && T <= (1 << 24) && G >= 1 && R >= 0, "1 <= T <= 2^24, G >= 1, R >= 0");
+  if (rc) return rc;
+  MMFT_REQUIRE(radius >= 1 && radius <= WINDOW_RADIUS_MAX, "refine_rows: radius must lie in [1, %d] (got %d)", WINDOW_RADIUS_MAX, radius);
   if (R == 0) return MMFT_OK;
-  MMFT_REQUIRE(path_nodes && path_lens && loc_x && loc_y && paths && grow_row && grow_grp && mv_ptr && mv_node && sel && best_w && GP &&
-                   x && xt,
-               "refine_rows: null pointer");
-  MMFT_REQUIRE(aligned16(GP) && aligned16(x) && aligned16(xt) && (!bias || aligned16(bias)), "refine_rows: 16-byte alignment");
-  DeviceGuard dg(device);
-  const int P = map_x * map_y;
-  static DynLdsOnce once;
-  int arc = ensure_dyn_lds(once, (const void*)refine_rows_kernel, (int)trial_lds_bytes(MASK_MAX_CELLS), "refine_rows");
-  if (arc) return arc;
   RefineRowsArgs a;
-  TrialRowArgs& r = a.row;
-  r.path_nodes = path_nodes; r.path_lens = path_lens; r.loc_x = loc_x; r.loc_y = loc_y; r.paths = paths; r.foff = f_off;
-  r.GP = GP; r.bias = bias; r.x = x; r.xt = xt; r.ldx = ldx; r.ldxt = ldxt;
-  r.maxlen = maxlen; r.map_x = map_x; r.map_y = map_y; r.width = width; r.cnn_col = cnn_col; r.Dout = Dout;
   a.grow_row = grow_row; a.grow_grp = grow_grp; a.mv_ptr = mv_ptr; a.mv_node = mv_node; a.sel = sel; a.best_w = best_w;
   a.G = G; a.T = T; a.radius = radius;
-  MMFT_LAUNCH_LDS("refine_rows_kernel", 0.0, 0.0, refine_rows_kernel, dim3((unsigned)R), dim3(256), trial_lds_bytes(P), (hipStream_t)stream, a);
-  return check_launch("refine_rows");
+  return trial_row_launch<RefineRowsArgs, refine_rows_kernel>(c, "refine_rows_kernel", a, (unsigned)R,
+                                                              grow_row && grow_grp && mv_ptr && mv_node && sel && best_w);
 }
 
 int mmft_refine_patch(float* x, long long ldx, float* pred, int T, const float* xt, long long ldxt, const float* pred_t, const int* sel,
                       const int* best_w, int radius, const int* grow_row, const int* grow_grp, int R, int G, int cnn_col, int Dout,
                       long long* stats, int device, void* stream) {
   MMFT_REQUIRE(T >= 1 && T <= (1 << 24) && G >= 1 && R >= 0, "refine_patch: need 1 <= T <= 2^24, G >= 1, R >= 0 (got T %d, G %d, R %d)", T, G, R);
-  MMFT_REQUIRE(radius >= 1 && radius <= REFINE_MAX_RADIUS, "refine_patch: radius must lie in [1, %d] (got %d)", REFINE_MAX_RADIUS, radius);
+  MMFT_REQUIRE(radius >= 1 && radius <= WINDOW_RADIUS_MAX, "refine_patch: radius must lie in [1, %d] (got %d)", WINDOW_RADIUS_MAX, radius);
   MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && cnn_col >= 0 && cnn_col % 4 == 0 && ldx % 4 == 0 && ldxt % 4 == 0 &&
                    (long long)cnn_col + Dout <= ldx && (long long)cnn_col + Dout <= ldxt,
                "refine_patch: bad columns (Dout a multiple of 4 in [4, 1024], cnn_col, ldx, ldxt multiples of 4, 0 <= cnn_col, "
                "cnn_col + Dout <= ldx, ldxt)");
   MMFT_REQUIRE(x && pred && sel && best_w && stats && ((grow_row && grow_grp && xt && pred_t) || R == 0), "refine_patch: null pointer");
   MMFT_REQUIRE(aligned16(x) && (!xt || aligned16(xt)), "refine_patch: x and xt must be 16-byte aligned");
-  MMFT_REQUIRE(refine_aligned8(stats), "refine_patch: stats must be 8-byte aligned");
+  MMFT_REQUIRE(aligned8(stats), "refine_patch: stats must be 8-byte aligned");
   DeviceGuard dg(device);
   hipStream_t st = (hipStream_t)stream;
   hipError_t err = hipMemsetAsync(stats, 0, 2 * sizeof(long long), st);
@@ -171,9 +136,8 @@ int mmft_refine_patch(float* x, long long ldx, float* pred, int T, const float* 
   if (R == 0) return MMFT_OK;
   int grid = cdiv(R, 4);
   grid = grid > 2048 ? 2048 : grid;
-  const int side = 2 * radius + 1;
   MMFT_LAUNCH("refine_patch_kernel", 0.0, 8.0 * (double)R * Dout, refine_patch_kernel, dim3(grid), dim3(256), st, x, ldx, pred, T, xt, ldxt,
-              pred_t, sel, best_w, side * side, grow_row, grow_grp, R, G, cnn_col, Dout, reinterpret_cast<refine_u64*>(stats));
+              pred_t, sel, best_w, window_cells(radius), grow_row, grow_grp, R, G, cnn_col, Dout, reinterpret_cast<unsigned long long*>(stats));
   return check_launch("refine_patch");
 }
 

@@ -18,4 +18,8 @@ __device__ __forceinline__ float ordered_float(unsigned o) {
   return __uint_as_float((o & 0x80000000u) ? (o & 0x7fffffffu) : ~o);
 }
 
+// a (slack, row) key: ordered_bits(slack) << 32 | row, so the smallest key is the worst slack at the lowest row
+typedef unsigned long long slack_u64;
+constexpr slack_u64 SLACK_KEY_NONE = ~0ull;   // no valid key has all-ones slack bits (that pattern is a NaN)
+
 }  // namespace mmft

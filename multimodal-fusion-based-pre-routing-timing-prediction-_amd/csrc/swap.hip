@@ -1,28 +1,18 @@
 // Exact search and commit of cell swaps (include/mmft_swap.h).
 //
 // swap_rows_kernel: one workgroup per entry.  The overrides of both groups of the entry's pair are formed from the resident
-// pins and the two anchors - a 64-bit difference and sum saturated to int32 once -, staged in LDS where search_rows_kernel
-// stages a group's, and the row is written by trial_row_write (trial_row.h), the function trial_rows_kernel and
-// search_rows_kernel call: the same bits, and the tables are never written.
+// pins and the difference of the two anchors - in 64 bits, saturated to int32 once, by THE MOVE RULE (move_rule.h) -, staged
+// in LDS where search_rows_kernel stages a group's, and the row is written by trial_row_write (trial_row.h), the function
+// trial_rows_kernel and search_rows_kernel call: the same bits, and the tables are never written.
 // swap_score_kernel: one wave per pair walks the pair's entries with the accumulation of search_score_kernel
-// (search_score.h) and writes the six figures and `pick`.
-// swap_base_kernel: the body of search_base_kernel (search_score.h).
-// swap_apply_kernel: one wave per selected pair writes both groups' pins at their swapped coordinates, saturating.
+// (search_score.h) and writes the six figures and `pick`.  The base figures are search.hip's (search_base_launch).
+// swap_apply_kernel: one wave per selected pair writes both groups' pins at their swapped coordinates, by the same rule.
 #include "common.h"
 #include "search_score.h"
 #include "trial_row.h"
 #include "../../include/mmft_swap.h"
 
 namespace mmft {
-
-// a resident coordinate moved by d, d a difference of two resident coordinates: the sum in 64 bits (|c + d| < 2^33),
-// saturated to int32
-__device__ __forceinline__ int swap_moved(int c, long long d) {
-  const long long v = (long long)c + d;
-  return v > 2147483647ll ? 2147483647 : (v < -2147483648ll ? (int)-2147483648ll : (int)v);
-}
-
-__device__ __forceinline__ int swap_clamp(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
 
 struct SwapRowsArgs {
   TrialRowArgs row;
@@ -57,14 +47,16 @@ __global__ void __launch_bounds__(256) swap_rows_kernel(SwapRowsArgs a) {
   n_a = n_a > TRIAL_MOVES ? TRIAL_MOVES : n_a;            // group a's pins first, then b's, TRIAL_MOVES in all
   n_b = n_b > TRIAL_MOVES - n_a ? TRIAL_MOVES - n_a : n_b;
   const int n_mv = n_a + n_b;
+  // both groups in one pass, not two calls of trial_stage_group: a thread's pin id is fetched while the anchors' dependent
+  // loads are under way; behind them (the two-call form) the launches of swap_moves measured 1 - 2 % longer
   if (tid < n_mv) {
     const int A = a.mv_node[m_a], B = a.mv_node[m_b];
     const long long dx = (long long)a.row.loc_x[B] - a.row.loc_x[A], dy = (long long)a.row.loc_y[B] - a.row.loc_y[A];
     const bool first = tid < n_a;
     const int node = first ? a.mv_node[m_a + tid] : a.mv_node[m_b + tid - n_a];
     mv.node[tid] = node;
-    mv.x[tid] = swap_moved(a.row.loc_x[node], first ? dx : -dx);
-    mv.y[tid] = swap_moved(a.row.loc_y[node], first ? dy : -dy);
+    mv.x[tid] = moved(a.row.loc_x[node], first ? dx : -dx);
+    mv.y[tid] = moved(a.row.loc_y[node], first ? dy : -dy);
   }
   trial_row_write(a.row, L, mv, n_mv, t, slot, tid);
 }
@@ -79,8 +71,8 @@ __global__ void __launch_bounds__(256) swap_score_kernel(const float* __restrict
   const long long item = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);      // the same for the lanes of a wave
   if (item >= (long long)k1 - k0) return;
   const int k = k0 + (int)item;
-  const int first = swap_clamp(prow_ptr[k0], RP);         // where the call's predictions start
-  const int e0 = swap_clamp(prow_ptr[k], RP), e1 = swap_clamp(prow_ptr[k + 1], RP);
+  const int first = clamp_to(prow_ptr[k0], RP);         // where the call's predictions start
+  const int e0 = clamp_to(prow_ptr[k], RP), e1 = clamp_to(prow_ptr[k + 1], RP);
   SearchAcc acc;
   for (int e = e0 + lane; e < e1; e += 64)
     if (e >= first) search_acc_entry(acc, prow_row[e], T, required, pred_base, pred_trial + (e - first), scale_log2);
@@ -89,12 +81,6 @@ __global__ void __launch_bounds__(256) swap_score_kernel(const float* __restrict
     search_acc_store(acc, k, dq, dviol, new_nan, capped, worst, worst_row);
     pick[k] = acc.nans == 0 ? 0 : -1;
   }
-}
-
-__global__ void __launch_bounds__(256) swap_base_kernel(const float* __restrict__ pred_base, const float* __restrict__ required,
-                                                        const int* __restrict__ design_rows, int n, int T, int scale_log2,
-                                                        search_u64* __restrict__ base) {
-  search_base_rows(pred_base, required, design_rows, n, T, scale_log2, base);
 }
 
 __global__ void __launch_bounds__(256) swap_apply_kernel(int* loc_x, int* loc_y, int n_nodes, const int* __restrict__ sel,
@@ -106,8 +92,8 @@ __global__ void __launch_bounds__(256) swap_apply_kernel(int* loc_x, int* loc_y,
   if (k >= K || sel[k] == 0 || pick[k] != 0) return;
   const int ga = pair_a[k], gb = pair_b[k];
   if ((unsigned)ga >= (unsigned)G || (unsigned)gb >= (unsigned)G || ga == gb) return;
-  const int a0 = swap_clamp(mv_ptr[ga], M), a1 = swap_clamp(mv_ptr[ga + 1], M);
-  const int b0 = swap_clamp(mv_ptr[gb], M), b1 = swap_clamp(mv_ptr[gb + 1], M);
+  const int a0 = clamp_to(mv_ptr[ga], M), a1 = clamp_to(mv_ptr[ga + 1], M);
+  const int b0 = clamp_to(mv_ptr[gb], M), b1 = clamp_to(mv_ptr[gb + 1], M);
   if (a1 <= a0 || b1 <= b0) return;
   const int A = mv_node[a0], B = mv_node[b0];
   if ((unsigned)A >= (unsigned)n_nodes || (unsigned)B >= (unsigned)n_nodes) return;
@@ -121,12 +107,10 @@ __global__ void __launch_bounds__(256) swap_apply_kernel(int* loc_x, int* loc_y,
     const bool first = m < n_a;
     const int n = first ? mv_node[a0 + m] : mv_node[b0 + m - n_a];
     if ((unsigned)n >= (unsigned)n_nodes) continue;
-    loc_x[n] = swap_moved(loc_x[n], first ? dx : -dx);
-    loc_y[n] = swap_moved(loc_y[n], first ? dy : -dy);
+    loc_x[n] = moved(loc_x[n], first ? dx : -dx);
+    loc_y[n] = moved(loc_y[n], first ? dy : -dy);
   }
 }
-
-static bool swap_aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
 
 }  // namespace mmft
 
@@ -139,34 +123,17 @@ int mmft_swap_rows(const int* path_nodes, const int* path_lens, int maxlen, cons
                    const int* pair_b, int K, const int* mv_ptr, const int* mv_node, int G, int e0, int e1, const float* GP,
                    const float* bias, const float* x, long long ldx, float* xt, long long ldxt, int width, int cnn_col, int Dout, int S,
                    int device, void* stream) {
-  MMFT_REQUIRE(S == 64, "swap_rows: the prefix block must be 64 cells (one bitmap word per block)");
-  MMFT_REQUIRE(mask_map_ok(map_x, map_y), "swap_rows: the map must hold a multiple of 64 cells, at most 65536");
-  MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && maxlen >= 1 && T >= 1 && G >= 1 && K >= 1 && RP >= 0,
-               "swap_rows: bad sizes (Dout a multiple of 4 in [4, 1024], maxlen >= 1, T >= 1, G >= 1, K >= 1, RP >= 0)");
-  MMFT_REQUIRE(cnn_col >= 0 && cnn_col % 4 == 0 && ldx % 4 == 0 && ldxt % 4 == 0 && (long long)cnn_col + Dout <= width &&
-                   width <= ldx && width <= ldxt,
-               "swap_rows: bad columns (cnn_col, ldx, ldxt multiples of 4, 0 <= cnn_col, cnn_col + Dout <= width <= ldx, ldxt)");
+  const TrialRowCall c = {"swap_rows", path_nodes, path_lens, maxlen, loc_x, loc_y, map_x, map_y, paths, f_off, GP, bias,
+                          x, ldx, xt, ldxt, width, cnn_col, Dout, S, device, stream};
+  int rc = trial_row_check(c, T >= 1 && G >= 1 && K >= 1 && RP >= 0, "T >= 1, G >= 1, K >= 1, RP >= 0");
+  if (rc) return rc;
   MMFT_REQUIRE(e0 >= 0 && e0 <= e1 && e1 <= RP, "swap_rows: need 0 <= e0 <= e1 <= RP = %d (got %d, %d)", RP, e0, e1);
   if (e0 == e1) return MMFT_OK;
-  MMFT_REQUIRE(path_nodes && path_lens && loc_x && loc_y && paths && prow_row && prow_pair && pair_a && pair_b && mv_ptr && mv_node &&
-                   GP && x && xt,
-               "swap_rows: null pointer");
-  MMFT_REQUIRE(aligned16(GP) && aligned16(x) && aligned16(xt) && (!bias || aligned16(bias)), "swap_rows: 16-byte alignment");
-  DeviceGuard dg(device);
-  const int P = map_x * map_y;
-  static DynLdsOnce once;
-  int arc = ensure_dyn_lds(once, (const void*)swap_rows_kernel, (int)trial_lds_bytes(MASK_MAX_CELLS), "swap_rows");
-  if (arc) return arc;
   SwapRowsArgs a;
-  TrialRowArgs& r = a.row;
-  r.path_nodes = path_nodes; r.path_lens = path_lens; r.loc_x = loc_x; r.loc_y = loc_y; r.paths = paths; r.foff = f_off;
-  r.GP = GP; r.bias = bias; r.x = x; r.xt = xt; r.ldx = ldx; r.ldxt = ldxt;
-  r.maxlen = maxlen; r.map_x = map_x; r.map_y = map_y; r.width = width; r.cnn_col = cnn_col; r.Dout = Dout;
   a.prow_row = prow_row; a.prow_pair = prow_pair; a.pair_a = pair_a; a.pair_b = pair_b; a.mv_ptr = mv_ptr; a.mv_node = mv_node;
   a.K = K; a.G = G; a.e0 = e0;
-  MMFT_LAUNCH_LDS("swap_rows_kernel", 0.0, 0.0, swap_rows_kernel, dim3((unsigned)(e1 - e0)), dim3(256), trial_lds_bytes(P),
-                  (hipStream_t)stream, a);
-  return check_launch("swap_rows");
+  return trial_row_launch<SwapRowsArgs, swap_rows_kernel>(c, "swap_rows_kernel", a, (unsigned)(e1 - e0),
+                                                          prow_row && prow_pair && pair_a && pair_b && mv_ptr && mv_node);
 }
 
 int mmft_swap_score(const float* pred_trial, const float* pred_base, const float* required, int T, const int* prow_ptr,
@@ -180,10 +147,10 @@ int mmft_swap_score(const float* pred_trial, const float* pred_base, const float
   MMFT_REQUIRE(pred_base && required && prow_ptr && dq && dviol && new_nan && capped && worst && worst_row && pick &&
                    ((prow_row && pred_trial) || RP == 0),
                "swap_score: null pointer");
-  MMFT_REQUIRE(swap_aligned8(dq), "swap_score: dq must be 8-byte aligned");
+  MMFT_REQUIRE(aligned8(dq), "swap_score: dq must be 8-byte aligned");
   if (base) {
     MMFT_REQUIRE(n >= 1 && n <= (1 << 24) && design_rows, "swap_score: the base figures need design_rows [n], 1 <= n <= 2^24 (got n %d)", n);
-    MMFT_REQUIRE(swap_aligned8(base), "swap_score: base must be 8-byte aligned");
+    MMFT_REQUIRE(aligned8(base), "swap_score: base must be 8-byte aligned");
   }
   DeviceGuard dg(device);
   hipStream_t st = (hipStream_t)stream;
@@ -193,16 +160,7 @@ int mmft_swap_score(const float* pred_trial, const float* pred_base, const float
               pick);
   int rc = check_launch("swap_score");
   if (rc || !base) return rc;
-  hipError_t e = hipMemsetAsync(base, 0, 3 * sizeof(long long), st);
-  if (e != hipSuccess) {
-    set_error("swap_score: clearing the base figures failed: %s", hipGetErrorString(e));
-    return MMFT_ERR_LAUNCH;
-  }
-  int grid = cdiv(n, 256);
-  grid = grid > 256 ? 256 : grid;
-  MMFT_LAUNCH("swap_base_kernel", 0.0, 12.0 * n, swap_base_kernel, dim3(grid), dim3(256), st, pred_base, required, design_rows, n, T,
-              scale_log2, reinterpret_cast<search_u64*>(base));
-  return check_launch("swap_base");
+  return search_base_launch("swap_score", "swap_base", pred_base, required, design_rows, n, T, scale_log2, base, st);
 }
 
 int mmft_swap_apply(int* loc_x, int* loc_y, int n_nodes, const int* sel, const int* pick, const int* pair_a, const int* pair_b, int K,

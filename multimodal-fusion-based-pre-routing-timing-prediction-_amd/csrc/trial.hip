@@ -4,7 +4,8 @@
 // rasterised with them (mask_raster_path_moved, mask_rule.h: the boxes of mask_raster_path, on the same mask_or_box) and
 // projected by place_project (place_project.h), the function placed_fc_fwd_kernel calls - the h_cnn columns are that kernel's
 // bits on moved tables, and the tables are never written.  The row's other columns are copied.  Everything after the staging
-// is trial_row_write (trial_row.h), which search.hip calls too.
+// is trial_row_write (trial_row.h), which the rows kernels of search.hip, refine.hip and swap.hip call too; the entry point
+// refuses and launches through that header's launcher, as theirs do.
 // trial_reduce_kernel: one workgroup per candidate walks the design's rows, takes the trial prediction where the candidate has
 // a pair and the resident one elsewhere, and reduces counts, the worst (slack, row) key and the fp64 negative sum in one fixed
 // tree.
@@ -33,8 +34,7 @@ __global__ void __launch_bounds__(256) trial_rows_kernel(TrialRowsArgs a) {
   const int p = blockIdx.x, tid = threadIdx.x;
   const int t = a.pair_row[p], k = a.pair_cand[p];
   const int m0 = a.mv_ptr[k];
-  int n_mv = a.mv_ptr[k + 1] - m0;                      // the same for every thread
-  n_mv = n_mv < 0 ? 0 : (n_mv > TRIAL_MOVES ? TRIAL_MOVES : n_mv);
+  const int n_mv = clamp_to(a.mv_ptr[k + 1] - m0, TRIAL_MOVES);      // the same for every thread
   if (tid < n_mv) {
     mv.node[tid] = a.mv_node[m0 + tid];
     mv.x[tid] = a.mv_x[m0 + tid];
@@ -43,15 +43,12 @@ __global__ void __launch_bounds__(256) trial_rows_kernel(TrialRowsArgs a) {
   trial_row_write(a.row, L, mv, n_mv, t, p, tid);       // trial_row.h: the copy, the raster under the overrides, the projection
 }
 
-typedef unsigned long long trial_u64;
-constexpr trial_u64 TRIAL_KEY_NONE = ~0ull;   // no valid key has all-ones slack bits (that pattern is a NaN)
-
 __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restrict__ pred_base, const float* __restrict__ pred_trial,
                                                            const float* __restrict__ required, const int* __restrict__ design_rows,
                                                            int n, int T, const int* __restrict__ pair_ptr,
                                                            const int* __restrict__ pair_row, int K, double* __restrict__ summary) {
   __shared__ double s_sum[4];
-  __shared__ trial_u64 s_key[4];
+  __shared__ slack_u64 s_key[4];
   __shared__ int s_cnt[4][3];
   const int k = blockIdx.x, tid = threadIdx.x;
   int p0 = 0, p1 = 0;                                   // the candidate's pairs; entry K, the base, has none
@@ -61,7 +58,7 @@ __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restri
   }
   int nv = 0, nn = 0, nneg = 0;
   double sum = 0.0;
-  trial_u64 best = TRIAL_KEY_NONE;
+  slack_u64 best = SLACK_KEY_NONE;
   for (int i = tid; i < n; i += 256) {
     const int r = design_rows[i];
     float s = __uint_as_float(0x7fc00000u);
@@ -79,7 +76,7 @@ __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restri
       ++nn;
     } else {
       ++nv;
-      const trial_u64 key = ((trial_u64)ordered_bits(s) << 32) | (unsigned)r;
+      const slack_u64 key = ((slack_u64)ordered_bits(s) << 32) | (unsigned)r;
       best = key < best ? key : best;
       if (s < 0.f) {
         ++nneg;
@@ -93,7 +90,7 @@ __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restri
     nn += __shfl_xor(nn, o, 64);
     nneg += __shfl_xor(nneg, o, 64);
     sum += __shfl_xor(sum, o, 64);
-    const trial_u64 other = __shfl_xor(best, o, 64);
+    const slack_u64 other = __shfl_xor(best, o, 64);
     best = other < best ? other : best;
   }
   if ((tid & 63) == 0) {
@@ -105,7 +102,7 @@ __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restri
   if (tid == 0) {
     nv = nn = nneg = 0;
     sum = 0.0;
-    best = TRIAL_KEY_NONE;
+    best = SLACK_KEY_NONE;
     for (int w = 0; w < 4; ++w) {
       nv += s_cnt[w][0]; nn += s_cnt[w][1]; nneg += s_cnt[w][2];
       sum += s_sum[w];
@@ -113,8 +110,8 @@ __global__ void __launch_bounds__(256) trial_reduce_kernel(const float* __restri
     }
     double* o = summary + (long long)k * 6;
     o[0] = nv; o[1] = nn; o[2] = nneg;
-    o[3] = best == TRIAL_KEY_NONE ? (double)__uint_as_float(0x7fc00000u) : (double)ordered_float((unsigned)(best >> 32));
-    o[4] = best == TRIAL_KEY_NONE ? -1.0 : (double)(int)(unsigned)(best & 0xffffffffull);
+    o[3] = best == SLACK_KEY_NONE ? (double)__uint_as_float(0x7fc00000u) : (double)ordered_float((unsigned)(best >> 32));
+    o[4] = best == SLACK_KEY_NONE ? -1.0 : (double)(int)(unsigned)(best & 0xffffffffull);
     o[5] = sum;
   }
 }
@@ -130,31 +127,15 @@ int mmft_trial_rows(const int* path_nodes, const int* path_lens, int maxlen, con
                     const int* mv_ptr, const int* mv_node, const int* mv_x, const int* mv_y, int K, const float* GP,
                     const float* bias, const float* x, long long ldx, float* xt, long long ldxt, int width, int cnn_col, int Dout,
                     int S, int device, void* stream) {
-  MMFT_REQUIRE(S == 64, "trial_rows: the prefix block must be 64 cells (one bitmap word per block)");
-  MMFT_REQUIRE(mask_map_ok(map_x, map_y), "trial_rows: the map must hold a multiple of 64 cells, at most 65536");
-  MMFT_REQUIRE(Dout >= 4 && Dout % 4 == 0 && Dout <= 1024 && maxlen >= 1 && T >= 1 && K >= 1 && n_pairs >= 0,
-               "trial_rows: bad sizes (Dout a multiple of 4 in [4, 1024], maxlen >= 1, T >= 1, K >= 1, n_pairs >= 0)");
-  MMFT_REQUIRE(cnn_col >= 0 && cnn_col % 4 == 0 && ldx % 4 == 0 && ldxt % 4 == 0 && (long long)cnn_col + Dout <= width &&
-                   width <= ldx && width <= ldxt,
-               "trial_rows: bad columns (cnn_col, ldx, ldxt multiples of 4, 0 <= cnn_col, cnn_col + Dout <= width <= ldx, ldxt)");
+  const TrialRowCall c = {"trial_rows", path_nodes, path_lens, maxlen, loc_x, loc_y, map_x, map_y, paths, f_off, GP, bias,
+                          x, ldx, xt, ldxt, width, cnn_col, Dout, S, device, stream};
+  int rc = trial_row_check(c, T >= 1 && K >= 1 && n_pairs >= 0, "T >= 1, K >= 1, n_pairs >= 0");
+  if (rc) return rc;
   if (n_pairs == 0) return MMFT_OK;
-  MMFT_REQUIRE(path_nodes && path_lens && loc_x && loc_y && paths && pair_row && pair_cand && mv_ptr && mv_node && mv_x && mv_y &&
-                   GP && x && xt,
-               "trial_rows: null pointer");
-  MMFT_REQUIRE(aligned16(GP) && aligned16(x) && aligned16(xt) && (!bias || aligned16(bias)), "trial_rows: 16-byte alignment");
-  DeviceGuard dg(device);
-  const int P = map_x * map_y;
-  static DynLdsOnce once;
-  int arc = ensure_dyn_lds(once, (const void*)trial_rows_kernel, (int)trial_lds_bytes(MASK_MAX_CELLS), "trial_rows");
-  if (arc) return arc;
   TrialRowsArgs a;
-  TrialRowArgs& r = a.row;
-  r.path_nodes = path_nodes; r.path_lens = path_lens; r.loc_x = loc_x; r.loc_y = loc_y; r.paths = paths; r.foff = f_off;
-  r.GP = GP; r.bias = bias; r.x = x; r.xt = xt; r.ldx = ldx; r.ldxt = ldxt;
-  r.maxlen = maxlen; r.map_x = map_x; r.map_y = map_y; r.width = width; r.cnn_col = cnn_col; r.Dout = Dout;
   a.pair_row = pair_row; a.pair_cand = pair_cand; a.mv_ptr = mv_ptr; a.mv_node = mv_node; a.mv_x = mv_x; a.mv_y = mv_y;
-  MMFT_LAUNCH_LDS("trial_rows_kernel", 0.0, 0.0, trial_rows_kernel, dim3(n_pairs), dim3(256), trial_lds_bytes(P), (hipStream_t)stream, a);
-  return check_launch("trial_rows");
+  return trial_row_launch<TrialRowsArgs, trial_rows_kernel>(c, "trial_rows_kernel", a, n_pairs,
+                                                            pair_row && pair_cand && mv_ptr && mv_node && mv_x && mv_y);
 }
 
 int mmft_trial_reduce(const float* pred_base, const float* pred_trial, const float* required, const int* design_rows, int n, int T,
@@ -164,7 +145,7 @@ int mmft_trial_reduce(const float* pred_base, const float* pred_trial, const flo
                n_pairs);
   MMFT_REQUIRE(pred_base && required && design_rows && summary && (pair_ptr || K == 0) && ((pair_row && pred_trial) || n_pairs == 0),
                "trial_reduce: null pointer");
-  MMFT_REQUIRE((reinterpret_cast<uintptr_t>(summary) & 7) == 0, "trial_reduce: summary must be 8-byte aligned");
+  MMFT_REQUIRE(aligned8(summary), "trial_reduce: summary must be 8-byte aligned");
   DeviceGuard dg(device);
   const double alg_bytes = (double)(K + 1) * (12.0 * n + 48.0);
   MMFT_LAUNCH("trial_reduce_kernel", 0.0, alg_bytes, trial_reduce_kernel, dim3(K + 1), dim3(256), (hipStream_t)stream, pred_base,
