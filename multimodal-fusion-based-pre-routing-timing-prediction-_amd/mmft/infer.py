@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import commit, gradsink, lib, ops, search, swap, trial
+from . import commit, gradsink, lib, ops, pairs, search, swap, trial
 from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
 from .placement import batch_tables, placed_fc
@@ -451,7 +451,7 @@ class Predictor(ResidentDesigns):
         plan of another Predictor; TypeError for something that is no swap plan."""
         return swap.swap_moves(self, splan, scale_log2, max_rows)
 
-    def commit_swaps(self, splan, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+    def commit_swaps(self, splan, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True, patch=False):
         """swap_moves, then the commit of a conflict-free set of swaps, on the device (mmft.swap; the selection is
         mmft_commit_select of include/mmft_commit.h as it stands).  A pair is a CANDIDATE iff it is eligible and improves the
         design's sum by at least max(1, ceil(min_gain * 2^scale_log2)) quanta, commit_moves' own threshold; two pairs
@@ -467,8 +467,49 @@ class Predictor(ResidentDesigns):
         (addresses stay: a replayed graph sees them), and the trial state is stale exactly as after commit_moves():
         trial_moves / search_moves / swap_moves / commit_swaps refuse until a predict() has run.  apply=False: nothing
         another call reads is written.  Eager: refused under an outer stream capture.  Refusals: those of swap_moves, and
-        ValueError for a min_gain that is negative, not finite or too large for 62 bits of quanta."""
-        return swap.commit_swaps(self, splan, scale_log2, max_rows, min_gain, apply)
+        ValueError for a min_gain that is negative, not finite or too large for 62 bits of quanta.
+
+        patch=True (needs apply=True, else ValueError; mmft_refine_patch of include/mmft_refine.h as it stands, the pairs as
+        its groups): before the pins move, the rows of the selected pairs' entries under their swaps are written into the
+        kept head state - the h_cnn columns of the head's input and the predictions -, which then holds, bit for bit, what
+        a predict() on the swapped pins would write.  A call of one chunk patches from the rows of its scoring pass; a call
+        of several (max_rows) recomputes each chunk's rows first.  The trial state stays fresh: swap_moves, commit_swaps,
+        near_swap_plan and the window calls may follow at once.  The result gains n_patched, the entries written, in the
+        same copy.  The kept predictions ARE the static buffer a replayed predict() returned: a tensor the caller still
+        holds from the last predict() changes in place.  report() and criticality() keep describing the last predict()."""
+        return swap.commit_swaps(self, splan, scale_log2, max_rows, min_gain, apply, patch)
+
+    def near_swap_plan(self, plan, reach, group_class=None, max_pairs=1 << 20):
+        """The swap plan of the groups of `plan` that are NEAR each other on the resident pins as they are now, built on the
+        device (trials=True; mmft.pairs, include/mmft_pairs.h).  Groups a < b pair iff both are non-empty, hold at most 64
+        pins together, share a class - group_class: an int array [G], None for one class - and their anchors (first pins)
+        lie 1 .. reach map cells apart in the larger of the two axes (differences in 64 bits; coinciding anchors are no
+        pair).  The pairs come in ascending (a, b), K in all, and with them every table of swap_plan: the result is an
+        ordinary swap plan for swap_moves and commit_swaps.
+
+        Six launches - count, scan, fill of the pairs; count, scan, fill of their rows - and THREE small synchronisations
+        per plan: the read of K (8 bytes), the read of RP (8 bytes), and one copy of the int32 buffer back, from which the
+        plan's host tables are decoded.  No host table arithmetic.  The neighbour test is all-pairs on the device.
+
+        None where nothing is near (K == 0): a normal end of a refinement.  Needs no predict() and does not look at the trial
+        state: it reads pins only.  RuntimeError without trials=True; TypeError for something that is no search plan;
+        ValueError for a plan of another Predictor, a plan in which two groups hold one pin, more than 2^24 rows and groups
+        together, a reach that is not an int in [1, 2^31 - 1], a group_class that is not an int array [G], K > max_pairs
+        (the message names K) and RP + 2 K >= 2^31."""
+        return pairs.near_swap_plan(self, plan, reach, group_class, max_pairs)
+
+    def refine_swaps(self, plan, reach, passes=4, patch=True, group_class=None, **kw):
+        """near_swap_plan(plan, reach, group_class) on the pins as they are now, then commit_swaps(patch=patch, **kw),
+        repeated until nothing is near, a pass selects nothing or `passes` have run: the list of the passes' results, each
+        with its plan's pair_a / pair_b.  Every pass pairs the cells that are near each other at that moment.  Each pass's
+        predicted_nsum is the next pass's base['nsum'], and the sums never increase.
+
+        patch=True: no pass needs a predict() - the patched commit keeps the head state current -, and one predict() follows
+        the loop, after which the static output, report() and criticality() are current again.  patch=False: a predict()
+        follows every pass.  Needs a predict() before the call, like every trial call.  Refusals: those of near_swap_plan
+        and commit_swaps; ValueError for passes that is not an integer of at least 1 and for apply=False; refused under an
+        outer stream capture."""
+        return pairs.refine_swaps(self, plan, reach, passes, patch, group_class, **kw)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

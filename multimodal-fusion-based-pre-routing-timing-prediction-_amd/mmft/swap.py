@@ -22,6 +22,7 @@ import torch
 
 from . import commit as CM
 from . import lib
+from . import refine as RF
 from . import search as SE
 from . import trial as TR
 
@@ -196,6 +197,21 @@ class SwapPlan:
         cuts = np.concatenate([[0], np.cumsum([v.shape[0] for v in parts])])
         self.dev = [self.ints[cuts[j]:cuts[j + 1]] for j in range(len(parts))]
 
+    @classmethod
+    def from_device(cls, owner, plan, ints, K, RP, T):
+        """The plan of tables that were built on the device (mmft.pairs): `ints` is the int32 buffer in the layout above, and
+        the host tables are decoded from ONE copy of it."""
+        self = cls.__new__(cls)
+        self.owner, self.plan, self.i, self.T = owner, plan, plan.i, int(T)
+        self.K, self.RP, self.G, self.ints = int(K), int(RP), plan.G, ints
+        cuts = np.concatenate([[0], np.cumsum([K, K, K + 1, RP, RP, K + 1, RP + 2 * K])])
+        assert ints.dtype == torch.int32 and ints.numel() == cuts[-1]
+        self.dev = [ints[cuts[j]:cuts[j + 1]] for j in range(7)]
+        host = ints.cpu().numpy().astype(np.int64)
+        self.pair_a, self.pair_b, self.prow_ptr, self.prow_row, self.prow_pair, self.sel_ptr, self.sel_row = \
+            [host[cuts[j]:cuts[j + 1]] for j in range(7)]
+        return self
+
 
 def swap_plan(p, plan, pair_a, pair_b):
     """Predictor.swap_plan: see there."""
@@ -227,11 +243,14 @@ def chunks(prow_ptr, max_rows):
     return out
 
 
-def prepare(p, splan, scale_log2=20, max_rows=65536, min_gain=None, apply=False, who='swap_moves'):
+def prepare(p, splan, scale_log2=20, max_rows=65536, min_gain=None, apply=False, who='swap_moves', patch=False):
     """Stage 1, host: trial.check_state's state and mode refusals, validation, the chunks, the call's ONE output buffer - int64
-    [dq K | base 3 | stats 4], then int32 [dviol | new_nan | capped | worst | worst_row | pick | sel, K each].  min_gain not
-    None: the call selects (commit.min_quanta is its threshold) and, with `apply`, writes.  No host table is built and nothing
-    is uploaded: the plan holds the tables.  Returns the call `launch` takes."""
+    [dq K | base 3 | stats 4], then int32 [dviol | new_nan | capped | worst | worst_row | pick | sel, K each] and - patch=True -
+    behind those the two counts of mmft_refine_patch, int64, per chunk.  min_gain not None: the call selects (commit.min_quanta
+    is its threshold) and, with `apply`, writes.  No host table is built and nothing is uploaded: the plan holds the tables.
+    Returns the call `launch` takes."""
+    if patch and not apply:
+        raise ValueError(f'{who}: patch=True writes the rows of the moved pins into the kept state; it needs apply=True')
     TR.check_state(p, who, 'the chunks of the pairs are launched from the host per call')
     if not isinstance(splan, SwapPlan):
         raise TypeError(f'{who}: the plan must come from swap_plan(), got {type(splan).__name__}')
@@ -239,8 +258,12 @@ def prepare(p, splan, scale_log2=20, max_rows=65536, min_gain=None, apply=False,
         raise ValueError(f'{who}: the plan belongs to another Predictor')
     SE.check_call(0, 1, scale_log2, max_rows, who)
     K = splan.K
-    call = dict(splan=splan, scale_log2=int(scale_log2), chunks=chunks(splan.prow_ptr, max_rows), n64=K + 7,
-                raw=torch.empty(K + 7 + (7 * K + 1) // 2, dtype=torch.int64, device=p.device),
+    if patch and not p._trial.kept['pred'].is_contiguous():
+        raise ValueError(f'{who}: patch=True writes the kept predictions in place; they are not contiguous')
+    cuts = chunks(splan.prow_ptr, max_rows)
+    tail = K + 7 + (7 * K + 1) // 2
+    call = dict(splan=splan, scale_log2=int(scale_log2), chunks=cuts, n64=K + 7, tail=tail, patch=bool(patch),
+                raw=torch.empty(tail + (2 * len(cuts) if patch else 0), dtype=torch.int64, device=p.device),
                 min_q=None if min_gain is None else CM.min_quanta(min_gain, scale_log2), apply=bool(apply))
     if call['min_q'] is not None:
         owner = getattr(splan, 'commit_owner', None)         # scratch over the rows and the groups, kept with the plan
@@ -252,7 +275,7 @@ def prepare(p, splan, scale_log2=20, max_rows=65536, min_gain=None, apply=False,
 
 def _views(raw, K, n64):
     """The tables inside the call's buffer (torch tensor or numpy array alike)."""
-    i64, i32 = raw[:n64], raw[n64:].view(torch.int32 if torch.is_tensor(raw) else np.int32)
+    i64, i32 = raw[:n64], raw[n64:n64 + (7 * K + 1) // 2].view(torch.int32 if torch.is_tensor(raw) else np.int32)
     f32 = torch.float32 if torch.is_tensor(raw) else np.float32
     return dict(dq=i64[:K], base=i64[K:K + 3], stats=i64[K + 3:K + 7], dviol=i32[:K], new_nan=i32[K:2 * K], capped=i32[2 * K:3 * K],
                 worst=i32[3 * K:4 * K].view(f32), worst_row=i32[4 * K:5 * K], pick=i32[5 * K:6 * K], sel=i32[6 * K:7 * K])
@@ -262,7 +285,12 @@ def launch(p, call, timed=None):
     """Stage 2, device, on the current stream: per chunk of pairs mmft_swap_rows over its entries, mmft_head_mlp_fwd over
     their rows and mmft_swap_score (the first one with the base figures); then, for a call that selects, mmft_commit_select
     over the select table and - apply - mmft_swap_apply on the resident pins, after which the trial state is stale as after
-    update().  Returns the call.  `timed`: a callable that is handed each part as a function."""
+    update().  patch=True: between the two, mmft_refine_patch (mmft_refine.h, as it stands) with the pairs as its groups -
+    best_w = pick at radius 1, grow_row = prow_row, grow_grp = prow_pair, G = K - writes the selected pairs' entries into the
+    kept x and pred, and the trial state stays fresh.  A call of one chunk patches from the rows and predictions of its
+    scoring pass, in one launch; a call of several runs mmft_swap_rows and the head again per chunk - the pins have not
+    moved yet - and patches that chunk's slice, each chunk with two counts of its own.  Returns the call.  `timed`: a callable
+    that is handed each part as a function."""
     run = timed if timed is not None else (lambda name, fn: fn())
     splan, placed, b, kept = call['splan'], p._placed, p.batch, p._trial.kept
     plan = splan.plan
@@ -280,15 +308,18 @@ def launch(p, call, timed=None):
     pred_t = torch.empty(most, dtype=torch.float32, device=p.device) if RP else None
     rows = p.slack.rows_of(splan.i)
 
+    def entry_rows(e0, e1):
+        abi('mmft_swap_rows', placed.nodes, placed.lens, placed.maxlen, placed.loc_x, placed.loc_y, placed.map_x, placed.map_y,
+            p._sel.paths, p._sel.feat_off if b.B > 1 else None, T, d_prow, d_ppair, RP, d_pa, d_pb, K, d_mptr, d_node, G, e0, e1,
+            GP, fcn.bias, x, x.stride(0), xt, width, width, kept['cnn_col'], Dout, b.masks.run_block, *lib.stream_args(x))
+        lib.head('mmft_head_mlp_fwd', xt, width, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, None, pred_t,
+                 e1 - e0, mods[0].weight.shape[1], mods[0].weight.shape[0], 1, *lib.stream_args(x))
+
     def score():
         for k0, k1 in call['chunks']:
             e0, e1 = int(splan.prow_ptr[k0]), int(splan.prow_ptr[k1])
             if e1 > e0:
-                abi('mmft_swap_rows', placed.nodes, placed.lens, placed.maxlen, placed.loc_x, placed.loc_y, placed.map_x, placed.map_y,
-                    p._sel.paths, p._sel.feat_off if b.B > 1 else None, T, d_prow, d_ppair, RP, d_pa, d_pb, K, d_mptr, d_node, G, e0, e1,
-                    GP, fcn.bias, x, x.stride(0), xt, width, width, kept['cnn_col'], Dout, b.masks.run_block, *lib.stream_args(x))
-                lib.head('mmft_head_mlp_fwd', xt, width, mods[0].weight, mods[0].bias, mods[2].weight, mods[2].bias, None, pred_t,
-                         e1 - e0, mods[0].weight.shape[1], mods[0].weight.shape[0], 1, *lib.stream_args(x))
+                entry_rows(e0, e1)
             abi('mmft_swap_score', pred_t, pred.reshape(-1), p.slack.required, T, d_pptr, d_prow if RP else None, K, RP, k0, k1, scale,
                 v['dq'], v['dviol'], v['new_nan'], v['capped'], v['worst'], v['worst_row'], v['pick'],
                 v['base'] if k0 == 0 else None, rows, rows.numel(), *lib.stream_args(x))
@@ -297,8 +328,21 @@ def launch(p, call, timed=None):
     if call['min_q'] is not None:
         run('select', lambda: CM.abi('mmft_commit_select', v['pick'], v['dq'], K, 1, d_sptr, d_srow, RP + 2 * K, T + G, call['min_q'],
                                      v['sel'], v['stats'], call['owner'], *lib.stream_args(x)))
+        if call['patch']:
+            counts, one = call['raw'][call['tail']:], len(call['chunks']) == 1
+
+            def patch():
+                for c, (k0, k1) in enumerate(call['chunks']):
+                    e0, e1 = int(splan.prow_ptr[k0]), int(splan.prow_ptr[k1])
+                    if e1 > e0 and not one:                  # (one chunk: xt and pred_t of the scoring pass hold these rows)
+                        entry_rows(e0, e1)
+                    some = e1 > e0
+                    RF.abi('mmft_refine_patch', x, x.stride(0), pred.reshape(-1), T, xt if some else None, width, pred_t if some else None,
+                           v['sel'], v['pick'], 1, d_prow[e0:] if some else None, d_ppair[e0:] if some else None, e1 - e0, K,
+                           kept['cnn_col'], Dout, counts[2 * c:2 * c + 2], *lib.stream_args(x))
+            run('patch', patch)
         if call['apply']:
-            p._trial.stale = True                            # until the next predict(), exactly as update() leaves it
+            p._trial.stale = not call['patch']               # unpatched: until the next predict(), exactly as update() leaves it
             run('apply', lambda: abi('mmft_swap_apply', placed.loc_x, placed.loc_y, placed.loc_x.numel(), v['sel'], v['pick'], d_pa, d_pb, K,
                                      d_mptr, d_node if plan.M else None, G, plan.M, *lib.stream_args(x)))
     return call
@@ -322,6 +366,8 @@ def fetch(call):
         res['pair_gain'] = res['gain']
         res.update(selected=v['sel'] != 0, n_selected=int(stats[0]), n_candidates=int(stats[2]), rounds=int(stats[3]), sum_dq=sum_dq,
                    gain=float(-sum_dq) * 2.0 ** -scale, predicted_nsum=res['base']['nsum'] + sum_dq)
+        if call['patch']:                                    # the chunks' counts, summed here
+            res['n_patched'] = int(host[call['tail']:].reshape(-1, 2)[:, 0].sum())
     return res
 
 
@@ -330,6 +376,6 @@ def swap_moves(p, splan, scale_log2=20, max_rows=65536):
     return fetch(launch(p, prepare(p, splan, scale_log2, max_rows)))
 
 
-def commit_swaps(p, splan, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True):
+def commit_swaps(p, splan, scale_log2=20, max_rows=65536, min_gain=0.0, apply=True, patch=False):
     """Predictor.commit_swaps: see there."""
-    return fetch(launch(p, prepare(p, splan, scale_log2, max_rows, min_gain, apply, who='commit_swaps')))
+    return fetch(launch(p, prepare(p, splan, scale_log2, max_rows, min_gain, apply, who='commit_swaps', patch=patch)))

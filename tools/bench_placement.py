@@ -871,6 +871,115 @@ def refine_rows(a, emit, designs, ids, pmodel, cnn, dev):
              resident_is_faster=bool(med[True]['per_pass_ms'] < med[False]['per_pass_ms']))
 
 
+def near_swaps_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--near-swaps: Predictor.near_swap_plan over the groups of design 0 next to the host's route to the same plan (a download
+    of loc_x / loc_y, near_pairs_host, swap_plan), the five kernels timed apart, and refine_swaps(patch=True) next to
+    patch=False per pass, in the same run."""
+    from mmft import pairs as PR
+    d = designs[0]
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    ptr, _ = p._trial.rows_of_pin
+    N = int(d.N)
+    count = ptr[1:N + 1] - ptr[:N]                                     # design 0: offset 0
+    rng = np.random.default_rng(7)
+    on = rng.permutation(np.flatnonzero(count > 0)).astype(np.int64)
+    n1, n8 = min(a.groups, on.size), min(a.groups // 8, on.size // 8)
+    sets = {'single': (on[:n1], None), 'group8': (on[:8 * n8], np.arange(0, 8 * n8 + 1, 8, dtype=np.int64))}
+    home_x, home_y = np.asarray(d.pin_x).copy(), np.asarray(d.pin_y).copy()
+    reach = a.reach
+    emit(row='near_swap_shapes', designs=a.designs, map=designs[0].map_size, rows=int(p.T), pins_on_a_row_design0=int(on.size), reach=reach,
+         passes=a.passes)
+    plans = {nm: p.search_plan(0, pins, gptr) for nm, (pins, gptr) in sets.items()}
+
+    def go_home():
+        p.update(0, pin_x=home_x, pin_y=home_y)
+        p.predict()
+        torch.cuda.synchronize()
+
+    def device_once(plan):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        sp = p.near_swap_plan(plan, reach)
+        torch.cuda.synchronize()
+        return sp, dict(call_ms=1e3 * (time.perf_counter() - t0))
+
+    def host_once(plan):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lx, ly = p._placed.loc_x.cpu().numpy(), p._placed.loc_y.cpu().numpy()
+        t1 = time.perf_counter()
+        pa, pb = PR.near_pairs_host(plan.mv_ptr, plan.mv_node, lx, ly, reach)
+        t2 = time.perf_counter()
+        sp = p.swap_plan(plan, pa, pb)
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        return sp, dict(download_ms=1e3 * (t1 - t0), near_pairs_host_ms=1e3 * (t2 - t1), swap_plan_ms=1e3 * (t3 - t2), call_ms=1e3 * (t3 - t0))
+
+    def kernels_once(plan):
+        ms = {}
+
+        def run(name, fn):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            e1.synchronize()
+            ms[name + '_ms'] = ms.get(name + '_ms', 0.0) + e0.elapsed_time(e1)
+        PR.near_swap_plan(p, plan, reach, timed=run)
+        return ms
+
+    def refine_once(plan, patch):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        res = p.refine_swaps(plan, reach, passes=a.passes, patch=patch, scale_log2=a.scale_log2, max_rows=a.max_rows, min_gain=a.min_gain)
+        torch.cuda.synchronize()
+        ms = 1e3 * (time.perf_counter() - t0)
+        go_home()
+        return res, dict(call_ms=ms, passes=len(res), per_pass_ms=ms / max(len(res), 1))
+
+    names = ('pair_a', 'pair_b', 'prow_ptr', 'prow_row', 'prow_pair', 'sel_ptr', 'sel_row')
+    for nm, plan in plans.items():                                      # the routes agree
+        got, want = device_once(plan)[0], host_once(plan)[0]
+        same = all(np.array_equal(getattr(got, k), getattr(want, k)) for k in names) and torch.equal(got.ints, want.ints)
+        on_dev, on_host = refine_once(plan, True)[0], refine_once(plan, False)[0]
+        keys = ('n_selected', 'sum_dq', 'predicted_nsum')
+        agree = len(on_dev) == len(on_host) and all(u[k] == v[k] for u, v in zip(on_dev, on_host) for k in keys)
+        agree &= all(np.array_equal(u['pair_a'], v['pair_a']) and np.array_equal(u['pair_b'], v['pair_b']) for u, v in zip(on_dev, on_host))
+        emit(row=f'near_swap_outputs_{nm}', groups=plan.G, pins=plan.M, pairs=got.K, entries=got.RP, device_equals_host_route=bool(same),
+             passes=len(on_dev), pairs_per_pass=[len(r['pair_a']) for r in on_dev], selected_per_pass=[r['n_selected'] for r in on_dev],
+             patched_per_pass=[r['n_patched'] for r in on_dev], base_tns=-on_dev[0]['base']['nsum'] * 2.0 ** -a.scale_log2,
+             final_tns=-on_dev[-1]['predicted_nsum'] * 2.0 ** -a.scale_log2, patched_equals_predict_per_pass=bool(agree))
+        assert same and agree
+    assert torch.equal(p.predict()[0], base)
+    rows = {nm: dict(device=[], host=[], kernels=[], patched=[], predicted=[]) for nm in plans}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, plan in plans.items():
+            rows[nm]['device'].append(device_once(plan)[1])
+            rows[nm]['host'].append(host_once(plan)[1])
+            rows[nm]['kernels'].append(kernels_once(plan))
+            rows[nm]['patched'].append(refine_once(plan, True)[1])
+            rows[nm]['predicted'].append(refine_once(plan, False)[1])
+    for nm, plan in plans.items():
+        med = {w: {k: statistics.median(r[k] for r in rs) for k in rs[0]} for w, rs in rows[nm].items()}
+        span = lambda w, k='call_ms': {k + '_min': min(r[k] for r in rows[nm][w]), k + '_max': max(r[k] for r in rows[nm][w])}
+        emit(row=f'near_swap_plan_{nm}', groups=plan.G, rounds=a.rounds, **{k + '_median': v for k, v in med['device'].items()}, **span('device'))
+        emit(row=f'near_swap_host_route_{nm}', groups=plan.G, rounds=a.rounds, **{k + '_median': v for k, v in med['host'].items()}, **span('host'),
+             speedup_over_host_route=med['host']['call_ms'] / med['device']['call_ms'],
+             device_is_faster=bool(med['device']['call_ms'] < med['host']['call_ms']))
+        emit(row=f'near_swap_kernels_{nm}', groups=plan.G, rounds=a.rounds, **{k + '_median': v for k, v in med['kernels'].items()})
+        emit(row=f'refine_swaps_patched_{nm}', groups=plan.G, rounds=a.rounds, **{k + '_median': v for k, v in med['patched'].items()},
+             **span('patched', 'per_pass_ms'))
+        emit(row=f'refine_swaps_predict_per_pass_{nm}', groups=plan.G, rounds=a.rounds, **{k + '_median': v for k, v in med['predicted'].items()},
+             **span('predicted', 'per_pass_ms'), per_pass_ratio_predict_over_patched=med['predicted']['per_pass_ms'] / med['patched']['per_pass_ms'],
+             patched_is_faster=bool(med['patched']['per_pass_ms'] < med['predicted']['per_pass_ms']))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -893,6 +1002,8 @@ def main():
     ap.add_argument('--refine', action='store_true')
     ap.add_argument('--swaps', action='store_true')
     ap.add_argument('--passes', type=int, default=4, help='--refine: the passes of one refine_moves call')
+    ap.add_argument('--near-swaps', action='store_true')
+    ap.add_argument('--reach', type=int, default=2, help='--near-swaps: groups pair whose anchors lie within this many map cells')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -938,6 +1049,10 @@ def main():
     if a.swaps:
         with lib.math_mode('bf16'), torch.no_grad():
             swaps_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.near_swaps:
+        with lib.math_mode('bf16'), torch.no_grad():
+            near_swaps_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
