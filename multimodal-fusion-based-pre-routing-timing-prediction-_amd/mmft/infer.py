@@ -12,7 +12,7 @@ import contextlib
 import numpy as np
 import torch
 
-from . import commit, gradsink, lib, ops, pairs, search, swap, trial
+from . import cells as _cells, commit, gradsink, lib, ops, pairs, search, swap, trial
 from .criticality import PredictorCriticality
 from .evaluate import frozen_statistics
 from .placement import batch_tables, placed_fc
@@ -510,6 +510,51 @@ class Predictor(ResidentDesigns):
         and commit_swaps; ValueError for passes that is not an integer of at least 1 and for apply=False; refused under an
         outer stream capture."""
         return pairs.refine_swaps(self, plan, reach, passes, patch, group_class, **kw)
+
+    def cell_set(self, i, pins, cell_ptr=None):
+        """C cells of design i for critical_plan / refine_cells (trials=True; mmft.cells, include/mmft_cells.h).  pins: int64
+        [M] node ids in design i's own numbering; cell_ptr: int64 [C + 1], CSR over pins - non-decreasing, from 0 to M -,
+        None: every pin a cell of its own.  Validated once, on the host, by search_plan's rules for groups - and no pin may
+        belong to two cells: that is what lets every plan built from the set be committed without a check per plan.  ONE
+        upload of cell_ptr | cell_node; the incidence of the selection is uploaded once per Predictor, on first use.  Valid
+        for the life of this Predictor, and its alone.
+        RuntimeError without trials=True; TypeError / IndexError / ValueError as search_plan validates its pins; ValueError
+        for a pin in two cells (the message names the pin and the cells) and for a design without a selected path."""
+        return _cells.cell_set(self, i, pins, cell_ptr)
+
+    def critical_plan(self, cells, slack_below=0.0, max_groups=1 << 20):
+        """The search plan of the cells of a cell set that VIOLATE NOW, built on the device from the kept predictions
+        (trials=True; mmft.cells, include/mmft_cells.h).  A cell is selected iff it holds 1 .. 64 pins and one of the rows
+        its pins lie on has a slack (required - pred) + 0.0f that is not NaN and strictly below slack_below, compared in
+        fp32; slack_below=None selects every cell of 1 .. 64 pins.  The selected cells, in ascending order, are the G groups
+        of an ordinary search plan - each with ALL its rows, word for word what search_plan gives for them - for
+        search_moves, commit_moves, refine_moves, swap_plan and near_swap_plan.  The plan also carries cell (int64 [G], the
+        cell of each group) and worst (fp32 [G], the smallest valid slack among its rows, NaN without one).
+
+        Five launches - count, three scans, fill - and TWO small synchronisations: the read of G, R and M' (24 bytes) and
+        one copy of the int32 buffer back.  No host table arithmetic, no download of the predictions.  The kept
+        predictions are those of the last predict() or of the patched commits since: the call is fresh after predict() and
+        after commit_moves(patch=True) / commit_swaps(patch=True), and refused after update() or an unpatched commit.
+
+        None where no cell is selected.  Refusals: those of search_moves' state and mode (RuntimeError without trials=True,
+        under an outer stream capture, before the first predict(), on a stale state; ValueError outside bf16 math mode
+        with the fused regression head); TypeError for something that is no cell set; ValueError for a cell set of another
+        Predictor, a slack_below that is NaN or no number, G > max_groups (the message names G) and a design whose rows
+        span more than 65536 rows of the selection (cells.critical_host and search_plan remain)."""
+        return _cells.critical_plan(self, cells, slack_below, max_groups)
+
+    def refine_cells(self, cells, radius=1, passes=4, slack_below=0.0, patch=True, **kw):
+        """critical_plan(cells, slack_below) on the state as it is now, then commit_moves(plan, radius, patch=patch, **kw),
+        repeated until no cell violates, a pass selects nothing or `passes` have run: the list of the passes' results, each
+        with its plan's `cell`.  Every pass searches the cells that violate at that moment, not those that violated before
+        the first.
+
+        patch=True: no pass needs a predict() - the patched commit keeps the head state current, and each pass's
+        predicted_nsum is the next pass's base['nsum'] -, and one predict() follows the loop, after which the static
+        output, report() and criticality() are current again.  patch=False: a predict() follows every pass.  Needs a
+        predict() before the call, like every trial call.  Refusals: those of critical_plan and commit_moves; ValueError for
+        passes that is not an integer of at least 1 and for apply=False."""
+        return _cells.refine_cells(self, cells, radius, passes, slack_below, patch, **kw)
 
     def _begin_incremental(self):
         """Decides what this predict()'s sweep is: the ordinary full one (incremental_active False) where the masked path is

@@ -103,6 +103,24 @@ class SearchPlan:
         cuts = np.concatenate([[0], np.cumsum(sizes)])
         self.dev = [self.ints[cuts[j]:cuts[j + 1]] for j in range(len(tables))]
 
+    @classmethod
+    def from_device(cls, owner, i, buf, G, R, M, node_off=0, pins_distinct=None):
+        """The plan of tables that were built on the device (mmft.cells): `buf` is an int32 buffer that starts with the five
+        tables in the layout above and may hold more words behind them.  The host tables are decoded from ONE copy of it;
+        `ints` and `dev` are views of it, and `tail` holds the words behind the tables as that copy brought them (int32)."""
+        self = cls.__new__(cls)
+        self.owner, self.i, self.node_off, self.pins_distinct = owner, int(i), int(node_off), pins_distinct
+        self.G, self.R, self.M = int(G), int(R), int(M)
+        cuts = np.concatenate([[0], np.cumsum([self.G + 1, self.R, self.R, self.G + 1, self.M])])
+        assert buf.dtype == torch.int32 and buf.dim() == 1 and buf.numel() >= cuts[-1]
+        self.ints = buf[:cuts[-1]]
+        self.dev = [buf[cuts[j]:cuts[j + 1]] for j in range(5)]
+        words = buf.cpu().numpy()
+        host = words[:cuts[-1]].astype(np.int64)
+        self.grow_ptr, self.grow_row, self.grow_grp, self.mv_ptr, self.mv_node = [host[cuts[j]:cuts[j + 1]] for j in range(5)]
+        self.tail = words[cuts[-1]:]
+        return self
+
 
 def search_plan(p, i, pins, group_ptr=None):
     """Predictor.search_plan: see there."""

@@ -8,6 +8,7 @@
     python tools/bench_placement.py --commit       (one commit_moves call next to the host's route to the same pins, see below)
     python tools/bench_placement.py --refine       (refine_moves: the host loop next to resident=True, see below)
     python tools/bench_placement.py --swaps        (one swap_moves / commit_swaps call over pairs of pin groups, see below)
+    python tools/bench_placement.py --critical     (one critical_plan call over every cell of a design, refine_cells, see below)
 
 The designs are tests/place_cases.placed(config_design('B', i)): seeded local boxes, masks rasterised from the pins.  Rows:
   rebuild_host / rebuild_device   the only way to follow a move WITHOUT placement mode: rasterise the moved pins
@@ -87,6 +88,18 @@ rounds) next to the host's route to the same pins (swap_host_route_*: swap_moves
 update(0, pin_x=, pin_y=)).  swap_moves' tables must equal, bitwise, score_host fed with the trial route's predictions; the
 two commits must leave the same pins and return the same selection, and the predict() that follows must have exactly the
 predicted sum.  Between commits the pins go home and a predict() runs, outside every clock.  Per row the median over `rounds`.
+
+--critical [--radius 2] [--passes 4] [--min-gain 0], on the same designs (nothing of the above is run), required times at the
+median prediction, slack_below 0: a cell set that covers every node of design 0, as cells of 1 pin (cells1) and as cells of 8
+(cells8).  ONE Predictor.critical_plan call under one host clock (critical_plan_*: call_ms) and its parts, each between
+synchronisations of its own (critical_parts_*: count, the three scans, the size read, fill, the copy back and decoding); next
+to it, alternating inside the same rounds, the host's route to the same plan (critical_host_route_*: the download of the kept
+predictions, cells.critical_host, search_plan).  Then ONE refine_cells call from the pins at home with patch=True
+(refine_cells_patched_*) and with a predict() per pass (refine_cells_predict_per_pass_*), and ONE refine_moves(resident=True)
+call over the plan of ALL cells (refine_moves_resident_all_*): what searching everything costs, and - critical_outputs_* - what
+it gains next to the critical cells alone.  The two routes must build the same plan, and the two loops must return the same
+passes.  Between calls the pins go home and a predict() runs, outside every clock.  Per row the median over `rounds`, in which
+the rows alternate; the all-cells rows alternate in rounds of their own behind the others.
 Needs a GPU."""
 import argparse
 import copy
@@ -980,6 +993,124 @@ def near_swaps_rows(a, emit, designs, ids, pmodel, cnn, dev):
              patched_is_faster=bool(med['patched']['per_pass_ms'] < med['predicted']['per_pass_ms']))
 
 
+def critical_rows(a, emit, designs, ids, pmodel, cnn, dev):
+    """--critical: Predictor.critical_plan over a cell set that covers every node of design 0 - cells of 1 pin and cells of 8 -
+    next to the host's route to the same plan (a download of the kept predictions, cells.critical_host, search_plan), its parts
+    timed apart, a pass of refine_cells(patch=True) next to patch=False, and a pass of refine_moves(resident=True) over the plan of
+    ALL cells - what searching everything costs, and gains -, in the same run."""
+    from mmft import cells as CL
+    d = designs[0]
+    median = float(Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, graphed=False).predict()[0].median())
+    for q in designs:
+        q.required_time[:] = median
+    p = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids, placement=True, trials=True)
+    for _ in range(3):
+        base = p.predict()[0].clone()
+    assert p._replay.graph is not None
+    N = int(d.N)
+    order = np.random.default_rng(7).permutation(N).astype(np.int64)
+    n8 = N // 8
+    sets = {'cells1': p.cell_set(0, order), 'cells8': p.cell_set(0, order[:8 * n8], np.arange(0, 8 * n8 + 1, 8, dtype=np.int64))}
+    home_x, home_y = np.asarray(d.pin_x).copy(), np.asarray(d.pin_y).copy()
+    thr, radius = 0.0, a.radius
+    kw = dict(scale_log2=a.scale_log2, max_rows=a.max_rows, min_gain=a.min_gain)
+    emit(row='critical_shapes', designs=a.designs, map=designs[0].map_size, rows=int(p.T), nodes_design0=N, row_lo=sets['cells1'].row_lo,
+         span=sets['cells1'].span, incidence=int(p._trial.rows_of_pin[1].shape[0]), radius=radius, passes=a.passes, slack_below=thr)
+
+    def go_home():
+        p.update(0, pin_x=home_x, pin_y=home_y)
+        p.predict()
+        torch.cuda.synchronize()
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return out, 1e3 * (time.perf_counter() - t0)
+
+    def device_once(cs):
+        plan, ms = clock(lambda: p.critical_plan(cs, thr))
+        return plan, dict(call_ms=ms)
+
+    def parts_once(cs):
+        ms = {}
+
+        def run(name, fn):
+            ms[name + '_ms'] = ms.get(name + '_ms', 0.0) + clock(fn)[1]
+        CL.critical_plan(p, cs, thr, timed=run)
+        return ms
+
+    def host_once(cs):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        pred, required = p._trial.kept['pred'].cpu().numpy().reshape(-1), p.slack.required.cpu().numpy()
+        t1 = time.perf_counter()
+        chosen, _ = CL.critical_host(p._trial.rows_of_pin, cs.node_off, cs.pins, cs.cell_ptr, pred, required, cs.row_lo, cs.span, thr)
+        t2 = time.perf_counter()
+        plan = p.search_plan(0, *CL.pins_of(cs.pins, cs.cell_ptr, chosen))
+        torch.cuda.synchronize()
+        t3 = time.perf_counter()
+        return plan, dict(download_ms=1e3 * (t1 - t0), critical_host_ms=1e3 * (t2 - t1), search_plan_ms=1e3 * (t3 - t2), call_ms=1e3 * (t3 - t0))
+
+    def refine_once(cs, patch):
+        res, ms = clock(lambda: p.refine_cells(cs, radius, passes=a.passes, slack_below=thr, patch=patch, **kw))
+        go_home()
+        return res, dict(call_ms=ms, passes=len(res), per_pass_ms=ms / max(len(res), 1))
+
+    def everything_once(plan):
+        res, ms = clock(lambda: p.refine_moves(plan, radius, passes=a.passes, resident=True, **kw))
+        go_home()
+        return res, dict(call_ms=ms, passes=len(res), per_pass_ms=ms / max(len(res), 1))
+
+    tns = lambda q: -q * 2.0 ** -a.scale_log2
+    all_plans = {}
+    for nm, cs in sets.items():                                         # the routes agree
+        got, want = device_once(cs)[0], host_once(cs)[0]
+        same = all(np.array_equal(getattr(got, k), getattr(want, k)) for k in ('grow_ptr', 'grow_row', 'grow_grp', 'mv_ptr', 'mv_node')) and \
+            torch.equal(got.ints, want.ints)
+        on_dev, on_host = refine_once(cs, True)[0], refine_once(cs, False)[0]
+        keys = ('n_selected', 'sum_dq', 'predicted_nsum')
+        agree = len(on_dev) == len(on_host) and all(u[k] == v[k] for u, v in zip(on_dev, on_host) for k in keys) and \
+            all(np.array_equal(u['cell'], v['cell']) for u, v in zip(on_dev, on_host))
+        all_plans[nm] = p.critical_plan(cs, None)
+        whole = everything_once(all_plans[nm])[0]
+        emit(row=f'critical_outputs_{nm}', cells=cs.C, pins=cs.M, G=got.G, R=got.R, share_selected=got.G / cs.C, device_equals_host_route=bool(same),
+             passes=len(on_dev), cells_per_pass=[len(r['cell']) for r in on_dev], selected_per_pass=[r['n_selected'] for r in on_dev],
+             base_tns=tns(on_dev[0]['base']['nsum']), final_tns=tns(on_dev[-1]['predicted_nsum']), patched_equals_predict_per_pass=bool(agree),
+             all_cells_G=all_plans[nm].G, all_cells_R=all_plans[nm].R, all_cells_passes=len(whole),
+             all_cells_selected_per_pass=[r['n_selected'] for r in whole], all_cells_final_tns=tns(whole[-1]['predicted_nsum']))
+        assert same and agree
+    assert torch.equal(p.predict()[0], base)
+    rows = {nm: dict(device=[], parts=[], host=[], patched=[], predicted=[], everything=[]) for nm in sets}
+    for _ in range(a.rounds):                                           # the rows alternate inside a round
+        for nm, cs in sets.items():
+            rows[nm]['device'].append(device_once(cs)[1])
+            rows[nm]['parts'].append(parts_once(cs))
+            rows[nm]['host'].append(host_once(cs)[1])
+            rows[nm]['patched'].append(refine_once(cs, True)[1])
+            rows[nm]['predicted'].append(refine_once(cs, False)[1])
+    for _ in range(a.rounds):                                           # in rounds of its own: a call over every cell copies hundreds of
+        for nm in sets:                                                 # megabytes back, and the calls timed next to it showed it
+            rows[nm]['everything'].append(everything_once(all_plans[nm])[1])
+    for nm, cs in sets.items():
+        med = {w: {k: statistics.median(r[k] for r in rs) for k in rs[0]} for w, rs in rows[nm].items()}
+        span = lambda w, k='call_ms': {k + '_min': min(r[k] for r in rows[nm][w]), k + '_max': max(r[k] for r in rows[nm][w]),
+                                       k + '_rounds': [round(r[k], 3) for r in rows[nm][w]]}
+        emit(row=f'critical_plan_{nm}', cells=cs.C, rounds=a.rounds, **{k + '_median': v for k, v in med['device'].items()}, **span('device'))
+        emit(row=f'critical_parts_{nm}', cells=cs.C, rounds=a.rounds, **{k + '_median': v for k, v in med['parts'].items()})
+        emit(row=f'critical_host_route_{nm}', cells=cs.C, rounds=a.rounds, **{k + '_median': v for k, v in med['host'].items()}, **span('host'),
+             speedup_over_host_route=med['host']['call_ms'] / med['device']['call_ms'],
+             device_is_faster=bool(med['device']['call_ms'] < med['host']['call_ms']))
+        emit(row=f'refine_cells_patched_{nm}', cells=cs.C, rounds=a.rounds, **{k + '_median': v for k, v in med['patched'].items()},
+             **span('patched', 'per_pass_ms'))
+        emit(row=f'refine_cells_predict_per_pass_{nm}', cells=cs.C, rounds=a.rounds, **{k + '_median': v for k, v in med['predicted'].items()},
+             **span('predicted', 'per_pass_ms'), per_pass_ratio_predict_over_patched=med['predicted']['per_pass_ms'] / med['patched']['per_pass_ms'],
+             patched_is_faster=bool(med['patched']['per_pass_ms'] < med['predicted']['per_pass_ms']))
+        emit(row=f'refine_moves_resident_all_{nm}', groups=all_plans[nm].G, rounds=a.rounds, **{k + '_median': v for k, v in med['everything'].items()},
+             **span('everything', 'per_pass_ms'), per_pass_ratio_all_over_critical=med['everything']['per_pass_ms'] / med['patched']['per_pass_ms'])
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--designs', type=int, default=8)
@@ -1004,6 +1135,7 @@ def main():
     ap.add_argument('--passes', type=int, default=4, help='--refine: the passes of one refine_moves call')
     ap.add_argument('--near-swaps', action='store_true')
     ap.add_argument('--reach', type=int, default=2, help='--near-swaps: groups pair whose anchors lie within this many map cells')
+    ap.add_argument('--critical', action='store_true')
     ap.add_argument('--out', default=None)
     a = ap.parse_args()
     assert torch.cuda.is_available(), 'needs a GPU'
@@ -1053,6 +1185,10 @@ def main():
     if a.near_swaps:
         with lib.math_mode('bf16'), torch.no_grad():
             near_swaps_rows(a, emit, designs, ids, pmodel, cnn, dev)
+        return
+    if a.critical:
+        with lib.math_mode('bf16'), torch.no_grad():
+            critical_rows(a, emit, designs, ids, pmodel, cnn, dev)
         return
     with lib.math_mode('bf16'), torch.no_grad():
         static = Predictor(pmodel, cnn, designs, dev, path_ids_per_design=ids)
